@@ -16,6 +16,10 @@ FLOPs the kernel EXECUTES, so frac <= 1; the algorithmic rate of a Winograd kern
 oracle on the host cores, rank 0 at N=1 only), ``sampling`` (DDIM-50 + CFG w=1 images/s, the second half of the metric),
 ``multi_gpu`` (N > 1: backend, rank count, per-rank step times, exposed all-reduce time), ``secondary`` (BASELINE configs[3]:
 CelebA 64x64 train step + DDIM-50 CFG sampling + its own cpu_baseline).
+
+``--dump-outputs DIR`` writes what the timed path computed as DIR/<name>.npy (float32): the loss of the last timed train step and a fixed,
+seeded sample of the parameters, gradients, Adam moments and EMA shadow it left behind (written after the timed region, before any
+later step), and the images of the DDIM sampling leg.  The inputs depend on the arguments alone, so two builds can be compared array by array.
 """
 import argparse
 import json
@@ -227,7 +231,47 @@ def executed_share(kernel_name):
     return 1.0
 
 
-def sample_once(diffusion, model, labels, SB, RES, T, W, device, rank, world, barrier):
+DUMP_LIMIT_BYTES = 64 * 2 ** 20           # --dump-outputs: total size cap of the .npy files
+DUMP_SAMPLE = 2 ** 20                     # elements drawn from each flat training buffer (60.8 M elements on the headline model)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def flat_sample_index(n, k=DUMP_SAMPLE, seed=DUMP_SAMPLE_SEED):
+    """the fixed, seeded positions --dump-outputs reads from a flat buffer of n elements (sorted; all of them when n <= k)"""
+    import numpy as np
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=k, replace=False))
+
+
+_dumped_bytes = [0]
+
+
+def write_dump(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float32 (float64 stays float64), within DUMP_LIMIT_BYTES over the run"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    outs = {k: np.ascontiguousarray(v, dtype=np.float64 if v.dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    _dumped_bytes[0] += sum(a.nbytes for a in outs.values())
+    assert _dumped_bytes[0] <= DUMP_LIMIT_BYTES, f"--dump-outputs would write {_dumped_bytes[0]} bytes (limit {DUMP_LIMIT_BYTES})"
+    for k, a in outs.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+
+
+def train_step_outputs(trainer, loss):
+    """what the last timed train step hands its caller: the mean loss, and the model state the step left behind (parameters, gradients,
+    Adam moments, EMA shadow) as one fixed, seeded sample of DUMP_SAMPLE positions of the flat buffers (flat_sample_index)"""
+    flat = trainer.flat
+    idx = torch.from_numpy(flat_sample_index(flat.numel)).to(flat.p.device)
+    bufs = {"params": flat.p, "grads": flat.g, "adam_m": flat.m, "adam_v": flat.v}
+    if flat.ema is not None:
+        bufs["ema"] = flat.ema
+    out = {"loss": loss.detach().reshape(1).float().cpu().numpy()}
+    out.update({k: v.index_select(0, idx).cpu().numpy() for k, v in bufs.items()})
+    return out
+
+
+def sample_once(diffusion, model, labels, SB, RES, T, W, device, rank, world, barrier, dump_dir=None):
     """DDIM-T + classifier-free guidance over SB images per GPU (2*SB UNet rows per reverse step): images/s + roofline"""
     model.eval()
     lab = labels[:SB].clone()
@@ -241,6 +285,8 @@ def sample_once(diffusion, model, labels, SB, RES, T, W, device, rank, world, ba
         tmax = torch.tensor([ds], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         ds = float(tmax.item())
+    if dump_dir is not None and rank == 0:
+        write_dump(dump_dir, {"ddim_samples": out.cpu().numpy()})
     # share of the algorithmic FLOPs the matrix cores execute in THIS sampler, from the launches two reverse steps record (each launch
     # carries the 2*M*N*K of the op it implements; executed_share() says what its kernel really multiplies)
     exec_frac, rec_gflop, dominant, table = W["fwd_exec_frac"], None, None, None
@@ -305,8 +351,9 @@ def sample_once(diffusion, model, labels, SB, RES, T, W, device, rank, world, ba
             "finite": bool(torch.isfinite(out).all())}
 
 
-def run_training(wl, B, steps, warmup, device, rank, world, barrier, sample_steps, extras=True, uint8_input=False):
-    """build the workload's model + trainer, time `steps` train steps, then the live per-kernel roofline of two more"""
+def run_training(wl, B, steps, warmup, device, rank, world, barrier, sample_steps, extras=True, uint8_input=False, dump_dir=None):
+    """build the workload's model + trainer, time `steps` train steps, then the live per-kernel roofline of two more; `dump_dir`: what the
+    last timed step computed goes there as .npy files (rank 0), before any later step changes it"""
     import v_diffusion
     from v_diffusion import _hip
     from v_diffusion.trainer import HotPathTrainer
@@ -367,6 +414,8 @@ def run_training(wl, B, steps, warmup, device, rank, world, barrier, sample_step
         dist.all_gather(parts, mine)
         rank_ms = [float(q.item()) for q in parts]
     ms_per_step = dt / steps * 1e3
+    if dump_dir is not None and rank == 0:
+        write_dump(dump_dir, train_step_outputs(trainer, loss))
     res = dict(model=model, diffusion=diffusion, labels=labels, ms_per_step=ms_per_step, value=world * B * steps / dt,
                final_loss=float(loss.item()), name=W["name"], res=RES, fwd_gflop=W["fwd_gflop"], W=W, rank_ms=rank_ms)
 
@@ -543,7 +592,13 @@ def main():
     ap.add_argument("--sample-steps", type=int, default=50)
     ap.add_argument("--config", choices=["cifar10", "celeba"], default="cifar10",
                     help="cifar10 = the headline workload (BASELINE configs[1]); celeba = configs[3] as the primary line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed as DIR/<name>.npy (float32, 64 MB at most): the last timed train step's loss and a "
+                         "fixed, seeded sample of the parameters, gradients, Adam moments and EMA it left behind, and the DDIM samples of the "
+                         "sampling leg; the inputs depend on the arguments only, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     wl = args.config
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -589,7 +644,7 @@ def main():
                  "note": "measured on this box immediately before the timed steps; the train step itself holds 2.33 GHz on a 2.40 GHz box "
                          "(profiles/r05_clock_by_kernel.txt) -- scale by in_kernel_clock_mhz / 2400 when comparing boxes"}
     r = run_training(wl, B, args.steps, args.warmup, device, rank, world, barrier, args.sample_steps, extras=not args.no_extras,
-                     uint8_input=args.uint8_input)
+                     uint8_input=args.uint8_input, dump_dir=args.dump_outputs)
     model, diffusion, labels, RES = r["model"], r["diffusion"], r["labels"], r["res"]
     fwd_gflop = r["fwd_gflop"]
     hbm_peak = torch.cuda.max_memory_allocated(device)
@@ -597,7 +652,8 @@ def main():
     # ---- sampling: DDIM-50 + classifier-free guidance (w=1): 2B UNet rows per step
     sampling = None
     if not args.no_sample:
-        sampling = sample_once(diffusion, model, labels, B, RES, args.sample_steps, r["W"], device, rank, world, barrier)
+        sampling = sample_once(diffusion, model, labels, B, RES, args.sample_steps, r["W"], device, rank, world, barrier,
+                               dump_dir=args.dump_outputs)
 
     # ---- secondary workload (BASELINE configs[3]): CelebA 64x64, per-GPU batch 128 -- a few train steps, then DDIM-50 + CFG
     # sampling of 128 images (the second half of the north-star metric on CelebA-shaped tensors), then the CPU oracle beside it
