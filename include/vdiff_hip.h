@@ -427,6 +427,28 @@ int vd_adamw_ema_flagged(float* p, const float* g, float* m, float* v, float* em
                          float bc1, float bc2, float ema_decay, int64_t r_lo, int64_t r_hi, const float* r_flag, int32_t* r_steps,
                          double r_beta1, double r_beta2, void* stream);
 
+/* ------------------------------------------------------------------ k-NN precision / recall (metrics.hip)
+ * The improved precision / recall metric (reference v_diffusion/metrics/precision_recall.py) on fp16 feature rows: a tiled fp16
+ * distance GEMM (v_mfma_f32_32x32x16_f16, fp32 accumulation) whose output is reduced per row as it is produced -- no distance
+ * matrix in memory (the reference materialises it through torch.cdist and copies it to the host, :50-62).
+ * Features: [n][d] IEEE binary16 bits, rows contiguous, base 16-byte aligned, d a positive multiple of 64 (pad with zeros: a zero
+ * column changes no distance).  Norms: the fp32 squared row norms written by vd_rows_sqnorm_f16 for those rows (the same MFMA
+ * chain as the distance products, so identical rows are at distance exactly 0).
+ * d2 = max(|x|^2 + |y|^2 - 2 x.y, 0) in fp32, distance = sqrtf(d2) correctly rounded.  Fixed-order, no atomics: bitwise
+ * reproducible.  Any n >= 1 on either side; 64-bit row offsets. */
+int    vd_rows_sqnorm_f16(const uint16_t* x, int64_t n, int32_t d, float* sq, void* stream);
+/* out[i] = the kth-th smallest distance from q_i to the rows of c, counted with multiplicity (torch.kthvalue(kth) of the distance
+ * row: for c == q the self-distance 0 is one of them); 1 <= kth <= min(16, nc).  ws: vd_knn_kth_ws_bytes(nq, nc, kth) bytes,
+ * 16-byte aligned (partial lists of the column splits, O(nq kth)). */
+size_t vd_knn_kth_ws_bytes(int64_t nq, int64_t nc, int32_t kth);
+int    vd_knn_kth_f16(const uint16_t* q, const float* q_sq, int64_t nq, const uint16_t* c, const float* c_sq, int64_t nc, int32_t d,
+                      int32_t kth, float* out, void* ws, size_t ws_bytes, void* stream);
+/* hit[i] = 1 if some j has distance(q_i, s_j) <= radius[j] (fp32 radii), else 0: the coverage test of calc_pr (reference
+ * precision_recall.py:177-206).  ws: vd_manifold_hits_ws_bytes(ns) bytes (per-support-row d2 thresholds). */
+size_t vd_manifold_hits_ws_bytes(int64_t ns);
+int    vd_manifold_hits_f16(const uint16_t* q, const float* q_sq, int64_t nq, const uint16_t* s, const float* s_sq, const float* radius,
+                            int64_t ns, int32_t d, uint8_t* hit, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,6 +125,11 @@ _SIGNATURES = {
                                _f32, _f32, _vp]),
     "vd_adamw_ema_flagged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64,
                                        _vp, _vp, _f64, _f64, _vp]),
+    "vd_rows_sqnorm_f16": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
+    "vd_knn_kth_ws_bytes": (_sz, [_i64, _i64, _i32]),
+    "vd_knn_kth_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
+    "vd_manifold_hits_ws_bytes": (_sz, [_i64]),
+    "vd_manifold_hits_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # extra entry points of libvdiff_hip_probe.so (built with -DVD_PROBES; tests/probe/*.py load it through VDIFF_HIP_LIB): bound when
@@ -793,3 +798,68 @@ def adamw_ema_flagged(p, g, m, v, ema, gnorm_sq, max_norm, lr, b1, b2, eps, wd, 
     _check(lib().vd_adamw_ema_flagged(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(gnorm_sq), max_norm, lr, b1, b2, eps,
                                       wd, bc1, bc2, ema_decay, int(r_lo), int(r_hi), ptr(r_flag), ptr(r_steps), float(b1), float(b2),
                                       stream()), "vd_adamw_ema_flagged")
+
+
+# ----------------------------------------------------------------------------------------------- k-NN precision / recall (metrics.hip)
+KNN_K_STEP = 64                # feature length granule of the distance kernels (zero padding changes no distance)
+
+
+def features_f16(x):
+    """[n, d] fp16 device features as the distance kernels take them: contiguous, 16-byte aligned, d zero-padded to a multiple of
+    KNN_K_STEP (a copy only when one of those does not hold already)"""
+    if not x.is_cuda:
+        raise HipError("v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)")
+    if x.dtype != torch.float16 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
+        raise HipError(f"features must be a non-empty [n, d] float16 tensor, got {x.dtype} {tuple(x.shape)}")
+    pad = -x.shape[1] % KNN_K_STEP
+    if pad or not x.is_contiguous() or x.data_ptr() % 16:
+        x = torch.nn.functional.pad(x, (0, pad)).contiguous()
+    return x
+
+
+def _dev_f16(x):
+    if not (x.is_cuda and x.dtype == torch.float16 and x.dim() == 2 and x.is_contiguous() and x.data_ptr() % 16 == 0
+            and x.shape[1] % KNN_K_STEP == 0):
+        raise HipError("distance kernels take features prepared by features_f16 (device fp16, contiguous, aligned, padded d)")
+    return x.data_ptr()
+
+
+def _dev_f32(x, n):
+    if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.numel() == n):
+        raise HipError(f"expected a contiguous device float32 tensor of {n} elements")
+    return x.data_ptr()
+
+
+def rows_sqnorm_f16(x):
+    """fp32 squared norms of the rows of prepared features x (features_f16)"""
+    n, d = x.shape
+    sq = torch.empty(n, dtype=torch.float32, device=x.device)
+    _check(lib().vd_rows_sqnorm_f16(_dev_f16(x), n, d, sq.data_ptr(), stream()), "vd_rows_sqnorm_f16")
+    return sq
+
+
+def knn_kth_f16(q, q_sq, c, c_sq, kth):
+    """fp32 [nq]: kth-th smallest distance from each row of q to the rows of c (with multiplicity), prepared features + their norms"""
+    nq, d = q.shape
+    nc = c.shape[0]
+    if c.shape[1] != d:
+        raise HipError(f"feature lengths differ: {d} vs {c.shape[1]}")
+    out = torch.empty(nq, dtype=torch.float32, device=q.device)
+    nb = lib().vd_knn_kth_ws_bytes(nq, nc, kth)
+    ws = workspace(nb, q.device, "knn")
+    _check(lib().vd_knn_kth_f16(_dev_f16(q), _dev_f32(q_sq, nq), nq, _dev_f16(c), _dev_f32(c_sq, nc), nc, d, kth, out.data_ptr(),
+                                ws.data_ptr(), ws.numel() * 4, stream()), "vd_knn_kth_f16")
+    return out
+
+
+def manifold_hits_f16(q, q_sq, s, s_sq, radius):
+    """uint8 [nq]: 1 where a row of q lies within radius[j] (fp32) of some support row s_j, else 0"""
+    nq, d = q.shape
+    ns = s.shape[0]
+    if s.shape[1] != d:
+        raise HipError(f"feature lengths differ: {d} vs {s.shape[1]}")
+    hit = torch.empty(nq, dtype=torch.uint8, device=q.device)
+    ws = workspace(lib().vd_manifold_hits_ws_bytes(ns), q.device, "knn_hits")
+    _check(lib().vd_manifold_hits_f16(_dev_f16(q), _dev_f32(q_sq, nq), nq, _dev_f16(s), _dev_f32(s_sq, ns), _dev_f32(radius, ns), ns, d,
+                                      hit.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream()), "vd_manifold_hits_f16")
+    return hit
