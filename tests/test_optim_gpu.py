@@ -2,6 +2,7 @@
 (train.py:158 ``AdamW(model.parameters(), ...)``, train_utils.py:159-168 ``clip_grad_norm_ -> optimizer.step -> zero_grad -> scheduler.step ->
 ema.update``, utils.py:123-190 ``EMA``).  Checked against that loop written with torch's own tools on a second copy of the same model."""
 import copy
+import io
 import math
 import os
 import sys
@@ -147,3 +148,70 @@ def test_gradient_slots_are_not_reused_while_a_gradient_is_alive():
         gd.train_loss(ma, x_0=x0, t=t.clone(), y=y.clone(), noise=noise).mean().backward()
         ptrs.append([p.grad.data_ptr() for p in ma.parameters()])
     assert ptrs[1] == ptrs[2]
+
+
+def test_fused_adamw_gradient_slots_are_not_reused_while_a_gradient_is_alive():
+    """the FusedAdamW slots follow the rule of the default pool (ADVICE: the second of two forwards inside one backward() overwrote the
+    first's undelivered gradients, 2 g2 instead of g1 + g2): two forwards + one backward give the same .grad as the default pool path, and
+    the results of one torch.autograd.grad call keep their values through the next"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from v_diffusion.optim import FusedAdamW
+    (ma, mb), gd, batches = _models()
+    kw = dict(lr=2e-3, betas=(0.9, 0.999), weight_decay=0.01)
+    torch.optim.AdamW(ma.parameters(), **kw)
+    ob = FusedAdamW(mb.parameters(), **kw)
+    torch.save(mb, io.BytesIO())                               # (ADVICE: the module could not be pickled once the optimizer existed)
+    loss = lambda m, b: gd.train_loss(m, x_0=b[0], t=b[1].clone(), y=b[2].clone(), noise=b[3]).mean()
+    for m in (ma, mb):
+        (loss(m, batches[0]) + loss(m, batches[1])).backward()
+    gmax = max(p.grad.abs().max().item() for p in ma.parameters())
+    for (k, pa), (_, pb) in zip(ma.named_parameters(), mb.named_parameters()):
+        assert torch.allclose(pb.grad, pa.grad, rtol=1e-4, atol=1e-6 * gmax), k
+    ob.zero_grad(set_to_none=True)
+    ps = list(mb.parameters())
+    first = torch.autograd.grad(loss(mb, batches[0]), ps)
+    kept = [g.clone() for g in first]
+    second = torch.autograd.grad(loss(mb, batches[1]), ps)
+    assert any(not torch.equal(a, b) for a, b in zip(kept, second))
+    for p, g, c in zip(ps, first, kept):
+        assert torch.equal(g, c), "a torch.autograd.grad result was overwritten by the next call"
+
+
+def test_fused_adamw_resumes_a_torch_checkpoint_saved_before_the_class_embedding_had_a_gradient():
+    """torch.optim.AdamW holds no state for parameters that never received a gradient; FusedAdamW.load_state_dict reads them as the lagging
+    range at step 0 (ADVICE: they were skipped and then updated with the global step's bias corrections), so the updates that follow equal
+    those of torch.optim.AdamW resumed from the same checkpoint"""
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    from v_diffusion.optim import FusedAdamW
+    (ma, mb), gd, batches = _models()
+    kw = dict(lr=2e-3, betas=(0.9, 0.999), weight_decay=0.01)
+    o0 = torch.optim.AdamW(ma.parameters(), **kw)
+    for x0, t, y, noise in batches[:2]:                        # unlabelled: the class embedding receives no gradient
+        gd.train_loss(ma, x_0=x0, t=t.clone(), y=None, noise=noise).mean().backward()
+        o0.step()
+        o0.zero_grad(set_to_none=True)
+    ck = copy.deepcopy(o0.state_dict())
+    assert len(ck["state"]) == len(list(ma.parameters())) - 2
+    mb.load_state_dict(ma.state_dict())
+    oa = torch.optim.AdamW(ma.parameters(), **kw)
+    oa.load_state_dict(ck)
+    ob = FusedAdamW(mb.parameters(), **kw)
+    ob.load_state_dict(ck)
+    assert ob.steps == 2 and ob.lag_steps == 0 and ob.lag_range is not None
+    for x0, t, y, noise in batches[2:]:
+        gd.train_loss(ma, x_0=x0, t=t.clone(), y=y.clone(), noise=noise).mean().backward()
+        gd.train_loss(mb, x_0=x0, t=t.clone(), y=y.clone(), noise=noise).mean().backward()
+        with torch.no_grad():                                   # identical gradients, as in the test above
+            for pa, pb in zip(ma.parameters(), mb.parameters()):
+                pb.grad.copy_(pa.grad)
+        for o in (oa, ob):
+            o.step()
+            o.zero_grad(set_to_none=True)
+    sda, sdb = oa.state_dict()["state"], ob.state_dict()["state"]
+    for i, ((k, pa), (_, pb)) in enumerate(zip(ma.named_parameters(), mb.named_parameters())):
+        tol = 1e-6 * max(pa.abs().max().item(), 1e-3) + 2e-4 * 2e-3
+        assert (pb - pa).abs().max().item() <= tol, k
+        assert int(float(sdb[i]["step"])) == int(float(sda[i]["step"])), (k, sdb[i]["step"], sda[i]["step"])
+    assert {int(float(v["step"])) for v in sda.values()} == {3, 5}

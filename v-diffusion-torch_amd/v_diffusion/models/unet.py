@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from ..flat import owner
 from ..modules import Linear, Conv2d, Sequential, OneHot, GroupNorm32
 
 
@@ -294,18 +295,17 @@ class UNet(nn.Module):
           * default: one tensor per parameter with its OWN storage; it is handed out only while nothing but this module references that
             storage (a ``.grad`` that was not reset -- gradient accumulation -- or a gradient tensor the caller kept get an ordinary fresh
             tensor, exactly as before);
-          * a parameter owned by v_diffusion.optim.FusedAdamW: a view of the optimizer's flat gradient buffer whenever ``param.grad`` is
-            None (the optimizer's documented contract: gradients live in its buffer until the next backward, as with DDP's
-            ``gradient_as_bucket_view=True``)."""
+          * a parameter in a flat store (``flat.FlatParams`` of v_diffusion.optim.FusedAdamW): a view of the store's gradient buffer under the
+            same rule, ``FlatParams.grad_slot`` (the optimizer's documented contract: gradients live in its buffer until the next backward,
+            as with DDP's ``gradient_as_bucket_view=True``)."""
         if self._flat_grad_views is not None:
             return self._flat_grad_views
         pool, use_count = self._grad_pool, torch._C._storage_Use_Count
         out = {}
         for k, p in self.named_parameters():
-            slot = getattr(p, "_vd_flat", None)
-            opt = slot[0]() if slot is not None else None
-            if opt is not None:
-                out[k] = opt.g[slot[1]:slot[1] + p.numel()].view_as(p) if p.grad is None else torch.empty_like(p)
+            own = owner(p)
+            if own is not None:
+                out[k] = own[0].grad_slot(own[1])
                 continue
             t = pool.get(k)
             if t is None or t.device != p.device or t.shape != p.shape:

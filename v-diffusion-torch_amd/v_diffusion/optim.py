@@ -6,10 +6,10 @@ utils.py:123-190).  The reference's ``Trainer.step`` runs ``clip_grad_norm_`` ->
     optimizer = v_diffusion.optim.FusedAdamW(model.parameters(), lr=lr, betas=(beta1, beta2), weight_decay=weight_decay)   # was torch.optim.AdamW(...)
     v_diffusion.optim.use_fused_ema()            # the reference Trainer's ``EMA(model, decay)`` becomes v_diffusion.optim.EMA
 
-``FusedAdamW`` moves the parameters into ONE flat fp32 buffer (``param.data`` become views: the module, ``state_dict()``, DDP and EMA see the
-same tensors as before) and gives every parameter a slot in one flat gradient buffer; the UNet's autograd nodes hand autograd fresh VIEWS of those
-slots (models/unet.py::_grad_targets), which ``AccumulateGrad`` keeps instead of cloning, so ``param.grad`` already lies in the flat buffer when
-``step()`` runs: one vd_adamw_ema launch updates parameters and moments (``EMA.update()`` then is one ``lerp_`` over the flat buffer).  Same
+``FusedAdamW`` moves the parameters into the flat store the hot-path trainer uses too (``flat.FlatParams``, here in ``parameters()`` order:
+``param.data`` become views) and so gives every parameter a slot in one flat gradient buffer; the UNet's autograd nodes hand autograd fresh
+VIEWS of those slots (models/unet.py::_grad_targets), which ``AccumulateGrad`` keeps instead of cloning, so ``param.grad`` already lies in the
+flat buffer when ``step()`` runs: one vd_adamw_ema launch updates parameters and moments (``EMA.update()`` then is one ``lerp_`` over it).  Same
 arithmetic as torch.optim.AdamW (decoupled weight decay, bias corrections, eps outside the square root's bias correction as torch does);
 parameters that received no gradient (a class-conditional network called with y = None) are skipped with their own step count, as torch does.
 There is no CPU path: CPU parameters raise."""
@@ -18,10 +18,7 @@ import weakref
 import torch
 
 from . import _hip
-
-
-def _flat_of(p):
-    return getattr(p, "_vd_flat", None)
+from .flat import FlatParams, owner
 
 
 class FusedAdamW(torch.optim.Optimizer):
@@ -33,23 +30,10 @@ class FusedAdamW(torch.optim.Optimizer):
             raise RuntimeError("FusedAdamW: fp32 parameters on an MI355X only (the v_diffusion hot path has no CPU fallback)")
         _hip.lib()
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, max_grad_norm=max_grad_norm))
-        dev = params[0].device
-        offs, n = [], 0
-        for p in params:
-            offs.append(n)
-            n += (p.numel() + 3) // 4 * 4                                   # every tensor 16-byte aligned
-        self._params, self._offs, self._n = params, offs, n
-        self.p = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.g = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
-        with torch.no_grad():
-            for p, o in zip(params, offs):
-                pv = self.p[o:o + p.numel()].view_as(p)
-                pv.copy_(p)
-                p.data = pv                                                 # the module now lives in the flat buffer
-                p._vd_flat = (weakref.ref(self), o)                         # models/unet.py::_grad_targets and EMA look for this
+        self.flat = FlatParams(list(enumerate(params)))              # named by position in parameters(): the AdamW state's index
+        self.p, self.g, self.m, self.v = self.flat.p, self.flat.g, self.flat.m, self.flat.v
+        self._params, self._offs = params, [self.flat.offsets[i] for i in range(len(params))]
+        self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=params[0].device)
         self.steps = 0                  # updates of the parameters that always receive gradients
         self.lag_range = None           # (lo, hi): the ONE contiguous range that may see no gradient (class embedding), with its own count
         self.skipped = 0                # updates that range sat out (its per-parameter step of torch.optim.AdamW = steps - skipped)
@@ -59,25 +43,17 @@ class FusedAdamW(torch.optim.Optimizer):
         return self.steps - self.skipped
 
     def _gather_grads(self):
-        """param.grad -> the flat gradient buffer (no copy for gradients that already lie in their slot); returns the index range without gradient"""
+        """param.grad -> the flat gradient buffer (no copy for gradients that already lie in their slot); returns the range without gradient"""
         base, missing, stray_dst, stray_src = self.g.data_ptr(), [], [], []
         for i, (p, o) in enumerate(zip(self._params, self._offs)):
             gr = p.grad
             if gr is None:
                 missing.append(i)
             elif gr.data_ptr() != base + 4 * o or not gr.is_contiguous():
-                stray_dst.append(self.g[o:o + p.numel()].view_as(p)); stray_src.append(gr)
+                stray_dst.append(self.flat.view(self.g, i)); stray_src.append(gr)
         if stray_dst:
             torch._foreach_copy_(stray_dst, stray_src)
-        if not missing:
-            return None
-        if missing != list(range(missing[0], missing[-1] + 1)):
-            raise NotImplementedError("FusedAdamW: parameters without a gradient must be adjacent in parameters() order (the class-embedding "
-                                      "tensors of the UNet are); freeze other parameters with requires_grad_(False) before building the optimizer")
-        lo = self._offs[missing[0]]
-        last = missing[-1]
-        hi = self._offs[last] + (self._params[last].numel() + 3) // 4 * 4
-        return (lo, min(hi, self._n))
+        return self.flat.span(missing) if missing else None
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -89,11 +65,10 @@ class FusedAdamW(torch.optim.Optimizer):
         lr, (b1, b2), eps, wd = float(grp["lr"]), grp["betas"], float(grp["eps"]), float(grp["weight_decay"])
         max_norm = grp.get("max_grad_norm") or 0.0
         nograd = self._gather_grads()
-        if nograd is not None or self.lag_range is not None:
-            rng = nograd if nograd is not None else self.lag_range
-            if self.lag_range is not None and rng != self.lag_range:
+        if nograd is not None:
+            if self.lag_range not in (None, nograd):
                 raise NotImplementedError("FusedAdamW: a second range of parameters without gradients")
-            self.lag_range = rng
+            self.lag_range = nograd
         self.steps += 1
         k = self.steps
         if max_norm > 0:
@@ -114,39 +89,16 @@ class FusedAdamW(torch.optim.Optimizer):
 
     # -- torch.optim.AdamW-format state (reference checkpoints: train_utils.py:317-331 saves optimizer.state_dict())
     def state_dict(self):
-        st = {}
-        for i, (p, o) in enumerate(zip(self._params, self._offs)):
-            lag = self.lag_range is not None and self.lag_range[0] <= o < self.lag_range[1]
-            st[i] = {"step": torch.tensor(float(self.lag_steps if lag else self.steps)),
-                     "exp_avg": self.m[o:o + p.numel()].view_as(p).clone(), "exp_avg_sq": self.v[o:o + p.numel()].view_as(p).clone()}
         grp = {k: v for k, v in self.param_groups[0].items() if k != "params"}
-        grp["params"] = list(range(len(self._params)))
-        return {"state": st, "param_groups": [grp]}
+        grp["params"] = list(range(len(self.flat.names)))
+        return {"state": self.flat.adamw_state(self.steps, self.lag_range, self.lag_steps), "param_groups": [grp]}
 
     def load_state_dict(self, sd):
         grp = dict(sd["param_groups"][0])
         grp.pop("params", None)
         self.param_groups[0].update(grp)
-        steps = set()
-        lag = []
-        for i, (p, o) in enumerate(zip(self._params, self._offs)):
-            s = sd["state"].get(i)
-            if s is None:
-                continue
-            self.m[o:o + p.numel()].view_as(p).copy_(s["exp_avg"]); self.v[o:o + p.numel()].view_as(p).copy_(s["exp_avg_sq"])
-            steps.add(int(float(s["step"])))
-        self.steps = max(steps) if steps else 0
-        if len(steps) > 1:
-            low = min(steps)
-            for i, (p, o) in enumerate(zip(self._params, self._offs)):
-                s = sd["state"].get(i)
-                if s is not None and int(float(s["step"])) == low:
-                    lag.append(i)
-            if lag != list(range(lag[0], lag[-1] + 1)) or len(steps) > 2:
-                raise NotImplementedError("FusedAdamW.load_state_dict: more than one group of lagging step counts")
-            last = lag[-1]
-            self.lag_range = (self._offs[lag[0]], min(self._offs[last] + (self._params[last].numel() + 3) // 4 * 4, self._n))
-            self.skipped = self.steps - low
+        self.steps, self.lag_range, lag_steps = self.flat.load_adamw_state(sd["state"])
+        self.skipped = self.steps - lag_steps
 
 
 class EMA:
@@ -161,22 +113,22 @@ class EMA:
         self.decay = decay
         self.num_updates = 0
         self.backup = None
-        self._opt = None
+        self._store = None
         self.shadow = None
         self._build()
 
     def _build(self):
-        """(re)build the shadow in the layout the parameters have NOW: flat if one FusedAdamW owns them all, in order; per tensor otherwise"""
+        """(re)build the shadow in the layout the parameters have NOW: flat if one flat store owns them all, in order; per tensor otherwise"""
         ps = [v for _, v in self._named]
-        owners = {(_flat_of(p)[0]() if _flat_of(p) else None) for p in ps}
-        opt = owners.pop() if len(owners) == 1 else None
+        own = [owner(p) for p in ps]
+        st = own[0][0] if own and own[0] is not None else None
         old = self.shadow
-        if opt is not None and len(opt._params) == len(ps) and all(a is b for a, b in zip(opt._params, ps)):
-            self._opt = weakref.ref(opt)
-            self._shadow_flat = opt.p.clone()
-            self.shadow = {k: self._shadow_flat[o:o + p.numel()].view_as(p) for (k, p), o in zip(self._named, opt._offs)}
+        if st is not None and len(st.names) == len(ps) and all(o is not None and o[0] is st and o[1] == i for o, i in zip(own, st.names)):
+            self._store = weakref.ref(st)
+            self._shadow_flat = st.p.clone()
+            self.shadow = {k: st.view(self._shadow_flat, i) for i, (k, _) in zip(st.names, self._named)}
         else:
-            self._opt, self._shadow_flat = None, None
+            self._store, self._shadow_flat = None, None
             self.shadow = {k: v.detach().clone() for k, v in self._named}
         if old is not None:
             with torch.no_grad():
@@ -185,22 +137,22 @@ class EMA:
 
     @torch.no_grad()
     def update(self):
-        if self._opt is None and all(_flat_of(p) for _, p in self._named):
+        if self._store is None and all(owner(p) is not None for _, p in self._named):
             self._build()                                                  # the optimizer was built after this object: move the shadow
         self.num_updates += 1
         decay = min(self.decay, (1 + self.num_updates) / (10 + self.num_updates))
-        opt = self._opt() if self._opt is not None else None
-        if opt is not None:
-            self._shadow_flat.lerp_(opt.p, 1 - decay)                      # shadow += (1 - decay) (p - shadow), utils.py:144-149
+        st = self._store() if self._store is not None else None
+        if st is not None:
+            self._shadow_flat.lerp_(st.p, 1 - decay)                      # shadow += (1 - decay) (p - shadow), utils.py:144-149
         else:
             torch._foreach_lerp_([self.shadow[k] for k, _ in self._named], [r().data for r in self._refs.values()], 1 - decay)
 
     @torch.no_grad()
     def apply(self):
-        opt = self._opt() if self._opt is not None else None
-        if opt is not None:
-            self.backup = opt.p.clone()
-            opt.p.copy_(self._shadow_flat)
+        st = self._store() if self._store is not None else None
+        if st is not None:
+            self.backup = st.p.clone()
+            st.p.copy_(self._shadow_flat)
         else:
             self.backup = {k: r().detach().clone() for k, r in self._refs.items()}
             for k, r in self._refs.items():
@@ -208,9 +160,9 @@ class EMA:
 
     @torch.no_grad()
     def restore(self):
-        opt = self._opt() if self._opt is not None else None
-        if opt is not None and torch.is_tensor(self.backup):
-            opt.p.copy_(self.backup)
+        st = self._store() if self._store is not None else None
+        if st is not None and torch.is_tensor(self.backup):
+            st.p.copy_(self.backup)
         else:
             for k, r in self._refs.items():
                 r().data.copy_(self.backup[k])

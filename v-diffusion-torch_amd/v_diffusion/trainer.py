@@ -18,6 +18,7 @@ MI355X-first choices
   * clip + AdamW + EMA is two passes over the flat buffers (sum of squares, then one fused update kernel) instead of
     the reference's >= 5 foreach passes.
 """
+import contextlib
 import math
 import os
 
@@ -25,6 +26,7 @@ import torch
 import torch.distributed as dist
 
 from . import _hip
+from .flat import FlatParams
 
 BUCKET_BYTES = 32 << 20
 FLAG_SLOTS = 4            # floats behind the flat gradient buffer that travel with its last bucket (16 bytes: keeps buckets float4-sized)
@@ -39,54 +41,28 @@ def completion_order(model):
     return model.engine().completion_order()
 
 
-class FlatState:
-    """Flat fp32 buffers for parameters / gradients / Adam moments / EMA, with per-tensor views."""
+class FlatState(FlatParams):
+    """The trainer's flat buffers: parameters / gradients / Adam moments laid out in completion order, FLAG_SLOTS floats behind the
+    gradients, the class-embedding range with its device-side step count, and the EMA buffer."""
 
     def __init__(self, model, use_ema=True):
         self.model = model
-        order = completion_order(model)
         params = dict(model.named_parameters())
-        dev = next(model.parameters()).device
-        offs, n = {}, 0
-        for k in order:
-            offs[k] = n
-            n += (params[k].numel() + 3) // 4 * 4                      # keep every tensor 16-byte aligned
-        self.numel, self.offsets, self.order = n, offs, order
-        self.p = torch.zeros(n, dtype=torch.float32, device=dev)
-        # gradients + FLAG_SLOTS floats behind them: slot 0 says "this rank's micro-batch carried labels" (see cls_range below); it rides
-        # in the last gradient bucket, so the rank SUM of the all-reduce makes it one decision for all replicas at no extra collective
-        self.g_all = torch.zeros(n + FLAG_SLOTS, dtype=torch.float32, device=dev)
-        self.g = self.g_all[:n]
-        self.flag = self.g_all[n:n + 1]
-        self.m = torch.zeros(n, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(n, dtype=torch.float32, device=dev)
-        views = {}
-        with torch.no_grad():
-            for k in order:
-                q = params[k]
-                pv = self.p[offs[k]: offs[k] + q.numel()].view_as(q)
-                pv.copy_(q)
-                q.data = pv                                            # the module now lives in the flat buffer
-                views[k] = self.g[offs[k]: offs[k] + q.numel()].view_as(q)
-        self.grad_views = views
-        model._flat_grad_views = views
+        super().__init__([(k, params[k]) for k in completion_order(model)], extra_grad=FLAG_SLOTS, state_order=list(params))
+        # slot 0 behind the gradients says "this rank's micro-batch carried labels" (see cls_range below); it rides in the last gradient
+        # bucket, so the rank SUM of the all-reduce makes it one decision for all replicas at no extra collective
+        self.flag = self.g_all[self.numel:self.numel + 1]
+        self.grad_views = model._flat_grad_views = {k: self.view(self.g, k) for k in self.names}
         self.ema = self.p.clone() if use_ema else None
-        self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=self.p.device)
         self.step_count = 0
         self.ema_updates = 0
         # the class-embedding tensors (unet.py:207-215) are the one parameter group that may see no gradient in a step (a class-
         # conditional network called with y = None: the reference leaves .grad None and torch.optim.AdamW skips those parameters,
         # so their per-parameter step count lags): a contiguous range at the end of the flat buffers with its own step count
-        cls = [k for k in order if k.startswith("class_embed.")]
-        self.cls_names = set(cls)
-        self.cls_range = None
-        if cls:
-            lo = min(offs[k] for k in cls)
-            hi = max(offs[k] + (params[k].numel() + 3) // 4 * 4 for k in cls)
-            assert all(lo <= offs[k] < hi for k in cls) and not any(lo <= offs[k] < hi for k in order if k not in self.cls_names), \
-                "class-embedding tensors are not contiguous in the flat buffer"
-            self.cls_range = (lo, min(hi, n))
-        self.cls_steps_dev = torch.zeros(1, dtype=torch.int32, device=dev)      # advanced by vd_adamw_ema_flagged, never read per step
+        cls = [k for k in self.names if k.startswith("class_embed.")]
+        self.cls_range = self.span(cls) if cls else None
+        self.cls_steps_dev = torch.zeros(1, dtype=torch.int32, device=self.p.device)      # advanced by vd_adamw_ema_flagged, never read per step
 
     @property
     def cls_steps(self):
@@ -100,8 +76,7 @@ class FlatState:
 
     def ema_state_dict(self):
         """EMA shadow as a reference-format state_dict (utils.py:168-175 keeps ``shadow`` per parameter name)."""
-        params = dict(self.model.named_parameters())
-        return {k: self.ema[self.offsets[k]: self.offsets[k] + params[k].numel()].view_as(params[k]) for k in self.order}
+        return {k: self.view(self.ema, k) for k in self.names}
 
 
 class GradReducer:
@@ -114,8 +89,7 @@ class GradReducer:
         self.total = n
         self.bounds = [(a, min(a + per, n)) for a in range(0, n, per)]
         # first flat offset AFTER each parameter, in completion order -> "ready prefix" length
-        params = dict(flat.model.named_parameters())
-        self.end_of = {k: flat.offsets[k] + params[k].numel() for k in flat.order}
+        self.end_of = {k: o + flat.params[k].numel() for k, o in flat.offsets.items()}
         self.works, self.next_bucket = [], 0
         self.trace = None
 
@@ -320,11 +294,17 @@ class HotPathTrainer:
         return self.stats.extract()
 
     # ------------------------------------------------------------------ EMA weights for sampling (utils.py:151-166)
+    @contextlib.contextmanager
     def ema_weights(self):
         """``with trainer.ema_weights(): ...`` runs the body on the EMA shadow.  The reference clones every parameter
         (``EMA.apply``) and copies back (``restore``); here the module's ``.data`` views are re-pointed from the flat
         parameter buffer to the flat shadow buffer and back -- no device traffic at all."""
-        return _EmaSwap(self.flat)
+        assert self.flat.ema is not None, "trainer was built with use_ema=False"
+        self.flat.point(self.flat.ema)
+        try:
+            yield
+        finally:
+            self.flat.point(self.flat.p)
 
     # ------------------------------------------------------------------ checkpoints (train_utils.py:309-348)
     def _lr_now(self):
@@ -336,25 +316,15 @@ class HotPathTrainer:
         feeds to ``UNet.load_state_dict`` / ``torch.optim.AdamW.load_state_dict`` / ``EMA.load_state_dict`` /
         ``LambdaLR.load_state_dict`` (optimizer state indexed by position in ``model.parameters()``)."""
         flat, names = self.flat, [k for k, _ in self.model.named_parameters()]
-        params = dict(self.model.named_parameters())
-
-        def view(buf, k):
-            return buf[flat.offsets[k]: flat.offsets[k] + params[k].numel()].view_as(params[k])
-
         out = {"model": {k: v.detach().clone() for k, v in self.model.state_dict().items()}}
-        state = {}
-        if flat.step_count > 0:
-            for i, k in enumerate(names):
-                steps = flat.cls_steps if k in flat.cls_names else flat.step_count
-                if steps == 0:
-                    continue                 # never received a gradient: torch.optim.AdamW holds no state for it
-                state[i] = {"step": torch.tensor(float(steps)), "exp_avg": view(flat.m, k).clone(), "exp_avg_sq": view(flat.v, k).clone()}
+        # (the class embedding's own step count: torch.optim.AdamW holds no state for a tensor that never received a gradient)
+        state = flat.adamw_state(flat.step_count, flat.cls_range, flat.cls_steps if flat.cls_range else 0)
         group = {"lr": self._lr_now(), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd, "amsgrad": False,
                  "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
                  "initial_lr": self.lr, "params": list(range(len(names)))}
         out["optimizer"] = {"state": state, "param_groups": [group]}
         if flat.ema is not None:
-            out["ema"] = {"decay": self.ema_decay, "shadow": {k: view(flat.ema, k).clone() for k in names},
+            out["ema"] = {"decay": self.ema_decay, "shadow": {k: flat.view(flat.ema, k).clone() for k in names},
                           "num_updates": flat.ema_updates}
         out["scheduler"] = {"base_lrs": [self.lr], "last_epoch": flat.step_count, "_step_count": flat.step_count + 1,
                             "_get_lr_called_within_step": False, "_last_lr": [self._lr_now()], "lr_lambdas": [None]}
@@ -388,34 +358,18 @@ class HotPathTrainer:
         ``module.``-prefixed keys (saved from a DDP wrapper) are accepted as the reference does (:319-323)."""
         ckpt = path_or_dict if isinstance(path_or_dict, dict) else torch.load(path_or_dict, map_location=map_location or "cpu")
         flat, names = self.flat, [k for k, _ in self.model.named_parameters()]
-        params = dict(self.model.named_parameters())
 
         def strip(d):
             return {(k[7:] if k.startswith("module.") else k): v for k, v in d.items()}
-
-        def view(buf, k):
-            return buf[flat.offsets[k]: flat.offsets[k] + params[k].numel()].view_as(params[k])
 
         self.model.load_state_dict(strip(ckpt["model"]))
         with torch.no_grad():
             opt = ckpt.get("optimizer")
             if opt is not None:
-                st = opt["state"]
-                ncls = len(flat.cls_names)
-                assert len(st) in (0, len(names), len(names) - ncls), "optimizer state does not match the parameter list"
-                flat.m.zero_(); flat.v.zero_()
-                steps, csteps = set(), set()
-                for i, k in enumerate(names):
-                    e = st.get(i, st.get(str(i)))
-                    if e is None:
-                        continue
-                    view(flat.m, k).copy_(e["exp_avg"])
-                    view(flat.v, k).copy_(e["exp_avg_sq"])
-                    (csteps if k in flat.cls_names else steps).add(int(e["step"]))
-                # (only the class-embedding tensors may lag: they are the one group a step can leave without a gradient)
-                assert len(steps) <= 1 and len(csteps) <= 1, "per-parameter step counts differ"
-                flat.step_count = steps.pop() if steps else 0
-                flat.cls_steps = csteps.pop() if csteps else 0
+                steps, lag, lag_steps = flat.load_adamw_state(opt["state"])
+                if lag is not None and lag != flat.cls_range:      # (the class embedding is the one group a step can leave without a gradient)
+                    raise NotImplementedError("optimizer state: per-parameter step counts differ outside the class embedding")
+                flat.step_count, flat.cls_steps = steps, lag_steps
             ema = ckpt.get("ema")
             if ema is not None and flat.ema is not None:
                 shadow = strip(ema["shadow"])
@@ -423,7 +377,7 @@ class HotPathTrainer:
                 if missing:
                     raise RuntimeError(f"EMA key mismatch: {sorted(missing)[:4]} ...")
                 for k in names:
-                    view(flat.ema, k).copy_(shadow[k])
+                    flat.view(flat.ema, k).copy_(shadow[k])
                 flat.ema_updates = int(ema["num_updates"])
                 self.ema_decay = float(ema.get("decay", self.ema_decay))
             sch = ckpt.get("scheduler")
@@ -439,21 +393,3 @@ class HotPathTrainer:
                               f"continues from its fresh seed and will replay the t/noise stream it drew before the checkpoint")
         return ckpt.get("epoch", 0)
 
-
-class _EmaSwap:
-    def __init__(self, flat):
-        self.flat = flat
-
-    def _point(self, buf):
-        flat = self.flat
-        for k, q in flat.model.named_parameters():
-            q.data = buf[flat.offsets[k]: flat.offsets[k] + q.numel()].view_as(q)
-
-    def __enter__(self):
-        assert self.flat.ema is not None, "trainer was built with use_ema=False"
-        self._point(self.flat.ema)
-        return self
-
-    def __exit__(self, *exc):
-        self._point(self.flat.p)
-        return False
