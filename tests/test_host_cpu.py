@@ -316,6 +316,27 @@ def test_step_coefficients_fold_the_eps_form(golden_dir):
         assert abs(k[3] * xt + k[4] * x0h - want) <= 1e-5 * max(1.0, abs(want))
 
 
+def test_step_coefficients_keep_the_raw_eps_of_an_unclipped_eps_network(golden_dir):
+    """x0eps_coef=True, model_out_type "eps", no clipping: the reference takes the network output itself as eps (:338-347), so its
+    weight goes to the kernel unfolded (k[7]) and x_t gets none; every other combination leaves k[7] at zero"""
+    import v_diffusion
+    g = np.load(os.path.join(golden_dir, "ext_tables.npz"))
+    T = 8
+    sched = v_diffusion.get_logsnr_schedule("cosine")
+    gd = v_diffusion.GaussianDiffusion(sched, T, "eps", "fixed_medium", "snr_trunc", "mse", intp_frac=0.3, x0eps_coef=True)
+    for step in range(T):
+        k, _ = gd._step_coefs(step, use_ddim=False, clip=False)
+        np.testing.assert_allclose([k[7], k[4]], g["ddpm_x0eps_fixed_medium_8"][:2, step], rtol=1e-6)
+        assert k[3] == 0.0
+        kc, _ = gd._step_coefs(step, use_ddim=False, clip=True)
+        assert kc[7] == 0.0 and kc == gd._step_coefs(step, use_ddim=False)[0] and kc[:3] == k[:3] and kc[5:7] == k[5:7]
+    for mot, x0eps in (("v", True), ("x0", True), ("both", True), ("eps", False)):
+        gd = v_diffusion.GaussianDiffusion(sched, T, mot, "fixed_medium", "snr_trunc", "mse", intp_frac=0.3, x0eps_coef=x0eps)
+        for clip in (False, True):
+            assert gd._step_coefs(3, use_ddim=False, clip=clip)[0][7] == 0.0
+            assert gd._step_coefs(3, use_ddim=False, clip=clip)[0] == gd._step_coefs(3, use_ddim=False)[0]
+
+
 def test_public_diffusion_helpers_vs_golden(golden_dir):
     """module-level helpers of reference diffusion.py:19-39,206-250 and GaussianDiffusion.from_model_out_to_pred (:466-490)
     against the reference's numbers (oracle/make_goldens_r2.py).  Tensor-shape / elementwise glue: device-agnostic."""

@@ -22,9 +22,10 @@ __device__ __forceinline__ PredCoef pred_coef(int type, float l) {
     else if (type == OUT_X0) { k.b0x = 1.f; k.a1 = rsqrtf(s0); k.b1x = -expf(0.5f * l); }         // :217-219
     else if (type == OUT_EPS) { k.a0 = rsqrtf(s1); k.b0x = -expf(-0.5f * l); k.b1x = 1.f; }       // :206-208
     else {                                                                                        // :211-214
-        const float r = rsqrtf(s1), e = expf(-0.5f * l), E = expf(0.5f * l);
-        k.a0 = r * s1; k.b0x = s0; k.b0e = -e * s1;
-        k.a1 = rsqrtf(s0) - k.a0 * E; k.b1x = -k.b0x * E; k.b1e = -k.b0e * E;
+        // x0_hat = s0*o_x + s1*(xt/alpha - o_e*sigma/alpha), eps_hat = (xt - alpha*x0_hat)/sigma, in closed form: written as
+        // 1/sigma - a0*alpha/sigma the xt weight of eps_hat is a difference of two numbers near 2.2e4 at logsnr = 20 (true value 4.5e-5)
+        k.a0 = sa; k.b0x = s0; k.b0e = -expf(-0.5f * l) * s1;
+        k.a1 = ss; k.b1x = -sa * ss; k.b1e = s1;
     }
     return k;
 }
@@ -123,7 +124,7 @@ __global__ void loss_bwd_kernel(const LossArgs p, const float* aux, const float*
 
 
 // ---- variational bound terms (diffusion.py:446-464; normal_kl / discretized_gaussian_loglik: functions.py:31-67).
-// coef[b][8] = {a0, b0x, b0e, c1, c2, true_logvar, model_logvar, -}: x0_hat = a0*xt + b0x*o (+ b0e*o_eps),
+// coef[b][8] = {a0, b0x, b0e, c1, c2, true_logvar, model_logvar, a0 - 1}: x0_hat = a0*xt + b0x*o (+ b0e*o_eps),
 // true_mean = c1*xt + c2*x0, model_mean = c1*xt + c2*x0_hat (the posterior mean weights do not depend on the variance type)
 struct BpdArgs {
     const float* x0; const float* xt; const float* out; const float* coef; int type, clip; int n, C; long long HW;
@@ -137,7 +138,7 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdArgs p, float* 
     __shared__ float sh[8];
     const int b = blockIdx.x;
     const float* k = p.coef + 8 * b;
-    const float a0 = k[0], b0x = k[1], b0e = k[2], c1 = k[3], c2 = k[4], tlv = k[5], mlv = k[6];
+    const float a0 = k[0], b0x = k[1], b0e = k[2], c1 = k[3], c2 = k[4], tlv = k[5], mlv = k[6], a0m1 = k[7];
     const float d = tlv - mlv, em = expf(-mlv), ed = expf(d), inv = expf(-0.5f * mlv);
     const long long N = (long long)p.C * p.HW;
     const int Co = p.type == OUT_BOTH ? 2 * p.C : p.C;
@@ -145,15 +146,18 @@ __global__ __launch_bounds__(256) void bpd_terms_kernel(const BpdArgs p, float* 
     float s_kl = 0.f, s_nll = 0.f, s_mse = 0.f;
     for (long long i = threadIdx.x; i < N; i += blockDim.x) {
         const float x0 = p.x0[(long long)b * N + i], xt = p.xt[(long long)b * N + i];
-        float x0h = a0 * xt + b0x * ob[i] + (p.type == OUT_BOTH ? b0e * ob[N + i] : 0.f);
-        if (p.clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
+        const float oe = p.type == OUT_BOTH ? ob[N + i] : 0.f;
+        float x0h = a0 * xt + b0x * ob[i] + b0e * oe;
+        // x0_hat - x0 without forming x0_hat: at high log-SNR the difference is far below one ulp-of-x0 per cent
+        float dx = fmaf(b0e, oe, fmaf(b0x, ob[i], fmaf(a0m1, xt, xt - x0)));
+        if (p.clip && (x0h < -1.f || x0h > 1.f)) { x0h = fminf(fmaxf(x0h, -1.f), 1.f); dx = x0h - x0; }
         const float tm = c1 * xt + c2 * x0, mm = c1 * xt + c2 * x0h;
         s_kl += 0.5f * ((-1.f - d) + (tm - mm) * (tm - mm) * em + ed);
         const float xc = x0 - x0h;
         const float cu = x0 > BPD_CUT ? 1.f : approx_cdf(inv * (xc + BPD_PREC));
         const float cl = x0 < -BPD_CUT ? 0.f : approx_cdf(inv * (xc - BPD_PREC));
         s_nll -= logf(fmaxf(cu - cl - BPD_TOL, 0.f) + BPD_TOL);
-        s_mse += (x0h - x0) * (x0h - x0);
+        s_mse += dx * dx;
         if (pred) pred[(long long)b * N + i] = x0h;
     }
     s_kl = block_sum(s_kl, sh);
@@ -208,11 +212,13 @@ struct StepArgs {
     int type, cfg, last, clip; float* xn; float* xdup; int n, C; long long HW;
 };
 
-// one reverse step for a batch sharing the step index; x0_hat = a0*xt + b0x*o (+ b0e*o_eps), mean = c1*xt + c2*x0_hat
+// one reverse step for a batch sharing the step index; x0_hat = a0*xt + b0x*o (+ b0e*o_eps), mean = c1*xt + c2*x0_hat + c3*o
+// (c3 = k[7]: the weight of the raw network output, for the posterior over (eps, x0) of an eps-network without clipping, where the
+// reference takes the output itself as eps, diffusion.py:338-347 -- rebuilding it as (xt - alpha*x0_hat)/sigma cancels)
 __global__ void sample_step_kernel(const StepArgs p) {
     const long long N = (long long)p.C * p.HW, total = (long long)p.n * N;
     const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
-    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6];
+    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
     const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 * p.C : p.C;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
@@ -223,7 +229,7 @@ __global__ void sample_step_kernel(const StepArgs p) {
             const float* ob = p.out + (b * mul + u) * Co * p.HW;
             float x0h = a0 * xt + b0x * ob[i] + (p.type == OUT_BOTH ? b0e * ob[N + i] : 0.f);
             if (p.clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
-            mean[u] = p.last ? x0h : c1 * xt + c2 * x0h;
+            mean[u] = p.last ? x0h : c1 * xt + c2 * x0h + c3 * ob[i];
         }
         float v = p.cfg ? mean[0] + w * (mean[0] - mean[1]) : mean[0];
         if (p.noise) v += nscale * p.noise[idx];

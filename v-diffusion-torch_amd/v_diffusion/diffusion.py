@@ -214,9 +214,18 @@ def _pred_coefs(model_out_type, lt32):
         return 0.0, 1.0, 0.0
     if model_out_type == "eps":
         return float(s1.rsqrt()), float(-torch.exp(-0.5 * l)), 0.0
-    if model_out_type == "both":
-        return float(s1.rsqrt() * s1), float(s0), float(-torch.exp(-0.5 * l) * s1)
+    if model_out_type == "both":                          # alpha, sigma^2, -alpha*sigma: closed forms, fp64, rounded once (_both_coefs)
+        return tuple(float(v.float()) for v in _both_coefs(l))
     raise NotImplementedError(model_out_type)
+
+
+def _both_coefs(l32):
+    """x0_hat weights of a "both" network, x0_hat = s0*out_x0 + s1*(x_t/alpha - out_eps*sigma/alpha) (reference :211-214), as
+    (alpha, sigma^2, -alpha*sigma) in fp64 from the fp32 log-SNR.  Evaluated in fp32 as ``rsqrt(s1)*s1`` the x_t weight carries up to
+    two ulps; at logsnr >= 12.9, where x0_hat - x_0 is 1e-3 ... 1e-5 of x_0, that shows in the bits-per-dim squared error."""
+    l = l32.double()
+    s1, s0 = torch.sigmoid(l), torch.sigmoid(-l)
+    return s1.sqrt(), s0, -(s1 * s0).sqrt()
 
 
 def _device_ctx(device):
@@ -443,19 +452,23 @@ class GaussianDiffusion:
         ls, lt = logsnr_s.reshape(-1).to(torch.float32), logsnr_t.reshape(-1).to(torch.float32)
         c1, c2, tlv = logsnr_to_posterior(ls, lt, "fixed_small")
         _, _, mlv = logsnr_to_posterior(ls, lt, self.model_var_type, self.intp_frac)
-        s1, s0 = torch.sigmoid(lt), torch.sigmoid(-lt)
-        z = torch.zeros_like(lt)
+        # prediction weights in fp64 from the fp32 log-SNR, rounded once; slot 7 carries a0 - 1, rounded on its own: the squared error
+        # of x0_hat is taken from (a0 - 1)*x_t + (x_t - x_0) + ..., which stays well conditioned where x0_hat - x_0 is 1e-3 ... 1e-5
+        # of x_0 (logsnr >= 12.9) -- through a0 itself one fp32 ulp of the weight is up to 1e-3 of that difference
+        l = lt.double()
+        s1, s0 = torch.sigmoid(l), torch.sigmoid(-l)
+        z = torch.zeros_like(l)
         if self.model_out_type == "v":
             a0, b0x, b0e = s1.sqrt(), -s0.sqrt(), z
         elif self.model_out_type == "x0":
-            a0, b0x, b0e = z, torch.ones_like(lt), z
+            a0, b0x, b0e = z, torch.ones_like(l), z
         elif self.model_out_type == "eps":
-            a0, b0x, b0e = s1.rsqrt(), -torch.exp(-0.5 * lt), z
+            a0, b0x, b0e = s1.rsqrt(), -torch.exp(-0.5 * l), z
         elif self.model_out_type == "both":
-            a0, b0x, b0e = s1.rsqrt() * s1, s0, -torch.exp(-0.5 * lt) * s1
+            a0, b0x, b0e = _both_coefs(lt)
         else:
             raise NotImplementedError(self.model_out_type)
-        return torch.stack([a0, b0x, b0e, c1, c2, tlv, mlv, z], dim=1).contiguous()
+        return torch.stack([a0.float(), b0x.float(), b0e.float(), c1, c2, tlv, mlv, (a0 - 1.0).float()], dim=1).contiguous()
 
     def _loss_term_bpd(self, model_out, x_0, x_t, logsnr_s, logsnr_t, clip_denoised, return_pred=False):
         """(kl, decoder_nll[, pred_x_0]) per sample in bits per dimension -- reference :446-464, one fused kernel."""
@@ -534,8 +547,10 @@ class GaussianDiffusion:
         return loss.sum(dim=1) + prior, loss, prior, mse
 
     # ------------------------------------------------------------------------------------------ sampling
-    def _step_coefs(self, step, use_ddim):
-        """(the 8 floats of vd_sample_step for reverse step ``step`` (python int), the time the network is called with)."""
+    def _step_coefs(self, step, use_ddim, clip=True):
+        """(the 8 floats of vd_sample_step for reverse step ``step`` (python int), the time the network is called with):
+        [a0, b0x, b0e, c1, c2, noise scale, w_guide, c3] with x0_hat = a0*x_t + b0x*out (+ b0e*out_eps) and
+        mean = c1*x_t + c2*x0_hat + c3*out.  ``clip`` (the step's clip_denoised) only matters with ``x0eps_coef``."""
         T = self.sample_timesteps
         st = torch.tensor([step / T, (step + 1) / T], dtype=F64)
         l = self.logsnr_fn(st)                                 # a rescaling schedule rewrites st in place (:105-109)
@@ -547,14 +562,20 @@ class GaussianDiffusion:
             c1, c2, lv = logsnr_to_posterior(ls32, lt32, self.model_var_type, self.intp_frac, x0eps_coef=self.x0eps_coef)
         a0, b0x, b0e = _pred_coefs(self.model_out_type, lt32[0])
         nscale = float(torch.exp(0.5 * lv.float().reshape(-1)[0])) if step > 0 else 0.0
-        c1, c2 = float(c1.reshape(-1)[0]), float(c2.reshape(-1)[0])
+        c1, c2, c3 = float(c1.reshape(-1)[0]), float(c2.reshape(-1)[0]), 0.0
         if self.x0eps_coef:
-            # mean = c1*eps + c2*x0_hat with eps = (x_t - alpha*x0_hat)/sigma (reference :338-347; for an eps-network without
-            # clipping eps is the raw output, the same number): folded on the host into weights of (x_t, x0_hat)
-            l = lt32[0].double()
-            alpha, rsig = float(torch.sigmoid(l).sqrt()), float(torch.sigmoid(-l).rsqrt())
-            c1, c2 = c1 * rsig, c2 - c1 * alpha * rsig
-        return [a0, b0x, b0e, c1, c2, nscale, float(self.w_guide), 0.0], t_net
+            # mean = c1*eps + c2*x0_hat (reference :338-347)
+            if self.model_out_type == "eps" and not clip:
+                # eps is the raw network output: its weight goes to the kernel as it is.  (Folding it into weights of (x_t, x0_hat)
+                # as below rebuilds eps by cancellation: c1/sigma * (x_t - alpha*x0_hat) with 1/sigma up to 2.2e4.)
+                c1, c3 = 0.0, c1
+            else:
+                # eps = (x_t - alpha*x0_hat)/sigma, re-derived from the (clipped) x0_hat as the reference does: folded on the host
+                # into weights of (x_t, x0_hat)
+                l = lt32[0].double()
+                alpha, rsig = float(torch.sigmoid(l).sqrt()), float(torch.sigmoid(-l).rsqrt())
+                c1, c2 = c1 * rsig, c2 - c1 * alpha * rsig
+        return [a0, b0x, b0e, c1, c2, nscale, float(self.w_guide), c3], t_net
 
     def _use_cfg(self, y):
         return (self.w_guide > 0) and (y is not None)
@@ -562,7 +583,7 @@ class GaussianDiffusion:
     def _reverse_step(self, denoise_fn, x_t, x_in, y_in, step, cfg, noise, use_ddim, clip, want_pred, x_next, x_dup):
         B, C = x_t.shape[:2]
         HW = x_t[0, 0].numel()
-        k8, t_net = self._step_coefs(step, use_ddim)
+        k8, t_net = self._step_coefs(step, use_ddim, clip)
         t_in = torch.full((x_in.shape[0],), t_net, dtype=F64, device=x_t.device)
         out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
         mot = _hip.OUT_TYPES[self.model_out_type]
