@@ -450,6 +450,23 @@ size_t vd_manifold_hits_ws_bytes(int64_t ns);
 int    vd_manifold_hits_f16(const uint16_t* q, const float* q_sq, int64_t nq, const uint16_t* s, const float* s_sq, const float* radius,
                             int64_t ns, int32_t d, uint8_t* hit, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------ FID statistics and products (fid.hip)
+ * fp64 accumulation on v_mfma_f64_16x16x4_f64; one workgroup owns each 64 x 64 output tile and walks the whole reduction in order:
+ * no atomics, the same call sequence gives bitwise identical results.
+ * vd_fid_accum: one batch of fp32 activations x[n][d] (row pitch ldx floats) into running fp64 sums about a per-column shift:
+ *   sum[c] += sum_i (x[i][c] - shift[c]),  outer[a][b] += sum_i (x[i][a] - shift[a]) (x[i][b] - shift[b])  (x - shift formed in fp64).
+ *   outer is [d][d] contiguous and only its LOWER TRIANGLE OF 64 x 64 TILES is updated (tile row >= tile column, diagonal tiles in
+ *   full); the caller mirrors it.  With N rows accumulated and delta = sum / N: mean = shift + delta,
+ *   cov = (outer - N delta delta^T) / (N - 1).  shift must stay fixed between resets of sum / outer; vd_fid_shift writes the
+ *   fp32-rounded column means of a batch (the first one), which makes every x - shift and every product exact for data of one scale.
+ *   Domain: n >= 1, d a positive multiple of 16, ldx >= d and a multiple of 4, every pointer 16-byte aligned.
+ * vd_atb_f64: C[m][n] = A^T B for fp64 A[k][m], B[k][n] (row-major, pitches lda / ldb / ldc doubles).
+ *   Domain: k >= 1, m and n positive multiples of 16, lda >= m, ldb >= n, ldc >= n, lda and ldb even, 16-byte aligned pointers. */
+int    vd_fid_shift(const float* x, int64_t n, int32_t d, int64_t ldx, double* shift, void* stream);
+int    vd_fid_accum(const float* x, int64_t n, int32_t d, int64_t ldx, const double* shift, double* sum, double* outer, void* stream);
+int    vd_atb_f64(const double* A, const double* B, double* C, int64_t k, int32_t m, int32_t n, int64_t lda, int64_t ldb, int64_t ldc,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

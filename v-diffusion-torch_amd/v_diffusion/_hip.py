@@ -130,6 +130,9 @@ _SIGNATURES = {
     "vd_knn_kth_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
     "vd_manifold_hits_ws_bytes": (_sz, [_i64]),
     "vd_manifold_hits_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
+    "vd_fid_shift": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
+    "vd_fid_accum": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
+    "vd_atb_f64": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # extra entry points of libvdiff_hip_probe.so (built with -DVD_PROBES; tests/probe/*.py load it through VDIFF_HIP_LIB): bound when
@@ -863,3 +866,45 @@ def manifold_hits_f16(q, q_sq, s, s_sq, radius):
     _check(lib().vd_manifold_hits_f16(_dev_f16(q), _dev_f32(q_sq, nq), nq, _dev_f16(s), _dev_f32(s_sq, ns), _dev_f32(radius, ns), ns, d,
                                       hit.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream()), "vd_manifold_hits_f16")
     return hit
+
+
+# ----------------------------------------------------------------------------------------------- FID statistics / products (fid.hip)
+def _dev_rows(x, dtype, what):
+    """a 2-D device tensor of `dtype` whose rows are contiguous (any row pitch): (pointer, rows, columns, pitch)"""
+    if not x.is_cuda:
+        raise HipError("v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)")
+    if x.dtype != dtype or x.dim() != 2 or x.shape[0] < 1 or x.stride(1) != 1:
+        raise HipError(f"{what} must be a non-empty 2-D {dtype} tensor with contiguous rows, got {x.dtype} {tuple(x.shape)} "
+                       f"strides {tuple(x.stride())}")
+    return x.data_ptr(), x.shape[0], x.shape[1], x.stride(0)
+
+
+def _dev_f64(x, shape):
+    if not (x.is_cuda and x.dtype == torch.float64 and x.is_contiguous() and tuple(x.shape) == tuple(shape)):
+        raise HipError(f"expected a contiguous device float64 tensor of shape {tuple(shape)}")
+    return x.data_ptr()
+
+
+def fid_shift(x, shift):
+    """shift[d] (fp64) = the fp32-rounded column means of the fp32 batch x[n, d]: the centre the running sums of fid_accum refer to"""
+    px, n, d, ldx = _dev_rows(x, torch.float32, "features")
+    _check(lib().vd_fid_shift(px, n, d, ldx, _dev_f64(shift, (d,)), stream()), "vd_fid_shift")
+
+
+def fid_accum(x, shift, sum_, outer):
+    """sum_[d] += sum_i (x_i - shift), outer[d, d] += sum_i (x_i - shift)(x_i - shift)^T in fp64 for the fp32 batch x[n, d]; outer
+    holds the lower triangle of 64 x 64 tiles only (include/vdiff_hip.h)"""
+    px, n, d, ldx = _dev_rows(x, torch.float32, "features")
+    _check(lib().vd_fid_accum(px, n, d, ldx, _dev_f64(shift, (d,)), _dev_f64(sum_, (d,)), _dev_f64(outer, (d, d)), stream()),
+           "vd_fid_accum")
+
+
+def atb_f64(A, B):
+    """fp64 [m, n] = A^T B for fp64 device matrices A[k, m], B[k, n]"""
+    pa, k, m, lda = _dev_rows(A, torch.float64, "A")
+    pb, kb, n, ldb = _dev_rows(B, torch.float64, "B")
+    if kb != k or A.device != B.device:
+        raise HipError(f"A^T B needs operands with the same number of rows on one device: {tuple(A.shape)} vs {tuple(B.shape)}")
+    Cm = torch.empty(m, n, dtype=torch.float64, device=A.device)
+    _check(lib().vd_atb_f64(pa, pb, Cm.data_ptr(), k, m, n, lda, ldb, n, stream()), "vd_atb_f64")
+    return Cm

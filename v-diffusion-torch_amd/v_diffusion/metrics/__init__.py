@@ -1,10 +1,11 @@
 """Evaluation metrics behind the call surface of the reference's v_diffusion.metrics (reference metrics/__init__.py).
 
 The precision / recall metric (ManifoldBuilder, Manifold, calc_pr) is implemented here on the fused k-NN kernels of
-csrc/metrics.hip.  The FID names (InceptionStatistics, get_precomputed, calc_fd) are not re-implemented: like the control-plane
-names of the parent package they resolve lazily from the reference checkout named by ``VDIFF_REFERENCE_ROOT``
-(``v_diffusion_ref.metrics``), so the reference's ``eval.py --metrics pr fid`` runs unchanged with this package first on
-``sys.path``.  ``import v_diffusion`` does not import this subpackage."""
+csrc/metrics.hip.  The FID names (InceptionStatistics, get_precomputed, calc_fd) resolve, by default, lazily from the reference
+checkout named by ``VDIFF_REFERENCE_ROOT`` (``v_diffusion_ref.metrics``) like the control-plane names of the parent package, so
+the reference's ``eval.py --metrics pr fid`` runs unchanged with this package first on ``sys.path``.  With ``VDIFF_NATIVE_FID=1``
+in the environment they resolve to this package's own fid_score module (fp64 statistics and products on the kernels of
+csrc/fid.hip) instead and are always listed.  ``import v_diffusion`` does not import this subpackage."""
 import importlib
 import os
 
@@ -12,10 +13,13 @@ from .precision_recall import Manifold, ManifoldBuilder, calc_pr
 
 _NATIVE = ["ManifoldBuilder", "Manifold", "calc_pr"]
 _DELEGATED = ["InceptionStatistics", "get_precomputed", "calc_fd"]
+_NATIVE_FID = os.environ.get("VDIFF_NATIVE_FID") == "1"
 
 
 def __getattr__(name):
     if name in _DELEGATED:
+        if _NATIVE_FID:
+            return getattr(importlib.import_module(__name__ + ".fid_score"), name)
         from .. import _reference
         _reference()                                   # loads the checkout as v_diffusion_ref (or raises the ImportError)
         return getattr(importlib.import_module("v_diffusion_ref.metrics"), name)
@@ -23,4 +27,4 @@ def __getattr__(name):
 
 
 # `from v_diffusion.metrics import *` (reference eval.py:10) resolves every name of __all__: list the delegated ones only when they can be
-__all__ = _NATIVE + (_DELEGATED if os.environ.get("VDIFF_REFERENCE_ROOT") else [])
+__all__ = _NATIVE + (_DELEGATED if _NATIVE_FID or os.environ.get("VDIFF_REFERENCE_ROOT") else [])
