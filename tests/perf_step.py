@@ -20,8 +20,8 @@ _gemm, _conv, _wgrad = H.gemm, H.conv3x3, H.conv3x3_wgrad
 def timed(key, flops, fn):
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record(); fn(); e1.record()
-    t = H.lib().vd_gemm_last_tile()
-    REC.append((key + f" tile={(t // 1000) % 1000}x{t % 1000}/kt{(t // 1000000) % 100}{'T' if t // 100000000 else ''}", flops, e0, e1))
+    tr, spl, kt, bm, bn = H.tile_fields(H.lib().vd_gemm_last_tile())
+    REC.append((key + f" tile={bm}x{bn}/kt{kt}{'T' if tr or spl else ''}", flops, e0, e1))
 
 
 def gemm(A, B, Cm, M, N, K, **kw):

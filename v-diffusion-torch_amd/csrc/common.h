@@ -27,6 +27,10 @@ int vd_gemm_grouped_wgrad_kblk(const float* const* A, const float* const* B, flo
                                void* stream, int64_t a_kblk, int64_t b_kblk, int32_t slabs_only);   // gemm.hip: grouped weight-gradient GEMMs on K-blocked operands
 int vd_gemm_grouped_wgrad_used_slabs(int32_t count, int32_t M, int32_t N, int32_t K, int32_t splitk);   // slabs such a launch fills
 extern thread_local int vd_g_last_tile;      // code of the calling thread's last matmul-shaped launch (vd_gemm_last_tile)
+// (decimal fields [tr + 2 spl][kt: 2 digits][bm: 3][bn: 3]: transposed epilogue, split-operand form, K tile or 0 = register-staged kernel; _hip.tile_fields)
+inline int vd_tile_code(bool tr, bool spl, int kt, int bm, int bn) {
+    return ((((tr ? 1 : 0) + (spl ? 2 : 0)) * 100 + kt) * 1000 + bm) * 1000 + bn;
+}
 
 #define VD_REQUIRE(cond, ...)                                   \
     do { if (!(cond)) { vd_set_error(__VA_ARGS__); return 1; } } while (0)

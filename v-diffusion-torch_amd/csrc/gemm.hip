@@ -1386,6 +1386,21 @@ static bool split_forms() {
 }  // namespace
 extern "C" int vd_gemm_split_forms(void) { return split_forms() ? 1 : 0; }
 namespace {
+// the one launch site of the LDS-DMA kernels: SPL = the split-operand kernel, else fp32 MFMA
+template <bool SPL, int BM, int BN, int AK, int BK, bool SPLITK, int KTV, bool TR, bool GROUPED, class GP>
+void launch_dma(const GemmArgs& a, const GP& gp, dim3 grid, hipStream_t st) {
+    if constexpr (SPL) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, AK, BK, SPLITK, KTV, TR, GROUPED>), grid, dim3(256), 0, st, a, gp);
+    else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, AK, BK, SPLITK, KTV, TR, GROUPED>), grid, dim3(256), 0, st, a, gp);
+}
+// K tile x epilogue of an ungrouped launch; KT16 = 16 where the tile has a KT = 16 instantiation, else 32 (so none is built)
+template <bool SPL, int BM, int BN, int AK, int BK, bool SPLITK, int KT16>
+void launch_k16_tr(const GemmArgs& a, dim3 grid, hipStream_t st, bool k16, bool tr) {
+    if (k16 && tr) launch_dma<SPL, BM, BN, AK, BK, SPLITK, KT16, true, false>(a, NoGroup{}, grid, st);
+    else if (k16) launch_dma<SPL, BM, BN, AK, BK, SPLITK, KT16, false, false>(a, NoGroup{}, grid, st);
+    else if (tr) launch_dma<SPL, BM, BN, AK, BK, SPLITK, 32, true, false>(a, NoGroup{}, grid, st);
+    else launch_dma<SPL, BM, BN, AK, BK, SPLITK, 32, false, false>(a, NoGroup{}, grid, st);
+}
+
 template <int BM, int BN, int AK, int BK, bool SPLITK>
 void launch(const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
     // the only tile with a KT = 16 instantiation; an unsplit conv weight gradient never takes it (ktile_for): those two
@@ -1396,21 +1411,12 @@ void launch(const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
     // split-operand forms (SPL): the 128-row tiles of every operand kind without im2col addressing
     constexpr bool has_spl = BM == 128 && AK != VD_IM2COL && BK != VD_IM2COL;
     const bool spl = has_spl && use_dma(a) && split_forms();
-    vd_g_last_tile = ((((tr ? 1 : 0) * 100 + (spl ? 200 : 0) + (use_dma(a) ? (k16 ? 16 : 32) : 0)) * 1000) + BM) * 1000 + BN;
+    vd_g_last_tile = vd_tile_code(tr, spl, use_dma(a) ? (k16 ? 16 : 32) : 0, BM, BN);
     if constexpr (has_spl) {
-        if (spl) {
-            if (k16 && tr) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32), true>), grid, dim3(256), 0, st, a, NoGroup{});
-            else if (k16) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32), false>), grid, dim3(256), 0, st, a, NoGroup{});
-            else if (tr) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, AK, BK, SPLITK, 32, true>), grid, dim3(256), 0, st, a, NoGroup{});
-            else hipLaunchKernelGGL((gemm_split_kernel<BM, BN, AK, BK, SPLITK, 32, false>), grid, dim3(256), 0, st, a, NoGroup{});
-            return;
-        }
+        if (spl) return launch_k16_tr<true, BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32)>(a, grid, st, k16, tr);
     }
     if (!use_dma(a)) hipLaunchKernelGGL((gemm_kernel<BM, BN, AK, BK, SPLITK>), grid, dim3(256), 0, st, a);
-    else if (k16 && tr) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32), true>), grid, dim3(256), 0, st, a, NoGroup{});
-    else if (k16) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32), false>), grid, dim3(256), 0, st, a, NoGroup{});
-    else if (tr) hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, AK, BK, SPLITK, 32, true>), grid, dim3(256), 0, st, a, NoGroup{});
-    else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, AK, BK, SPLITK, 32, false>), grid, dim3(256), 0, st, a, NoGroup{});
+    else launch_k16_tr<false, BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32)>(a, grid, st, k16, tr);
 }
 
 template <int AK, int BK, bool SPLITK>
@@ -1522,9 +1528,9 @@ int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
 template <int BM, int BN, int KTV = 32>
 void launch_grouped(const GemmArgs& a, const GroupPtrs& gp, dim3 grid, hipStream_t st) {
     const bool spl = split_forms();
-    vd_g_last_tile = ((((spl ? 3 : 1) * 100 + KTV) * 1000) + BM) * 1000 + BN;
-    if (spl) hipLaunchKernelGGL((gemm_split_kernel<BM, BN, VD_COL, VD_COL, true, KTV, true, true>), grid, dim3(256), 0, st, a, gp);
-    else hipLaunchKernelGGL((gemm_dma_kernel<BM, BN, VD_COL, VD_COL, true, KTV, true, true>), grid, dim3(256), 0, st, a, gp);
+    vd_g_last_tile = vd_tile_code(true, spl, KTV, BM, BN);
+    if (spl) launch_dma<true, BM, BN, VD_COL, VD_COL, true, KTV, true, true>(a, gp, grid, st);
+    else launch_dma<false, BM, BN, VD_COL, VD_COL, true, KTV, true, true>(a, gp, grid, st);
 }
 // 128x128 tiles of a grouped launch with at least this many workgroups take the KT = 16 form (32 KB of LDS: four workgroups per CU)
 constexpr long long GROUPED_K16_MIN_WGS = 768;
@@ -1546,6 +1552,25 @@ static bool planes256(int count, int M, int N, int K) {
     return best >= 0.85;
 }
 
+// output tiles of one entry of a grouped launch: the 256x256 planes kernel or `tile` of the menu
+void grouped_tiles(int tile, bool p256, int M, int N, long long* nm, long long* nn) {
+    const int bm = p256 ? 256 : TILES[tile].bm, bn = p256 ? 256 : TILES[tile].bn;
+    *nm = (M + bm - 1) / bm; *nn = (N + bn - 1) / bn;
+}
+
+// what a grouped weight-gradient launch of S slabs per entry runs: read by the launcher and by the slab count its callers size and reduce by
+struct GroupedPlan { int tile; bool p256, k16; long long nm, nn; int kt_total, kt_per_split, used; };
+GroupedPlan plan_grouped(int count, int M, int N, int K, int S) {
+    GroupedPlan g;
+    g.tile = choose_tile(M, N, false, (long long)count * S, 0);
+    g.p256 = planes256(count, M, N, K);
+    grouped_tiles(g.tile, g.p256, M, N, &g.nm, &g.nn);
+    g.k16 = g.p256 || (g.tile == 0 && g.nm * g.nn * count * S >= GROUPED_K16_MIN_WGS);
+    g.kt_total = g.k16 ? (K + 15) / 16 : (K + 31) / 32;
+    g.kt_per_split = (g.kt_total + S - 1) / S;
+    g.used = (g.kt_total + g.kt_per_split - 1) / g.kt_per_split;      // slabs that hold work (<= S)
+    return g;
+}
 }  // namespace
 
 /* count same-shape weight-gradient GEMMs in one launch: C[e][M][N] = A[e]^T B[e] (A[e]: [K][M] rows of pitch lda, B[e]: [K][N] rows of
@@ -1557,8 +1582,9 @@ static bool planes256(int count, int M, int N, int K) {
 extern "C" int vd_gemm_grouped_wgrad_auto_split(int32_t count, int32_t M, int32_t N, int32_t K, int32_t min_slabs, int32_t max_slabs) {
     const int tile = choose_tile(M, N, false, (long long)count * 8, 0);
     const bool p256 = planes256(count, M, N, K);
-    const long long blocks = p256 ? (long long)(M / 256) * (N / 256) * count
-                                  : (long long)((M + TILES[tile].bm - 1) / TILES[tile].bm) * ((N + TILES[tile].bn - 1) / TILES[tile].bn) * count;
+    long long nm, nn;
+    grouped_tiles(tile, p256, M, N, &nm, &nn);
+    const long long blocks = nm * nn * count;
     // (128x128 tiles: long launches run the KT = 16 form, four workgroups per CU; 256x256 tiles: one workgroup per CU)
     const long long slots = (long long)vd_cu_count() * (p256 ? 1 : (tile == 0 && blocks * (min_slabs > 1 ? min_slabs : 1) >= GROUPED_K16_MIN_WGS / 2 ? 4 : TILES[tile].per_cu));
     int lo = min_slabs > 1 ? min_slabs : 1, hi = max_slabs > lo ? max_slabs : lo;
@@ -1581,11 +1607,8 @@ extern "C" size_t vd_gemm_grouped_wgrad_ws_bytes(int32_t count, int32_t M, int32
 }
 
 /* a_kblk / b_kblk != 0: the A / B rows of every entry are stored in blocks of 16 K rows, block b of an entry at A[e] + b * a_kblk (see
- * GemmArgs): the 36 planes of the F(4x4,3x3) weight gradient interleave block by block so that its transform pass writes one contiguous run */
-int vd_gemm_grouped_wgrad_kblk(const float* const* A, const float* const* B, float* const* C, float* const* colsum, int32_t count,
-                               int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t splitk, float* ws,
-                               size_t ws_bytes, void* stream, int64_t a_kblk, int64_t b_kblk, int32_t slabs_only);
-
+ * GemmArgs): the 36 planes of the F(4x4,3x3) weight gradient interleave block by block so that its transform pass writes one contiguous run
+ * (vd_gemm_grouped_wgrad_kblk, declared in common.h) */
 extern "C" int vd_gemm_grouped_wgrad(const float* const* A, const float* const* B, float* const* C, float* const* colsum, int32_t count,
                                      int32_t M, int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t splitk, float* ws,
                                      size_t ws_bytes, void* stream) {
@@ -1594,12 +1617,7 @@ extern "C" int vd_gemm_grouped_wgrad(const float* const* A, const float* const* 
 
 /* slabs a grouped launch of this shape fills (<= splitk): the launcher's own plan, for callers that reduce the slabs themselves */
 int vd_gemm_grouped_wgrad_used_slabs(int32_t count, int32_t M, int32_t N, int32_t K, int32_t splitk) {
-    const int S = splitk > 1 ? splitk : 1;
-    const int tile = choose_tile(M, N, false, (long long)count * S, 0);
-    const long long nm = (M + TILES[tile].bm - 1) / TILES[tile].bm, nn = (N + TILES[tile].bn - 1) / TILES[tile].bn;
-    const bool k16 = planes256(count, M, N, K) || (tile == 0 && nm * nn * count * S >= GROUPED_K16_MIN_WGS);
-    const int kt_total = k16 ? (K + 15) / 16 : (K + 31) / 32, per = (kt_total + S - 1) / S;
-    return (kt_total + per - 1) / per;
+    return plan_grouped(count, M, N, K, splitk > 1 ? splitk : 1).used;
 }
 
 /* slabs_only != 0: stop after the split-K launch -- slab z of entry e is left at ws + (e * used + z) * M * N, its column sums at
@@ -1627,34 +1645,25 @@ int vd_gemm_grouped_wgrad_kblk(const float* const* A, const float* const* B, flo
                2 * b_kblk + 16 * ldb + 128 < 0x70000000LL / 4, "vd_gemm_grouped_wgrad: K-block strides outside the LDS-DMA kernel's range");
     // (the grouped launch exists only on the LDS-DMA kernel: VD_GEMM_LEGACY does not apply to it)
     VD_REQUIRE(dma_in_range(a), "vd_gemm_grouped_wgrad: operands outside the LDS-DMA kernel's range (alignment / row pitch)");
-    const int tile = choose_tile(M, N, false, (long long)count * S, 0);
-    const int tbm = TILES[tile].bm, tbn = TILES[tile].bn;
-    const bool p256 = planes256(count, M, N, K);
-    const long long nm = p256 ? M / 256 : (M + tbm - 1) / tbm, nn = p256 ? N / 256 : (N + tbn - 1) / tbn;
-    const bool k16 = p256 || (tile == 0 && nm * nn * count * S >= GROUPED_K16_MIN_WGS);
-    a.kt_total = k16 ? (K + 15) / 16 : (K + 31) / 32;
-    a.kt_per_split = (a.kt_total + S - 1) / S;
-    const int used = (a.kt_total + a.kt_per_split - 1) / a.kt_per_split;      // slabs that hold work (<= S)
-    a.group_S = used;
+    const GroupedPlan g = plan_grouped(count, M, N, K, S);
+    const int used = g.used;
+    a.kt_total = g.kt_total; a.kt_per_split = g.kt_per_split; a.group_S = used;
     a.slab_stride = (long long)M * N;
     a.C = ws;
     float* cpart = ws + (long long)count * used * a.slab_stride;
     a.colsum = colsum ? cpart : nullptr;
-    const dim3 grid((unsigned)nn, (unsigned)nm, (unsigned)(count * used));
+    const dim3 grid((unsigned)g.nn, (unsigned)g.nm, (unsigned)(count * used));
     hipStream_t st = (hipStream_t)stream;
-    if (p256) {
-        vd_g_last_tile = (((3 * 100 + 16) * 1000) + 256) * 1000 + 256;
+    if (g.p256) {
+        vd_g_last_tile = vd_tile_code(true, true, 16, 256, 256);
         hipLaunchKernelGGL(wgrad_planes256_kernel, grid, dim3(512), 0, st, a, gp);
-    } else if (tile == 0 && k16) launch_grouped<128, 128, 16>(a, gp, grid, st);
-    else if (tile == 0) launch_grouped<128, 128>(a, gp, grid, st);
-    else if (tile == 1) launch_grouped<128, 64>(a, gp, grid, st);
-    else if (tile == 2) launch_grouped<64, 128>(a, gp, grid, st);
+    } else if (g.tile == 0 && g.k16) launch_grouped<128, 128, 16>(a, gp, grid, st);
+    else if (g.tile == 0) launch_grouped<128, 128>(a, gp, grid, st);
+    else if (g.tile == 1) launch_grouped<128, 64>(a, gp, grid, st);
+    else if (g.tile == 2) launch_grouped<64, 128>(a, gp, grid, st);
     else launch_grouped<64, 64>(a, gp, grid, st);
     VD_LAUNCH_CHECK("gemm_dma_kernel(grouped)");
-    if (slabs_only) {
-        VD_REQUIRE(used == vd_gemm_grouped_wgrad_used_slabs(count, M, N, K, splitk), "vd_gemm_grouped_wgrad: slab plan mismatch");
-        return 0;
-    }
+    if (slabs_only) return 0;
     const long long tot = (long long)M * N;
     hipLaunchKernelGGL(reduce_slabs_grouped_kernel, dim3((unsigned)((tot + 255) / 256), (unsigned)count), dim3(256), 0, st, ws, used,
                        a.slab_stride, M, N, go, (long long)ldc, cpart);

@@ -867,36 +867,23 @@ inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 
 struct Plan { bool ok; int TW, TH, TPI, P, RIN, NTR, NS, nwgimg; };
 
-Plan plan_of(int H, int W) {
+// geometry of a form with `tiles_item` tiles per work item, min_TW <= tiles per image row <= max_TW, at most max_slots patch slots per chunk
+Plan plan_tiles(int H, int W, int tiles_item, int min_TW, int max_TW, int max_slots) {
     Plan g = {};
     if (H % 2 || W % 2) return g;
     g.TW = W / 2; g.TH = H / 2; g.TPI = g.TW * g.TH;
-    if (!pow2(g.TW) || !pow2(g.TH) || g.TW < 4 || g.TW > 64 || g.TPI < 16) return g;
-    if (g.TPI >= TILES_WG) { g.nwgimg = 1; g.NTR = TILES_WG / g.TW; if (g.NTR < 1 || g.NTR > g.TH) return g; }
-    else { g.nwgimg = TILES_WG / g.TPI; g.NTR = g.TH; }
+    if (!pow2(g.TW) || !pow2(g.TH) || g.TW < min_TW || g.TW > max_TW || g.TPI < 16) return g;
+    if (g.TPI >= tiles_item) { g.nwgimg = 1; g.NTR = tiles_item / g.TW; if (g.NTR < 1 || g.NTR > g.TH) return g; }
+    else { g.nwgimg = tiles_item / g.TPI; g.NTR = g.TH; }
     g.RIN = 2 * g.NTR + 2;
     g.P = g.TW >= 16 ? g.TW + 1 : (g.TW == 8 ? 10 : 5);       // pitch chosen so 16 consecutive tiles read 16 distinct bank quads
     const int slots = g.nwgimg * g.RIN * 2 * g.P;
     g.NS = (slots + 127) / 128 * 128;
-    g.ok = g.NS <= 640;
+    g.ok = g.NS <= max_slots;
     return g;
 }
-
-// geometry of the wide form (128 tiles per item): TW in {8, 16, 32} with at most 768 patch slots per chunk
-Plan plan_wide(int H, int W) {
-    Plan g = {};
-    if (H % 2 || W % 2) return g;
-    g.TW = W / 2; g.TH = H / 2; g.TPI = g.TW * g.TH;
-    if (!pow2(g.TW) || !pow2(g.TH) || (g.TW != 8 && g.TW != 16 && g.TW != 32) || g.TPI < 16) return g;
-    if (g.TPI >= TILES_WIDE) { g.nwgimg = 1; g.NTR = TILES_WIDE / g.TW; if (g.NTR < 1 || g.NTR > g.TH) return g; }
-    else { g.nwgimg = TILES_WIDE / g.TPI; g.NTR = g.TH; }
-    g.RIN = 2 * g.NTR + 2;
-    g.P = g.TW >= 16 ? g.TW + 1 : 10;
-    const int slots = g.nwgimg * g.RIN * 2 * g.P;
-    g.NS = (slots + 127) / 128 * 128;
-    g.ok = g.NS <= 768;
-    return g;
-}
+Plan plan_of(int H, int W) { return plan_tiles(H, W, TILES_WG, 4, 64, 640); }
+Plan plan_wide(int H, int W) { return plan_tiles(H, W, TILES_WIDE, 8, 32, 768); }     // the wide form (128 tiles per item)
 
 }  // namespace
 
@@ -920,6 +907,17 @@ extern "C" int vd_conv3x3_wino(const float* xin, int64_t ldx, const float* U, co
     VD_REQUIRE(vd_aligned16(xin) && vd_aligned16(U) && vd_aligned16(y) && (!res || vd_aligned16(res)) && (!bias || vd_aligned16(bias)),
                "vd_conv3x3_wino: operands must be 16-byte aligned");
     const int ncu = vd_persistent_cus();      // persistent workgroups: one per CU (the LDS footprint admits no second one), minus the reserved CUs
+    const auto make_args = [&](const Plan& g, int tiles_item) {
+        WinoArgs a = {};
+        a.x = xin; a.ldx = ldx; a.U = U; a.bias = bias; a.res = res; a.ldr = ldres; a.y = y; a.ldy = ldy; a.stats = stats_part;
+        a.nimg = nimg; a.H = H; a.W = W; a.K = Cin; a.Cout = Cout;
+        a.TW = g.TW; a.TH = g.TH; a.TPI = g.TPI; a.P = g.P; a.RIN = g.RIN; a.NTR = g.NTR; a.NIW = g.nwgimg;
+        a.lgTW = ilog2(g.TW); a.lgTPI = ilog2(g.TPI); a.ntiles = nimg * g.TPI;
+        a.invP2 = 1.0f / (float)(2 * g.P); a.invRIN = 1.0f / (float)g.RIN;
+        a.ncb = (Cout + TN - 1) / TN; a.ntg = (a.ntiles + tiles_item - 1) / tiles_item;
+        a.probe = g_probe;
+        return a;
+    };
     {
         // wide form (128-tile items, ~5 % faster per unit of work: same-box A/B in tests/perf_wino.py) wherever its items fill the
         // residency rounds at least as well as the 64-tile items do: rounds x 2 x 0.95 against the narrow form's rounds
@@ -933,14 +931,7 @@ extern "C" int vd_conv3x3_wino(const float* xin, int64_t ldx, const float* U, co
         const long long wrounds = (witems + ncu - 1) / ncu, nrounds = (nitems + ncu - 1) / ncu;
         const bool wide = wide_env >= 0 ? wide_env != 0 : (witems >= ncu && 1.9 * (double)wrounds <= (double)nrounds);
         if (wide && gw.ok) {
-            WinoArgs a = {};
-            a.x = xin; a.ldx = ldx; a.U = U; a.bias = bias; a.res = res; a.ldr = ldres; a.y = y; a.ldy = ldy; a.stats = stats_part;
-            a.nimg = nimg; a.H = H; a.W = W; a.K = Cin; a.Cout = Cout;
-            a.TW = gw.TW; a.TH = gw.TH; a.TPI = gw.TPI; a.P = gw.P; a.RIN = gw.RIN; a.NTR = gw.NTR; a.NIW = gw.nwgimg;
-            a.lgTW = ilog2(gw.TW); a.lgTPI = ilog2(gw.TPI); a.ntiles = (int)ntiles;
-            a.invP2 = 1.0f / (float)(2 * gw.P); a.invRIN = 1.0f / (float)gw.RIN;
-            a.ncb = (Cout + TN - 1) / TN; a.ntg = (int)((ntiles + TILES_WIDE - 1) / TILES_WIDE);
-            a.probe = g_probe;
+            const WinoArgs a = make_args(gw, TILES_WIDE);
             const dim3 grid((unsigned)(witems < ncu ? witems : ncu)), blk(WIDE_THREADS);
             hipStream_t st = (hipStream_t)stream;
 #define VD_WIDE_LAUNCH(TWV, NSV)                                                                                                   \
@@ -955,35 +946,25 @@ extern "C" int vd_conv3x3_wino(const float* xin, int64_t ldx, const float* U, co
             else VD_WIDE_LAUNCH(32, 768);
 #undef VD_WIDE_LAUNCH
             VD_LAUNCH_CHECK("wino_conv_wide_kernel");
-            vd_g_last_tile = ((16 * 1000) + 128) * 1000 + TN;
+            vd_g_last_tile = vd_tile_code(false, false, 16, 128, TN);
             return 0;
         }
     }
     const Plan g = plan_of(H, W);
-    WinoArgs a = {};
-    a.x = xin; a.ldx = ldx; a.U = U; a.bias = bias; a.res = res; a.ldr = ldres; a.y = y; a.ldy = ldy; a.stats = stats_part;
-    a.nimg = nimg; a.H = H; a.W = W; a.K = Cin; a.Cout = Cout;
-    a.TW = g.TW; a.TH = g.TH; a.TPI = g.TPI; a.P = g.P; a.RIN = g.RIN; a.NTR = g.NTR; a.NIW = g.nwgimg;
-    a.lgTW = ilog2(g.TW); a.lgTPI = ilog2(g.TPI); a.ntiles = nimg * g.TPI;
-    a.invP2 = 1.0f / (float)(2 * g.P); a.invRIN = 1.0f / (float)g.RIN;
-    a.ncb = (Cout + TN - 1) / TN; a.ntg = (a.ntiles + TILES_WG - 1) / TILES_WG;
+    WinoArgs a = make_args(g, TILES_WG);
     const long long items = (long long)a.ncb * a.ntg;
     VD_REQUIRE(items < (1LL << 30), "vd_conv3x3_wino: too many work items");
     const dim3 grid((unsigned)(items < ncu ? items : ncu));
     hipStream_t st = (hipStream_t)stream;
     const dim3 blk(WINO_THREADS);
 #ifdef VD_PROBES
-    a.probe = g_probe;
     { static const bool light = getenv("VD_WINO_PROBE_LIGHT") != nullptr; a.probe_light = light ? 1 : 0; }
-#define VD_WINO_LAUNCH(TWV, NSV)                                                                                                   \
-    do {                                                                                                                            \
-        g_last_wino = ((TWV) * 1000 + (NSV)) * 2 + (stats_part ? 1 : 0);                                                            \
-        if (g_probe) {      /* timing probe (tests/probe/wino_phases.py): per-wave phase stamps */                                  \
+    // timing probe (tests/probe/wino_phases.py): per-wave phase stamps
+#define VD_WINO_PROBE_ARM(TWV, NSV)                                                                                                \
+        if (g_probe) {                                                                                                              \
             if (stats_part) hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, true, true>), grid, blk, 0, st, a);                       \
             else hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, false, true>), grid, blk, 0, st, a);                                 \
-        } else if (stats_part) hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, true>), grid, blk, 0, st, a);                          \
-        else hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, false>), grid, blk, 0, st, a);                                           \
-    } while (0)
+        } else
     // timing experiments (WRONG results): probe library only -- the product library has no such instantiation and reads no such knob
     static const int exp_mode = getenv("VD_WINO_EXP") ? atoi(getenv("VD_WINO_EXP")) : 0;
     if (exp_mode && g.TW == 16 && g.NS <= 384 && !stats_part) {
@@ -1004,13 +985,15 @@ extern "C" int vd_conv3x3_wino(const float* xin, int64_t ldx, const float* U, co
         return 0;
     }
 #else
+#define VD_WINO_PROBE_ARM(TWV, NSV)
+#endif
 #define VD_WINO_LAUNCH(TWV, NSV)                                                                                                   \
     do {                                                                                                                            \
         g_last_wino = ((TWV) * 1000 + (NSV)) * 2 + (stats_part ? 1 : 0);                                                            \
+        VD_WINO_PROBE_ARM(TWV, NSV)                                                                                                 \
         if (stats_part) hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, true>), grid, blk, 0, st, a);                                 \
         else hipLaunchKernelGGL((wino_conv_kernel<TWV, NSV, false>), grid, blk, 0, st, a);                                           \
     } while (0)
-#endif
     // (tiles per row, patch slots): the square images of the shipped configs take the first form of each row
     if (g.TW == 16 && g.NS <= 384) VD_WINO_LAUNCH(16, 384);
     else if (g.TW == 8 && g.NS <= 384) VD_WINO_LAUNCH(8, 384);
@@ -1022,8 +1005,9 @@ extern "C" int vd_conv3x3_wino(const float* xin, int64_t ldx, const float* U, co
     else if (g.TW == 4) VD_WINO_LAUNCH(4, 640);
     else VD_WINO_LAUNCH(32, 640);
 #undef VD_WINO_LAUNCH
+#undef VD_WINO_PROBE_ARM
     VD_LAUNCH_CHECK("wino_conv_kernel");
-    vd_g_last_tile = ((16 * 1000) + 128) * 1000 + TN;          // (chunk of the statistics = 64 pixels = BM / 2 with BM = 128)
+    vd_g_last_tile = vd_tile_code(false, false, 16, 128, TN);         // (chunk of the statistics = 64 pixels = BM / 2 with BM = 128)
     return 0;
 }
 

@@ -203,9 +203,16 @@ def _note_bytes(name, nbytes):
         e[1] += 1
 
 
+def tile_fields(code):
+    """vd_gemm_last_tile code (csrc/common.h: vd_tile_code) -> (transposed epilogue, split-operand form, K tile [0: register-staged kernel], BM, BN)"""
+    flags = code // 100000000
+    return bool(flags & 1), flags >= 2, (code // 1000000) % 100, (code // 1000) % 1000, code % 1000
+
+
 class _Timed:
-    def __init__(self, name, flops):
-        self.name, self.flops = name, flops
+    """event pair around a launch; with PROFILE set, a clean exit appends (*_record(), start_event, end_event)"""
+    def __init__(self, name, amount, rename=None):
+        self.name, self.amount, self.rename = name, amount, rename
 
     def __enter__(self):
         if PROFILE is not None:
@@ -216,27 +223,49 @@ class _Timed:
     def __exit__(self, *exc):
         if PROFILE is not None and exc[0] is None:
             self.e1.record()
-            t = lib().vd_gemm_last_tile()
-            # hundreds digit of the K-tile group: 1 = transposed epilogue, 2 = split-operand form (VD_GEMM_SPLIT=1), 3 = both
-            flags, kt, bm, bn = t // 100000000, (t // 1000000) % 100, (t // 1000) % 1000, t % 1000
-            tr, spl = flags & 1, flags >= 2
-            name = self.name.format(tile=f"{bm}, {bn}", kt=f"{kt}, {'true' if tr else 'false'}")
-            if spl:
-                name = name.replace("gemm_dma_kernel", "gemm_split_kernel")
-            if spl and (bm, bn) == (256, 256):          # round 6: the 8-wave 256x256 form of the grouped weight-gradient launches (its rocprof name)
-                name = "wgrad_planes256_kernel" + name[name.index(">") + 1:]
-            if kt == 0:
-                name = name.replace("gemm_dma_kernel", "gemm_kernel").replace(", 0, false>", ">")
-            PROFILE.append((name, self.flops, self.e0, self.e1))
+            PROFILE.append(self._record() + (self.e0, self.e1))
+
+
+class _TimedTile(_Timed):
+    """(rocprof name of the tile-engine instantiation that ran, from vd_gemm_last_tile; flops)"""
+    def _record(self):
+        tr, spl, kt, bm, bn = tile_fields(lib().vd_gemm_last_tile())
+        name = self.name.format(tile=f"{bm}, {bn}", kt=f"{kt}, {'true' if tr else 'false'}")
+        if spl:
+            name = name.replace("gemm_dma_kernel", "gemm_split_kernel")
+        if spl and (bm, bn) == (256, 256):          # round 6: the 8-wave 256x256 form of the grouped weight-gradient launches (its rocprof name)
+            name = "wgrad_planes256_kernel" + name[name.index(">") + 1:]
+        if kt == 0:
+            name = name.replace("gemm_dma_kernel", "gemm_kernel").replace(", 0, false>", ">")
+        return name, self.amount
 
 
 class _TimedName(_Timed):
-    """PROFILE record under a fixed kernel name (launches whose instantiation does not come from vd_gemm_last_tile)"""
+    """(fixed kernel name, flops): launches whose instantiation does not come from vd_gemm_last_tile"""
+    def _record(self):
+        return self.name, self.amount
 
-    def __exit__(self, *exc):
-        if PROFILE is not None and exc[0] is None:
-            self.e1.record()
-            PROFILE.append((self.name, self.flops, self.e0, self.e1))
+
+class _TimedBytes(_Timed):
+    """HBM-bound launch: ("hbm:<rocprof kernel name>", algorithmic bytes = operands read + written once).  ``rename`` (optional) is
+    called after the launch and returns the name of the instantiation that ran."""
+    def _record(self):
+        return "hbm:" + (self.rename() if self.rename else self.name), float(self.amount)
+
+
+def _two_parts(parts):
+    """[(part, C, chunks)] of one or two channel-concatenated sources -> the six arguments of the *_from_partials entry points"""
+    (p1, c1, k1), (p2, c2, k2) = parts[0], (parts[1] if len(parts) > 1 else (None, 0, 0))
+    return ptr(p1), c1, k1, ptr(p2), c2, k2
+
+
+def _resampled_hw(H, W, resample):
+    return H * W // 4 if resample == RS_DOWN else (H * W * 4 if resample == RS_UP else H * W)
+
+
+def _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws):
+    return (ptr(x), ldx, ptr(dy), lddy, nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(),
+            ws.numel() * 4)
 
 
 def workspace(nbytes, device, tag="default"):
@@ -268,7 +297,7 @@ def gemm(A, B, Cm, M, N, K, *, a_kind=ROW, b_kind=ROW, lda, ldb, ldc, bias=None,
     if splitk > 1:
         ws = workspace(splitk * (M * N + M) * 4, A.device, "splitk")
         d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * 4
-    with _Timed("gemm_dma_kernel<{tile}, " + f"{a_kind}, {b_kind}, " + ("true, {kt}>" if splitk > 1 else "false, {kt}>"),
+    with _TimedTile("gemm_dma_kernel<{tile}, " + f"{a_kind}, {b_kind}, " + ("true, {kt}>" if splitk > 1 else "false, {kt}>"),
                 2.0 * M * N * K * batch):
         _check(lib().vd_gemm(C.byref(d), stream()), "vd_gemm")
 
@@ -287,14 +316,14 @@ def gemm_grouped_wgrad(entries, M, N, K, lda, ldb, ldc, splitk):
     assert all((e[3] is not None) == has_cs for e in entries)
     S = max(1, int(splitk))
     ws = workspace(lib().vd_gemm_grouped_wgrad_ws_bytes(n, M, N, S), entries[0][0].device, "splitk")
-    with _Timed("gemm_dma_kernel<{tile}, 1, 1, true, 32, true, true>", 2.0 * M * N * K * n):
+    with _TimedTile("gemm_dma_kernel<{tile}, 1, 1, true, 32, true, true>", 2.0 * M * N * K * n):
         _check(lib().vd_gemm_grouped_wgrad(arr(0), arr(1), arr(2), arr(3) if has_cs else None, n, M, N, K, lda, ldb, ldc, S,
                                            ws.data_ptr(), ws.numel() * 4, stream()), "vd_gemm_grouped_wgrad")
 
 
 def last_row_tile():
     """BM of the calling thread's last vd_gemm / vd_conv3x3 launch (chunk size of its output statistics = BM/2)"""
-    return (lib().vd_gemm_last_tile() // 1000) % 1000
+    return tile_fields(lib().vd_gemm_last_tile())[3]
 
 
 def stats_part_numel(nimg, HW, Cc):
@@ -304,14 +333,12 @@ def stats_part_numel(nimg, HW, Cc):
 
 def gn_stats_from_partials(parts, nimg, HW, stats, G=32, eps=1e-6):
     """parts: [(part, C, chunks)] for one or two channel-concatenated sources"""
-    (p1, c1, k1), (p2, c2, k2) = parts[0], (parts[1] if len(parts) > 1 else (None, 0, 0))
-    _check(lib().vd_gn_stats_from_partials(ptr(p1), c1, k1, ptr(p2), c2, k2, nimg, HW, G, eps, ptr(stats), stream()),
+    _check(lib().vd_gn_stats_from_partials(*_two_parts(parts), nimg, HW, G, eps, ptr(stats), stream()),
            "vd_gn_stats_from_partials")
 
 
 def gn_coef_from_partials(parts, nimg, HW, gamma, beta, film, coef, G=32, eps=1e-6):
-    (p1, c1, k1), (p2, c2, k2) = parts[0], (parts[1] if len(parts) > 1 else (None, 0, 0))
-    _check(lib().vd_gn_coef_from_partials(ptr(p1), c1, k1, ptr(p2), c2, k2, nimg, HW, G, eps, ptr(gamma), ptr(beta), ptr(film),
+    _check(lib().vd_gn_coef_from_partials(*_two_parts(parts), nimg, HW, G, eps, ptr(gamma), ptr(beta), ptr(film),
                                           ptr(coef), stream()), "vd_gn_coef_from_partials")
 
 
@@ -436,7 +463,7 @@ def conv3x3_dgrad_wino43(dy, lddy, U43, dx, lddx, nimg, H, W, Cin, Cout):
 
 
 def conv3x3(x, ldx, wpack, bias, y, ldy, nimg, H, W, Cin, Cout, res=None, ldres=0, accumulate=False, stats_part=None):
-    with _Timed("gemm_dma_kernel<{tile}, 2, 0, false, {kt}>", 2.0 * nimg * H * W * Cout * 9 * Cin):
+    with _TimedTile("gemm_dma_kernel<{tile}, 2, 0, false, {kt}>", 2.0 * nimg * H * W * Cout * 9 * Cin):
         _check(lib().vd_conv3x3(ptr(x), ldx, ptr(wpack), ptr(bias), ptr(res), ldres, ptr(y), ldy, nimg, H, W, Cin, Cout,
                                 int(accumulate), ptr(stats_part), stream()), "vd_conv3x3")
 
@@ -444,8 +471,7 @@ def conv3x3(x, ldx, wpack, bias, y, ldy, nimg, H, W, Cin, Cout, res=None, ldres=
 def conv3x3_wgrad_wino(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None):
     nb = lib().vd_conv3x3_wgrad_wino_ws_bytes(nimg, H, W, Cin, Cout)
     ws = workspace(nb, x.device, "wgrad")
-    args = (ptr(x), ldx, ptr(dy), lddy, nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(),
-            ws.numel() * 4)
+    args = _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws)
     if PROFILE is None:
         _check(lib().vd_conv3x3_wgrad_wino(*args, stream()), "vd_conv3x3_wgrad_wino")
         return
@@ -490,8 +516,7 @@ def conv3x3_wgrad_wino43(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cou
     """F(4x4,3x3) weight gradient, unfused (vd_conv3x3_wgrad_wino43): transforms -> 36 grouped GEMMs -> finish"""
     nb = lib().vd_conv3x3_wgrad_wino43_ws_bytes(nimg, H, W, Cin, Cout)
     ws = workspace(nb, x.device, "wgrad43")
-    args = (ptr(x), ldx, ptr(dy), lddy, nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(),
-            ws.numel() * 4)
+    args = _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws)
     if PROFILE is None:
         _check(lib().vd_conv3x3_wgrad_wino43(*args, stream()), "vd_conv3x3_wgrad_wino43")
         return
@@ -499,7 +524,7 @@ def conv3x3_wgrad_wino43(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cou
         _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, 1, stream()), "vd_conv3x3_wgrad_wino43_phase")
     # the 36 planes run as ONE grouped launch of the tile engine: recorded under that instantiation's rocprof name (from vd_gemm_last_tile),
     # tagged so that the bench knows its recorded work is the direct convolution's 2*M*N*K, of which the planes execute 1/4
-    with _Timed("gemm_dma_kernel<{tile}, 1, 1, true, {kt}, true> " + W43_WGRAD_TAG, 2.0 * nimg * H * W * Cout * 9 * Cin) as t:
+    with _TimedTile("gemm_dma_kernel<{tile}, 1, 1, true, {kt}, true> " + W43_WGRAD_TAG, 2.0 * nimg * H * W * Cout * 9 * Cin) as t:
         _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, 2, stream()), "vd_conv3x3_wgrad_wino43_phase")
     # (its operands are the transformed images: 36 planes of [tiles][Cin] and [tiles][Cout], read once, + the 36 x Cout x Cin result)
     _note_bytes(PROFILE[-1][0], 4.0 * (36.0 * nimg * (H // 4) * (W // 4) * (Cin + Cout) + 36.0 * Cout * Cin))
@@ -516,16 +541,15 @@ def conv3x3_wgrad(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, ac
         return conv3x3_wgrad_wino(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate, dbias)
     nb = lib().vd_conv3x3_wgrad_ws_bytes(nimg, H, W, Cin, Cout)
     ws = workspace(nb, x.device, "wgrad")
-    args = (ptr(x), ldx, ptr(dy), lddy, nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(),
-            ws.numel() * 4)
+    args = _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws)
     flops = 2.0 * nimg * H * W * Cout * 9 * Cin
     if PROFILE is None:
         _check(lib().vd_conv3x3_wgrad(*args, stream()), "vd_conv3x3_wgrad")
         return
     # per-kernel timing: the MFMA kernel and the slab reduction get their own event pairs (same kernels, same order)
-    with _Timed("gemm_dma_kernel<{tile}, 1, 2, true, {kt}>", flops):
+    with _TimedTile("gemm_dma_kernel<{tile}, 1, 2, true, {kt}>", flops):
         _check(lib().vd_conv3x3_wgrad_phase(*args, 1, stream()), "vd_conv3x3_wgrad_phase")
-    with _Timed("reduce_slabs_oihw_kernel", 0.0):
+    with _TimedTile("reduce_slabs_oihw_kernel", 0.0):
         _check(lib().vd_conv3x3_wgrad_phase(*args, 2, stream()), "vd_conv3x3_wgrad_phase")
 
 
@@ -563,25 +587,6 @@ def gn_stats(x, ldx, nimg, HW, Cc, stats, G=32, eps=1e-6):
            "vd_gn_stats")
 
 
-class _TimedBytes:
-    """PROFILE record of an HBM-bound launch: ("hbm:<rocprof kernel name>", algorithmic bytes = operands read + written once,
-    events).  ``rename`` (optional) is called after the launch and returns the name of the instantiation that ran."""
-
-    def __init__(self, name, nbytes, rename=None):
-        self.name, self.nbytes, self.rename = name, nbytes, rename
-
-    def __enter__(self):
-        if PROFILE is not None:
-            self.e0, self.e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            self.e0.record()
-        return self
-
-    def __exit__(self, *exc):
-        if PROFILE is not None and exc[0] is None:
-            self.e1.record()
-            PROFILE.append(("hbm:" + (self.rename() if self.rename else self.name), float(self.nbytes), self.e0, self.e1))
-
-
 def _gn_bwd_name():
     k = lib().vd_gn_bwd_last_kernel()
     if k > 0:
@@ -592,17 +597,14 @@ def _gn_bwd_name():
 
 
 def gn_apply(x, ldx, stats, gamma, beta, film, act, p_drop, seed, resample, y, ldy, nimg, H, W, Cc, coef, G=32):
-    hw_out = H * W // 4 if resample == RS_DOWN else (H * W * 4 if resample == RS_UP else H * W)
-    with _TimedBytes("gn_apply_kernel" if gamma is not None else "gn_apply_kernel (resample)", 4.0 * nimg * Cc * (H * W + hw_out)):
+    with _TimedBytes("gn_apply_kernel" if gamma is not None else "gn_apply_kernel (resample)", 4.0 * nimg * Cc * (H * W + _resampled_hw(H, W, resample))):
         _gn_apply(x, ldx, stats, gamma, beta, film, act, p_drop, seed, resample, y, ldy, nimg, H, W, Cc, coef, G)
 
 
 def gn_apply_from_partials(x, ldx, parts, gamma, beta, film, act, p_drop, seed, resample, y, ldy, nimg, H, W, Cc, coef, G=32, eps=1e-6):
     """statistics from the producers' partial sums + apply in one launch (vd_gn_apply_from_partials); parts: [(part, C, chunks)] x 1 or 2"""
-    (p1, c1, k1), (p2, c2, k2) = parts[0], (parts[1] if len(parts) > 1 else (None, 0, 0))
-    hw_out = H * W // 4 if resample == RS_DOWN else (H * W * 4 if resample == RS_UP else H * W)
-    with _TimedBytes("gn_apply_kernel", 4.0 * nimg * Cc * (H * W + hw_out)):
-        _check(lib().vd_gn_apply_from_partials(ptr(x), ldx, ptr(p1), c1, k1, ptr(p2), c2, k2, ptr(gamma), ptr(beta), ptr(film), int(act),
+    with _TimedBytes("gn_apply_kernel", 4.0 * nimg * Cc * (H * W + _resampled_hw(H, W, resample))):
+        _check(lib().vd_gn_apply_from_partials(ptr(x), ldx, *_two_parts(parts), ptr(gamma), ptr(beta), ptr(film), int(act),
                                                float(p_drop), int(seed), resample, ptr(y), ldy, nimg, H, W, Cc, G, eps, ptr(coef), stream()),
                "vd_gn_apply_from_partials")
 
@@ -618,8 +620,7 @@ def gn_apply_bwd(dy, lddy, x, ldx, coef, gamma, beta, film, act, p_drop, seed, r
     all norms of the backward pass instead of summing them here (dgamma / dbeta are then not touched)"""
     nb = lib().vd_gn_ws_bytes(nimg, H * W, Cc)
     ws = workspace(nb, dy.device, "gn")
-    hw_dy = H * W // 4 if resample == RS_DOWN else (H * W * 4 if resample == RS_UP else H * W)
-    nbytes = 4.0 * nimg * Cc * (hw_dy + H * W * (1 + (gamma is not None) + (add is not None) + bool(accumulate_dx)))
+    nbytes = 4.0 * nimg * Cc * (_resampled_hw(H, W, resample) + H * W * (1 + (gamma is not None) + (add is not None) + bool(accumulate_dx)))
     with _TimedBytes("gn_apply_bwd", nbytes, rename=_gn_bwd_name):
         if pgb_keep is not None:
             _check(lib().vd_gn_apply_bwd_keep(ptr(dy), lddy, ptr(x), ldx, ptr(coef), ptr(gamma), ptr(beta), ptr(film), int(act),
