@@ -196,6 +196,72 @@ def test_small_batch_networks_through_the_f43_kernels_in_subprocess():
     print("\n".join(l for l in r.stdout.splitlines() if "out err" in l))
 
 
+def test_declined_f43_layers_run_on_fallback_images(vd, monkeypatch):
+    """engine._conv when a layer was packed for F(4x4,3x3) and the call declines it: the F(2x2,3x3) image is made on demand.  tinyA at B = 4,
+    R = 16 is the smallest shape F(4x4,3x3) serves (16x16 images in groups of four, Cin % 8 == 0, Cout % 32 == 0) once the occupancy rule
+    is off.  Forward + backward (a) as packed, (b) with the call-time F(4x4,3x3) predicates declining -- twice, bitwise equal -- and (c)
+    with F(4x4,3x3) off at pack time: (b) against (c) and (a) against the reference inside the bounds of the tiny goldens (output 2e-5,
+    gradients rel-L2 1e-4).  The tinyA golden was captured at B = 3, so the reference at B = 4 is the oracle the goldens are checked with."""
+    from oracle import unet_ref, detrand
+    from oracle.cases import TINY, make_inputs
+    from v_diffusion import _hip
+    case = TINY["tinyA"]
+    cfg, B, R = case["cfg"], 4, case["R"]
+    model, sd = _build(vd, cfg, train=True)
+    eng = model.engine()
+    x, t, y = make_inputs(cfg, B, R, case["label"])
+    gout = detrand.normal("gout", (B, cfg["out_channels"], R, R), 1)
+    monkeypatch.setattr(_hip, "WINO43_OCC", False)
+    used, declining = [], [False]
+    for name in ("wino43_fwd_supported", "wino43_supported"):
+        real = getattr(_hip, name)
+        monkeypatch.setattr(_hip, name, lambda *a, _r=real: False if declining[0] else _r(*a))
+    for name in ("conv3x3_wino43_fwd", "conv3x3_dgrad_wino43", "wino_pack"):
+        real = getattr(_hip, name)
+        monkeypatch.setattr(_hip, name, lambda *a, _r=real, _n=name, **k: used.append(_n) or _r(*a, **k))
+    real_conv = eng._conv
+
+    def conv(*a, **k):                                      # the predicates decline inside _conv only: the pack-time choice stands
+        declining[0] = decline_calls[0]
+        try:
+            return real_conv(*a, **k)
+        finally:
+            declining[0] = False
+    monkeypatch.setattr(eng, "_conv", conv)
+    decline_calls = [False]
+
+    def run():
+        del used[:]
+        model.zero_grad(set_to_none=True)
+        out = model(x.to(DEV), t.to(DEV), y.to(DEV))
+        (out * gout.to(DEV)).sum().backward()
+        torch.cuda.synchronize()
+        return out.detach().clone(), [p.grad.clone() for p in model.parameters()], sorted(set(used))
+    oa, ga, ua = run()                                      # (a)
+    assert "conv3x3_wino43_fwd" in ua and "wino_pack" not in ua, ua
+    decline_calls[0] = True
+    ob, gb, ub = run()                                      # (b): every F(4x4,3x3)-packed layer takes an on-demand image
+    ob2, gb2, _ = run()
+    assert ub == ["wino_pack"], ub                          # no F(4x4,3x3) convolution ran
+    assert torch.equal(ob, ob2) and all(torch.equal(p, q) for p, q in zip(gb, gb2)), "fallback images: not bitwise reproducible"
+    decline_calls[0] = False
+    monkeypatch.setattr(_hip, "WINO43", False)
+    monkeypatch.setattr(_hip, "WINO43_FWD", False)
+    oc, gc, uc = run()                                      # (c): packed for F(2x2,3x3) in the first place
+    assert uc == [], uc
+    sdo = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    oo = unet_ref.unet_forward(sdo, cfg, x, t, y)
+    (oo * gout).sum().backward()
+    gmax = max(v.grad.double().norm().item() for v in sdo.values())
+    for tag, o, g, ro, rg in (("b vs c", ob, gb, oc, gc), ("a vs reference", oa, ga, oo.detach().to(DEV), [sdo[k].grad.to(DEV) for k, _ in model.named_parameters()])):
+        err = (o - ro).abs().max().item()
+        print(f"{tag}: output max-abs {err:.3e}")
+        assert err <= 2e-5, f"{tag}: output differs by {err:.3e}"
+        for (k, _), p, q in zip(model.named_parameters(), g, rg):
+            e = (p.double() - q.double()).norm().item()
+            assert e <= 1e-4 * q.double().norm().item() + 1e-6 * gmax, f"{tag}: {k}: L2 error {e:.3e} vs |grad| {q.norm().item():.3e}"
+
+
 def test_shard_gradients_sum_to_full_batch(vd):
     """data parallel invariant (SURVEY 4 iv): sum over shards of sum-loss gradients == full-batch gradient"""
     from oracle.cases import TINY, make_inputs

@@ -13,6 +13,7 @@ What runs where
 MI355X only: CPU tensors raise (the CPU restatement is oracle/diffusion_ref.py, test infrastructure).
 ``loss_type="kl"`` (variational-bound terms, reference :446-464) is one fused kernel pair as well (vd_bpd_terms / vd_bpd_bwd).
 """
+import contextlib
 import math
 
 import torch
@@ -692,13 +693,13 @@ class GaussianDiffusion:
             graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(graph):
                 body()
-            # the graph's pack / convolution nodes hold raw pointers into the engine's pack state (device table, U images):
-            # keep that state referenced by the cache entry, so an engine-side eviction can never free memory a cached graph
+            # the graph's pack / convolution nodes hold raw pointers into the forward's ConvPacks (device tables, U images):
+            # keep that object referenced by the cache entry, so an engine-side eviction can never free memory a cached graph
             # replays through; the graph cache itself is a small LRU (a graph pins its activations)
             eng = net.engine() if hasattr(net, "engine") else None
             while len(cache) >= self.GRAPH_CACHE_MAX:
                 cache.pop(next(iter(cache)))
-            entry = cache[key] = (graph, st, None if eng is None else eng._last_pack_state)
+            entry = cache[key] = (graph, st, None if eng is None else eng.packs)
         else:
             cache[key] = cache.pop(key)                # most recently used last
         graph, st = entry[0], entry[1]
@@ -750,14 +751,9 @@ class GaussianDiffusion:
         preds = []
         net = getattr(denoise_fn, "module", denoise_fn)
         eng = net.engine() if hasattr(net, "engine") else None
-        if eng is not None:
-            eng.pack_cache = {}                                # the weights do not change inside one reverse chain
-        try:
+        with (eng.fixed_weights() if eng is not None else contextlib.nullcontext()):       # the weights do not change inside one reverse chain
             return self._eager_chain(denoise_fn, x_t, x_in, x_in_next, x_next, y_in, cfg, B, T, device, generator, use_ddim,
                                      pred_freq, preds)
-        finally:
-            if eng is not None:
-                eng.pack_cache = None
 
     def _eager_chain(self, denoise_fn, x_t, x_in, x_in_next, x_next, y_in, cfg, B, T, device, generator, use_ddim, pred_freq, preds):
         for ti in reversed(range(T)):

@@ -18,6 +18,8 @@ Data layout in HBM
   * the tape (what backward needs) is a python list of per-block dicts of buffers; with 288 GB of HBM nothing is
     recomputed except the dropout mask (counter-based Philox, regenerated from (seed, element index)).
 """
+import collections
+import contextlib
 import math
 
 import torch
@@ -50,6 +52,90 @@ def _splitk(M, N, K):
 class _Blk:
     __slots__ = ("prefix", "kind", "cin", "cout", "rs", "attn", "consumes", "res", "att", "level", "dest", "src_hs", "push_hs",
                  "ch_h")
+
+
+class _Pack(collections.namedtuple("_Pack", "uf ud u43 u43f wf wd", defaults=(None,) * 6)):
+    """Images of one 3x3 kernel; None = not packed for this weight set and geometry.  uf / ud: F(2x2,3x3) U = G w G^T as [16][Cout][Cin]
+    (forward) / [16][Cin][Cout] (input gradient, rotated); u43f / u43: the 36-plane lane-ordered F(4x4,3x3) images of csrc/wino43.hip
+    (forward / input gradient); wf / wd: the direct [Cout][tap][Cin] / [Cin][tap'][Cout] packs."""
+    __slots__ = ()
+
+
+_NO_PACK = _Pack()            # a kernel ConvPacks does not hold (in / out convolution, nothing packed yet)
+
+
+class ConvPacks:
+    """Everything that belongs to the packed images of ONE weight set's residual-block 3x3 kernels at one (need_d, geometry): the
+    persistent buffers (``bufs``), the per-layer views into them (``layers``: id(weight) -> _Pack), the device tables of the batched pack
+    launches (``tables``: name -> (table, rows, blocks)) and the F(2x2,3x3) images made on demand (``fallback``).  Buffers and tables
+    never move while the object lives, so a captured HIP graph stays valid for as long as it references the object.
+    With H.WINO every layer gets Winograd-domain images -- F(4x4,3x3) for the directions ``geoms`` ([(weight, rows, H, W, Cin, Cout)],
+    dense pitches) lets those kernels serve, F(2x2,3x3) otherwise; a layer served by F(4x4,3x3) gets no F(2x2,3x3) image for that direction
+    (a call that declines asks image()) and the direct packs are made per tensor, on demand, by UNetEngine._pack_f / _pack_d for the
+    geometries that fall back (none in the shipped configs).  Without H.WINO every layer gets the direct packs."""
+    LAUNCHES = (("wino", "wino_pack_batched"), ("wino43", "wino43_pack_batched"), ("direct", "pack_conv3x3_batched"))
+
+    def __init__(self, ws, need_d, geoms):
+        dev, self.wino = ws[0].device, H.WINO
+        use43 = {id(w): need_d and H.wino43_supported(nb, lh, lw, ci, co, co, ci) for (w, nb, lh, lw, ci, co) in geoms if self.wino}
+        use43f = {id(w): H.wino43_fwd_supported(nb, lh, lw, ci, co, ci, co, co) for (w, nb, lh, lw, ci, co) in geoms if self.wino}
+
+        def forms(w):                                     # [(field, buffer, shape)] of one layer, in the order the buffers are carved
+            co, ci = w.shape[0], w.shape[1]
+            if not self.wino:
+                return [("wf", "wf", (co, 9, ci))] + ([("wd", "wd", (ci, 9, co))] if need_d else [])
+            out = [("u43f", "u43", (36 * co * ci,)) if use43f.get(id(w)) else ("uf", "uf", (16, co, ci))]
+            if need_d:
+                out.append(("u43", "u43", (36 * co * ci,)) if use43.get(id(w)) else ("ud", "ud", (16, ci, co)))
+            return out
+        lay = [(w, forms(w)) for w in ws]
+        self.bufs, self.layers, self.fallback = {}, {}, {}
+        for name in ("uf", "ud", "u43", "wf", "wd"):
+            n = sum(math.prod(shape) for _, fs in lay for _, buf, shape in fs if buf == name)
+            if n:
+                self.bufs[name] = torch.empty(n, dtype=torch.float32, device=dev)
+        off = dict.fromkeys(self.bufs, 0)
+        rows = {name: [] for name, _ in self.LAUNCHES}
+        blocks = dict.fromkeys(rows, 0)
+
+        def carve(buf, shape):                            # the next `shape` elements of a persistent buffer
+            n = math.prod(shape)
+            off[buf] += n
+            return self.bufs[buf][off[buf] - n: off[buf]].view(shape)
+
+        def row(tab, w, *cols, nblk):                     # [weight, destinations / flags ..., first block of the launch's grid]
+            rows[tab].append([w.data_ptr()] + [c.data_ptr() if torch.is_tensor(c) else int(c or 0) for c in cols] + [blocks[tab]])
+            blocks[tab] += nblk
+        for w, fs in lay:
+            p = self.layers[id(w)] = _Pack(**{field: carve(buf, shape) for field, buf, shape in fs})
+            co, ci = w.shape[0], w.shape[1]
+            if p.wf is not None:
+                row("direct", w, p.wf, p.wd, co, ci, ci, co, nblk=(w.numel() + 255) // 256)
+            if p.uf is not None or p.ud is not None:
+                tiled = int(co % 16 == 0 and ci % 16 == 0)
+                row("wino", w, p.uf, p.ud, co, ci, tiled, 0, nblk=(co // 16) * (ci // 16) if tiled else (co * ci + 255) // 256)
+            if p.u43f is not None:
+                row("wino43", w, p.u43f, 1, co, ci, 0, 0, nblk=(co // 32) * (ci // 8))
+            if p.u43 is not None:
+                row("wino43", w, p.u43, 0, co, ci, 0, 0, nblk=(ci // 32) * (co // 8))
+        self.tables = {k: (torch.tensor(r, dtype=torch.int64).to(dev), len(r), blocks[k]) for k, r in rows.items() if r}
+
+    def repack(self):
+        """the images follow the weights as they are NOW: one batched launch per table"""
+        for name, launch in self.LAUNCHES:
+            if name in self.tables:
+                getattr(H, launch)(*self.tables[name])
+
+    def image(self, w, dgrad):
+        """F(2x2,3x3) image -- rotated for the input gradient -- of a layer that was packed for an F(4x4,3x3) form: one allocation per
+        (weight, direction) that lives with this object (stable address: also valid inside a captured HIP graph), re-packed on every
+        call like every other image"""
+        co, ci = w.shape[0], w.shape[1]
+        U = self.fallback.get((id(w), dgrad))
+        if U is None:
+            U = self.fallback[(id(w), dgrad)] = torch.empty((16, ci, co) if dgrad else (16, co, ci), dtype=torch.float32, device=w.device)
+        H.wino_pack(w, co, ci, **{"ud" if dgrad else "uf": U})
+        return U
 
 
 class UNetEngine:
@@ -130,12 +216,10 @@ class UNetEngine:
                 grp = self.film_groups.setdefault(2 * b.cout, [])
                 self.film_slot[pre] = (2 * b.cout, len(grp))
                 grp.append(b.res)
-        # forward weight packs kept across calls while a sampler holds the weights fixed (set to {} by the sampling loop,
-        # None otherwise: training repacks every step because the optimizer rewrites the weights)
-        self.pack_cache = None
-        self._pack_state = None           # {weight-set key: persistent buffers + device table of the batched weight pack}
-        self._last_pack_state = None
-        self._packed = None               # {id(weight): (wf, wd)} valid for the weights as of the last forward
+        self._pack_lru = {}               # {weight-set key: ConvPacks}, at most PACK_STATES_MAX (_pack_all)
+        self._packs = None                # the ConvPacks of the forward (or backward) in flight
+        self._fixed = None                # {} inside fixed_weights(): what one sampler chain packs once; None otherwise -- training repacks
+                                          # every step because the optimizer rewrites the weights
         self._norm_channels = sum(p.numel() for k, p in model.named_parameters()
                                   if k.endswith(".weight") and p.ndim == 1)          # all GroupNorm weights (the only 1-D weights)
         self._pgb_arena = self._pgb_table = None
@@ -300,138 +384,63 @@ class UNetEngine:
         return out
 
     def _pack_all(self, need_d, geom=None):
-        """Re-pack the 3x3 kernels of every residual block in ONE launch (vd_wino_pack_batched / vd_pack_conv3x3_batched) into
-        persistent buffers; returns {id(weight): (forward pack, dgrad pack or None)}.
-        Pack state (buffers + device table) is kept PER WEIGHT SET -- the key is the parameters' storage pointers, so raw
-        weights and an EMA view swap (trainer.ema_weights) each keep their own stable buffers and table instead of freeing and
-        re-allocating them on every alternation -- in a small LRU.  ``self._last_pack_state`` is the state the last forward
-        used: a captured HIP graph keeps a reference to it, so the table / U images its pack and convolution nodes point to
-        stay allocated for as long as the graph is cached (diffusion._sample_loop_graph).
-        ``geom`` = (B, H0, W0) of the training input: the input gradients of the layers vd_conv3x3_dgrad_wino43 serves at that
-        geometry take the F(4x4,3x3) image U43 instead of the rotated F(2x2,3x3) one."""
+        """Re-pack the 3x3 kernels of every residual block (ConvPacks.repack: ONE launch per image family for the whole network) and
+        make the result ``self._packs``, the packs of the forward in flight.  The ConvPacks objects are kept PER WEIGHT SET -- the key
+        is the parameters' storage pointers, so raw weights and an EMA view swap (trainer.ema_weights) each keep their own stable
+        buffers and tables instead of freeing and re-allocating them on every alternation -- in a small LRU; whoever still needs an
+        evicted one (a tape, a captured HIP graph: diffusion._sample_loop_graph) holds a reference to it.
+        ``geom`` = (B, H0, W0) of the input: the layers the F(4x4,3x3) kernels serve at that geometry take those images."""
         ws = [c.weight for b in self.plan if b.res is not None for c in (b.res.conv1, b.res.conv2)]
         key = (bool(need_d), H.WINO, H.WINO43_FWD, geom) + tuple(w.data_ptr() for w in ws)
-        if self._pack_state is None:
-            self._pack_state = {}
-        st = self._pack_state.pop(key, None)             # (re-inserted below as the most recent entry)
-        if st is None:
-            dev = ws[0].device
-            sizes = [w.numel() for w in ws]
-            st = dict(n=len(ws))
-            if H.WINO:
-                # Winograd-domain kernels U = G w G^T (csrc/wino.hip): [16][Cout][Cin] forward, [16][Cin][Cout] input gradient;
-                # csrc/wino43.hip: 36 x Cin x Cout in lane order for the input gradients it serves
-                # per layer: which F(4x4,3x3) images the training / inference geometry lets it use (forward: u43f, input gradient: u43);
-                # a layer served by them gets no F(2x2,3x3) image for that direction (a call that declines packs one on demand: _conv)
-                use43, use43f = {}, {}
-                if geom is not None:
-                    for (w, nb, lh, lw, ci, co) in self._conv_geoms(*geom):
-                        use43[id(w)] = need_d and H.wino43_supported(nb, lh, lw, ci, co, co, ci)
-                        use43f[id(w)] = H.wino43_fwd_supported(nb, lh, lw, ci, co, ci, co, co)
-                nf = sum(n for w, n in zip(ws, sizes) if not use43f.get(id(w)))
-                nd = sum(n for w, n in zip(ws, sizes) if not use43.get(id(w))) if need_d else 0
-                n43 = sum(n for w, n in zip(ws, sizes) if use43.get(id(w))) + sum(n for w, n in zip(ws, sizes) if use43f.get(id(w)))
-                uf_all = torch.empty(16 * nf // 9, dtype=torch.float32, device=dev) if nf else None
-                ud_all = torch.empty(16 * nd // 9, dtype=torch.float32, device=dev) if nd else None
-                u43_all = torch.empty(36 * n43 // 9, dtype=torch.float32, device=dev) if n43 else None
-                wrows, wviews, woff, doff, wblk = [], {}, 0, 0, 0
-                rows43, off43, blk43 = [], 0, 0
-                for w, n in zip(ws, sizes):
-                    co, ci = w.shape[0], w.shape[1]
-                    m = 16 * co * ci
-                    uf = ud = u43 = u43f = None
-                    if use43f.get(id(w)):
-                        u43f = u43_all[off43: off43 + 36 * co * ci]
-                        rows43.append([w.data_ptr(), u43f.data_ptr(), 1, co, ci, 0, 0, blk43])
-                        off43 += 36 * co * ci
-                        blk43 += (co // 32) * (ci // 8)
-                    else:
-                        uf = uf_all[woff: woff + m].view(16, co, ci)
-                        woff += m
-                    if need_d and use43.get(id(w)):
-                        u43 = u43_all[off43: off43 + 36 * co * ci]
-                        rows43.append([w.data_ptr(), u43.data_ptr(), 0, co, ci, 0, 0, blk43])
-                        off43 += 36 * co * ci
-                        blk43 += (ci // 32) * (co // 8)
-                    elif need_d:
-                        ud = ud_all[doff: doff + m].view(16, ci, co)
-                        doff += m
-                    wviews[id(w)] = (uf, ud, u43, u43f)
-                    if uf is None and ud is None:
-                        continue
-                    tiled = int(co % 16 == 0 and ci % 16 == 0)
-                    wrows.append([w.data_ptr(), uf.data_ptr() if uf is not None else 0, ud.data_ptr() if ud is not None else 0, co, ci,
-                                  tiled, 0, wblk])
-                    wblk += (co // 16) * (ci // 16) if tiled else (co * ci + 255) // 256
-                st.update(uf=uf_all, ud=ud_all, u43=u43_all, wtable=torch.tensor(wrows, dtype=torch.int64).to(dev) if wrows else None,
-                          nw=len(wrows), wblocks=wblk,
-                          wviews=wviews, table43=torch.tensor(rows43, dtype=torch.int64).to(dev) if rows43 else None,
-                          n43=len(rows43), blocks43=blk43)
-            else:
-                wf_all = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
-                wd_all = torch.empty(sum(sizes), dtype=torch.float32, device=dev) if need_d else None
-                rows, views, off, blk = [], {}, 0, 0
-                for w, n in zip(ws, sizes):
-                    co, ci = w.shape[0], w.shape[1]
-                    wf = wf_all[off: off + n].view(co, 9, ci)
-                    wd = wd_all[off: off + n].view(ci, 9, co) if need_d else None
-                    rows.append([w.data_ptr(), wf.data_ptr(), wd.data_ptr() if need_d else 0, co, ci, ci, co, blk])
-                    views[id(w)] = (wf, wd)
-                    off += n
-                    blk += (n + 255) // 256
-                st.update(wf=wf_all, wd=wd_all, table=torch.tensor(rows, dtype=torch.int64).to(dev), blocks=blk, views=views)
-            while len(self._pack_state) >= self.PACK_STATES_MAX:
-                self._pack_state.pop(next(iter(self._pack_state)))       # least recently used
-        self._pack_state[key] = st
-        self._last_pack_state = st
-        if H.WINO:
-            # every convolution the Winograd kernels serve needs only U; the direct packs are made per tensor, on demand, by
-            # _pack_f / _pack_d for the geometries that fall back (none in the shipped configs)
-            if st["nw"]:
-                H.wino_pack_batched(st["wtable"], st["nw"], st["wblocks"])
-            if st["n43"]:
-                H.wino43_pack_batched(st["table43"], st["n43"], st["blocks43"])
-            self._wino = st["wviews"]
-            return {}
-        H.pack_conv3x3_batched(st["table"], st["n"], st["blocks"])
-        self._wino = None
-        return st["views"]
+        pk = self._pack_lru.pop(key, None)               # (re-inserted below as the most recent entry)
+        if pk is None:
+            pk = ConvPacks(ws, need_d, self._conv_geoms(*geom) if geom is not None else [])
+            while len(self._pack_lru) >= self.PACK_STATES_MAX:
+                self._pack_lru.pop(next(iter(self._pack_lru)))          # least recently used
+        self._pack_lru[key] = self._packs = pk
+        pk.repack()
+        return pk
+
+    @property
+    def packs(self):
+        """the ConvPacks of the last forward (or of the backward in flight): what a captured graph of that forward must keep alive"""
+        return self._packs
+
+    @contextlib.contextmanager
+    def fixed_weights(self):
+        """A sampler holds the weights fixed for one reverse chain: inside the context the first forward's ConvPacks, the FiLM stacks and
+        the thin-kernel / input-convolution images are made once and every later forward uses THEM, whatever was packed in between."""
+        self._fixed = {}
+        try:
+            yield
+        finally:
+            self._fixed = None
+
+    def _layer(self, w):
+        """the images the packs in flight hold for kernel ``w``"""
+        return self._packs.layers.get(id(w), _NO_PACK) if self._packs is not None else _NO_PACK
 
     def _conv(self, x, ldx, w, bias, y, ldy, B, Hh, Ww, Cin, Cout, dgrad=False, res=None, ldres=0, stats_part=None):
         """3x3 convolution with kernel ``w`` (forward) or its input gradient (``dgrad``: x = dy, Cin/Cout are the GEMM's):
         Winograd F(4x4,3x3) / F(2x2,3x3) wherever the geometry is served, the direct implicit GEMM otherwise.  Returns the pixel rows per
         chunk of the GroupNorm partial sums it left in ``stats_part`` (the consuming norm needs the chunk count: _parts)."""
-        wino = getattr(self, "_wino", None)
-        if wino is not None and not dgrad and id(w) in wino and wino[id(w)][3] is not None \
-                and H.wino43_fwd_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0):
+        pk, p = self._packs, self._layer(w)
+        if not dgrad and p.u43f is not None and H.wino43_fwd_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0):
             # forward pass through F(4x4,3x3) (csrc/wino43.hip, dyadic interpolation points); its GroupNorm partials come one chunk per
             # (image, work item)
-            H.conv3x3_wino43_fwd(x, ldx, wino[id(w)][3], bias, y, ldy, B, Hh, Ww, Cin, Cout, res=res, ldres=ldres, stats_part=stats_part)
+            H.conv3x3_wino43_fwd(x, ldx, p.u43f, bias, y, ldy, B, Hh, Ww, Cin, Cout, res=res, ldres=ldres, stats_part=stats_part)
             return H.wino43_fwd_chunk_rows(Hh, Ww)
-        if wino is not None and dgrad and id(w) in wino and wino[id(w)][2] is not None \
-                and H.wino43_supported(B, Hh, Ww, Cout, Cin, ldx, ldy):
+        if dgrad and p.u43 is not None and H.wino43_supported(B, Hh, Ww, Cout, Cin, ldx, ldy):
             # F(4x4,3x3) input gradient (csrc/wino43.hip): x = dy [.., Cin = conv Cout], y = dx [.., Cout = conv Cin].  The pack-time choice
-            # (_pack_all) saw dense pitches; the check above is the one with the pitches of THIS call (dy may be a channel slice of a concat
+            # (ConvPacks) saw dense pitches; the check above is the one with the pitches of THIS call (dy may be a channel slice of a concat
             # buffer) and of this geometry -- a layer it declines falls through to the F(2x2,3x3) / direct forms below.
             assert res is None and bias is None and stats_part is None
-            H.conv3x3_dgrad_wino43(x, ldx, wino[id(w)][2], y, ldy, B, Hh, Ww, Cout, Cin)
+            H.conv3x3_dgrad_wino43(x, ldx, p.u43, y, ldy, B, Hh, Ww, Cout, Cin)
             return None
-        if wino is not None and id(w) in wino and H.wino_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0):
-            U = wino[id(w)][1 if dgrad else 0]
-            if U is None:
-                # a layer packed for an F(4x4,3x3) form whose call declined it (pitches of THIS call): its F(2x2,3x3) image -- rotated for
-                # the input gradient -- is made on demand, into a buffer that lives with the pack state (one allocation per weight and
-                # direction, stable address: also valid inside a captured HIP graph), and re-packed per call like every other image
-                st = self._last_pack_state
-                fb = st.setdefault("fallback_u", {}) if st is not None else {}
-                U = fb.get((id(w), dgrad))
-                if U is None:
-                    shp = (16, w.shape[1], w.shape[0]) if dgrad else (16, w.shape[0], w.shape[1])
-                    U = fb[(id(w), dgrad)] = torch.empty(shp, dtype=torch.float32, device=w.device)
-                if dgrad:
-                    H.wino_pack(w, w.shape[0], w.shape[1], ud=U)
-                else:
-                    H.wino_pack(w, w.shape[0], w.shape[1], uf=U)
+        if p is not _NO_PACK and pk.wino and H.wino_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0):
+            U = p.ud if dgrad else p.uf
+            if U is None:                              # packed for an F(4x4,3x3) form that THIS call's pitches declined
+                U = pk.image(w, dgrad)
             H.conv3x3_wino(x, ldx, U, bias, y, ldy, B, Hh, Ww, Cin, Cout, res=res, ldres=ldres, stats_part=stats_part)
             return H.last_row_tile() // 2              # the F(2x2,3x3) kernels: one chunk per 64 output rows, reported like a 128-row tile
         H.conv3x3(x, ldx, self._pack_d(w) if dgrad else self._pack_f(w), bias, y, ldy, B, Hh, Ww, Cin, Cout, res=res, ldres=ldres,
@@ -439,9 +448,10 @@ class UNetEngine:
         return H.last_row_tile() // 2                  # the tile engine: half its row tile
 
     def _pack_f(self, w, cin_p=None):
-        if self._packed is not None and id(w) in self._packed:
-            return self._packed[id(w)][0]
-        cache = self.pack_cache
+        p = self._layer(w)
+        if p.wf is not None:
+            return p.wf
+        cache = self._fixed
         if cache is not None and id(w) in cache:
             return cache[id(w)]
         co, ci = w.shape[0], w.shape[1]
@@ -453,8 +463,9 @@ class UNetEngine:
         return wf
 
     def _pack_d(self, w, cout_p=None):
-        if self._packed is not None and id(w) in self._packed and self._packed[id(w)][1] is not None:
-            return self._packed[id(w)][1]
+        p = self._layer(w)
+        if p.wd is not None:
+            return p.wd
         co, ci = w.shape[0], w.shape[1]
         cout_p = cout_p or co
         wd = self._new(w, ci, 9, cout_p)
@@ -463,7 +474,7 @@ class UNetEngine:
 
     def _pack_thin(self, w, rows):
         """[rows][Cin] image of a thin-output 3x3 kernel: row co*9+tap = w[co][:, tap], rows beyond 9*Cout are zero"""
-        cache = self.pack_cache
+        cache = self._fixed
         key = ("thin", id(w))
         if cache is not None and key in cache:
             return cache[key]
@@ -556,7 +567,7 @@ class UNetEngine:
         """film[g][i] = fc_i(ta) for every residual block i of width group g: [nb][B][2*Cout], one launch per group"""
         B, E = ta.shape
         films, stacks = {}, {}
-        cache = self.pack_cache
+        cache = self._fixed
         for c2, mods in self.film_groups.items():
             key = ("film", c2)
             if cache is not None and key in cache:
@@ -755,13 +766,13 @@ class UNetEngine:
         assert Ci == m.in_channels and H0 % (1 << (self.levels - 1)) == 0 and W0 % (1 << (self.levels - 1)) == 0
         tape = {} if save else None
         x_nchw = x_nchw.to(torch.float32).contiguous()
-        cache = self.pack_cache
-        if cache is not None and "all" in cache:
-            self._packed = cache["all"]                  # a sampler holds the weights fixed: packed once per chain
+        fixed = self._fixed
+        if fixed is not None and "packs" in fixed:
+            self._packs = fixed["packs"]                 # a sampler holds the weights fixed: packed once per chain
         else:
-            self._packed = self._pack_all(need_d=save, geom=(B, H0, W0))
-            if cache is not None:
-                cache["all"] = self._packed
+            self._pack_all(need_d=save, geom=(B, H0, W0))
+            if fixed is not None:
+                fixed["packs"] = self._packs
         ta = self._embed_fwd(t, y, tape)
         films = self._film_fwd(ta, tape)
         p_drop = float(m.drop_rate) if training else 0.0
@@ -852,7 +863,7 @@ class UNetEngine:
             tape["ta"] = ta
             tape["in"] = dict(x4=x4 if xc is None else None, xc=xc, cip=cip)
             tape["out"] = dict(h=h, coef=coef, a=a, wz=wz)
-            tape["wino"] = getattr(self, "_wino", None)
+            tape["packs"] = self._packs
         return out, tape
 
     def new_grads(self):
@@ -952,7 +963,7 @@ class UNetEngine:
         m = self.m
         self._join_at_progress = bool(join)                    # a listener consumes gradients at every yield: finished means finished on every stream
         B, H0, W0, cop, _ = _chk(dout)
-        self._wino = tape.get("wino", getattr(self, "_wino", None))     # the Winograd images THIS forward packed (another forward may have run since)
+        self._packs = tape["packs"]                            # the images THIS forward packed (another forward may have run since)
         ta = tape["ta"]
         dta = torch.zeros_like(ta)
         dfilms = {c2: self._new(ta, len(mods), B, c2) for c2, mods in self.film_groups.items()}
