@@ -259,8 +259,15 @@ def _two_parts(parts):
     return ptr(p1), c1, k1, ptr(p2), c2, k2
 
 
+def _resampled(H, W, resample):
+    """(Ho, Wo) of an (H, W) image behind the RS_* resampling of the GroupNorm-apply kernels: the one statement of that rule (the engine
+    sizes its buffers by it; a host helper, not a launch wrapper, hence not among the public names)"""
+    return (H // 2, W // 2) if resample == RS_DOWN else ((H * 2, W * 2) if resample == RS_UP else (H, W))
+
+
 def _resampled_hw(H, W, resample):
-    return H * W // 4 if resample == RS_DOWN else (H * W * 4 if resample == RS_UP else H * W)
+    Ho, Wo = _resampled(H, W, resample)
+    return Ho * Wo
 
 
 def _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws):

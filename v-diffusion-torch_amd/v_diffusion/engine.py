@@ -42,16 +42,113 @@ def _chk(t):
     return B, Hh, Ww, C, ld
 
 
-def _splitk(M, N, K):
-    """split-K factor for the small-output weight-gradient GEMMs (K = batch*pixels)."""
-    tiles = ((M + 63) // 64) * ((N + 63) // 64)
-    s = max(1, min(64, 1024 // max(tiles, 1), K // 256))
-    return s
+def _splitk(M, N, K, n=1):
+    """split-K factor for the small-output weight-gradient GEMMs (K = batch*pixels); ``n`` = entries of a grouped launch"""
+    tiles = ((M + 63) // 64) * ((N + 63) // 64) * n
+    return max(1, min(64, 1024 // max(tiles, 1), K // 256))
 
 
-class _Blk:
-    __slots__ = ("prefix", "kind", "cin", "cout", "rs", "attn", "consumes", "res", "att", "level", "dest", "src_hs", "push_hs",
-                 "ch_h")
+# ---- the static plan: every fact the drivers below need about a block is stated HERE, once (_plan), and read from the record
+_Spec = collections.namedtuple("_Spec", "prefix kind cin cout rs level consumes mods")          # a block as the module tree has it
+# a skip-stack entry: block ``producer`` ("in_conv": the first) pushes ``cs`` channels, channels [ch, ch + cs) of block ``consumer``'s concat buffer
+_Push = collections.namedtuple("_Push", "producer cs consumer ch")
+# where an output goes: channels [c0, c0 + width) of the concat buffer of block ``cat``; cat None: a buffer of its own
+_Dest = collections.namedtuple("_Dest", "cat c0 width")
+# parameter-name suffixes of a residual / attention block in the order backward finishes their gradients, and those finished at the
+# end of backward (GroupNorm scales / shifts: _pgb_finish)
+_RES_GRADS = ("conv2.weight", "conv2.bias", "conv1.weight", "conv1.bias", "skip.weight", "skip.bias", "fc.weight", "fc.bias")
+_RES_NORMS = ("norm2.weight", "norm2.bias", "norm1.weight", "norm1.bias")
+_ATT_GRADS = ("proj_out.weight", "proj_out.bias", "proj_in.weight", "proj_in.bias")
+_ATT_NORMS = ("norm.weight", "norm.bias")
+
+
+class _Blk(collections.namedtuple("_Blk", _Spec._fields[:-1] + ("shift", "res", "att", "res_prefix", "att_prefix", "res_names", "att_names",
+           "film", "seed", "src_hs", "push_hs", "ch_h", "in_hs", "dest", "grads", "norm_grads", "report", "ends_group"))):
+    """One entry of the plan: a residual block, an attention block (kind "midattn") or a residual block followed by an attention block.
+      prefix, kind ("down" / "mid" / "midattn" / "up"), cin, cout, level: as the module tree has them; rs: RS_* resampling in front of
+          conv1, shift: levels its output lies below its input (+1 down-sampling, -1 up-sampling)
+      res, att / res_prefix, att_prefix / res_names, att_names: the two modules (None: absent), their parameter-name prefixes (also
+          their tape keys) and {suffix: parameter name}
+      film: (2*cout, index) of the residual part in the batched FiLM projection of its width group; seed: dropout seed index
+      consumes: its input is a concat buffer of cin = ch_h + Cs channels, [0, ch_h) from the previous block and the rest from
+          skip-stack entry src_hs;  push_hs: the entry a down block pushes;  in_hs: the entry a block reads as its input WITHOUT popping
+          it (down blocks and middle.0; None for the others) -- its input gradient accumulates into that entry's gradient
+      dest: _Dest of its output
+      grads: its parameter names in the order backward finishes them, norm_grads: those finished at the end of backward; report: the
+          name backward yields when its gradients are final; ends_group: the last block backward runs of a (level, down / middle / up)
+          group -- the deferred weight gradients are flushed and ``report`` is yielded there"""
+    __slots__ = ()
+
+
+def _plan(model):
+    """(plan: [_Blk] in forward order, pushes: [_Push], film_groups: {2*cout: [residual modules]}) of a UNet module"""
+    hid, mult, nrb = model.hid_channels, list(model.ch_multipliers), model.num_res_blocks
+    levels = len(mult)
+    chs = [hid * k for k in mult]
+    specs = []
+    for i in range(levels):                                                   # reference unet.py:250-263
+        mods = model.downsamples[f"level_{i}"]
+        prev = chs[i - 1] if i else hid
+        for j in range(nrb):
+            specs.append(_Spec(f"downsamples.level_{i}.{j}", "down", prev if j == 0 else chs[i], chs[i], H.RS_NONE, i, False, mods[j]))
+        if i != levels - 1:
+            specs.append(_Spec(f"downsamples.level_{i}.{nrb}", "down", chs[i], chs[i], H.RS_DOWN, i, False, mods[nrb]))
+    for j, kind in enumerate(("mid", "midattn", "mid")):
+        specs.append(_Spec(f"middle.{j}", kind, chs[-1], chs[-1], H.RS_NONE, levels - 1, False, model.middle[j]))
+    for i in range(levels - 1, -1, -1):                                       # reference unet.py:265-284
+        mods = model.upsamples[f"level_{i}"]
+        nxt = hid if i == 0 else chs[i - 1]
+        prv = chs[-1] if i == levels - 1 else chs[i + 1]
+        for j, cin in enumerate([prv + chs[i]] + [2 * chs[i]] * (nrb - 1) + [nxt + chs[i]]):
+            specs.append(_Spec(f"upsamples.level_{i}.{j}", "up", cin, chs[i], H.RS_NONE, i, True, mods[j]))
+        if i != 0:
+            specs.append(_Spec(f"upsamples.level_{i}.{nrb + 1}", "up", chs[i], chs[i], H.RS_UP, i, False, mods[nrb + 1]))
+    # the skip stack, statically: which concat buffer does every pushed tensor land in, and who reads the stack top without popping it?
+    pushes, stack = [["in_conv", hid, None, None]], [0]
+    push_hs, src_hs, in_hs = {}, {}, {}
+    for bi, s in enumerate(specs):
+        if s.kind == "down" or s.prefix == "middle.0":
+            in_hs[bi] = stack[-1]
+        if s.kind == "down":
+            pushes.append([bi, s.cout, None, None])
+            stack.append(len(pushes) - 1)
+            push_hs[bi] = stack[-1]
+        elif s.consumes:
+            k = src_hs[bi] = stack.pop()
+            pushes[k][2:] = bi, s.cin - pushes[k][1]
+    assert not stack, "skip stack not emptied"
+    pushes = [_Push(*p) for p in pushes]
+    group = lambda s: (s.level, "mid" if s.kind.startswith("mid") else s.kind)
+    plan, film_groups = [], {}
+    for bi, s in enumerate(specs):
+        nxt = specs[bi + 1] if bi + 1 < len(specs) else None
+        if s.kind == "midattn":
+            res, att = None, s.mods
+        else:
+            res, att = (s.mods[0], s.mods[1]) if s.kind != "mid" and model.apply_attn[s.level] else (s.mods, None)
+        res_prefix = None if res is None else s.prefix + (".0" if att is not None else "")
+        att_prefix = None if att is None else s.prefix + (".1" if res is not None else "")
+        res_names = {k: f"{res_prefix}.{k}" for k in _RES_GRADS + _RES_NORMS if s.cin != s.cout or not k.startswith("skip.")} if res else {}
+        att_names = {k: f"{att_prefix}.{k}" for k in _ATT_GRADS + _ATT_NORMS} if att else {}
+        grads = tuple(att_names[k] for k in _ATT_GRADS if att) + tuple(res_names[k] for k in _RES_GRADS if k in res_names)   # (backward
+        norm_grads = tuple(att_names[k] for k in _ATT_NORMS if att) + tuple(res_names[k] for k in _RES_NORMS if res)         # runs att first)
+        film = None
+        if res is not None:                 # FiLM projections of equal width run as ONE batched GEMM per pass (_film_fwd)
+            grp = film_groups.setdefault(2 * s.cout, [])
+            film = (2 * s.cout, len(grp))
+            grp.append(res)
+        if s.kind == "down":
+            p = pushes[push_hs[bi]]
+            dest = _Dest(p.consumer, p.ch, p.cs)
+        else:
+            dest = _Dest(bi + 1 if nxt is not None and nxt.consumes else None, 0, s.cout)
+        shift = {H.RS_DOWN: 1, H.RS_UP: -1}.get(s.rs, 0)
+        assert nxt is None or nxt.level == s.level + shift, "a block's output is not at the next block's level"
+        plan.append(_Blk(*s[:-1], shift, res, att, res_prefix, att_prefix, res_names, att_names, film, seed=2 * bi + 1,
+                         src_hs=src_hs.get(bi), push_hs=push_hs.get(bi), ch_h=s.cin - pushes[src_hs[bi]].cs if s.consumes else None,
+                         in_hs=in_hs.get(bi), dest=dest, grads=grads, norm_grads=norm_grads, report=grads[-1],
+                         ends_group=bi == 0 or group(specs[bi - 1]) != group(s)))
+    return plan, pushes, film_groups
 
 
 class _Pack(collections.namedtuple("_Pack", "uf ud u43 u43f wf wd", defaults=(None,) * 6)):
@@ -138,84 +235,31 @@ class ConvPacks:
         return U
 
 
+class _Cat:
+    """The concat buffer ``[B,H,W,Ch+Cs]`` of one consuming up-block with the GroupNorm partials its two producers left behind
+    (``parts``: channel offset -> what _parts returns)"""
+    __slots__ = ("buf", "parts")
+
+    def __init__(self, buf):
+        self.buf, self.parts = buf, {}
+
+    def joined(self, ch_h):
+        """partials of the whole buffer -- both channel ranges, in channel order -- or None when a producer left none"""
+        pa, pb = self.parts.get(0), self.parts.get(ch_h)
+        return pa + pb if (pa is not None and pb is not None) else None
+
+
 class UNetEngine:
     """Static execution plan + forward/backward drivers for one ``UNet`` module."""
 
     def __init__(self, model):
         self.m = model
-        hid, mult, nrb = model.hid_channels, list(model.ch_multipliers), model.num_res_blocks
-        levels = len(mult)
-        chs = [hid * k for k in mult]
-        plan = []
-
-        def add(prefix, kind, cin, cout, rs, attn, consumes, level, container):
-            b = _Blk()
-            b.prefix, b.kind, b.cin, b.cout, b.rs, b.attn, b.consumes, b.level = prefix, kind, cin, cout, rs, attn, consumes, level
-            if kind == "midattn":
-                b.res, b.att = None, container
-            elif attn:
-                b.res, b.att = container[0], container[1]
-            else:
-                b.res, b.att = container, None
-            plan.append(b)
-
-        for i in range(levels):                                               # reference unet.py:250-263
-            mods = model.downsamples[f"level_{i}"]
-            prev = chs[i - 1] if i else hid
-            for j in range(nrb):
-                add(f"downsamples.level_{i}.{j}", "down", prev if j == 0 else chs[i], chs[i], H.RS_NONE, model.apply_attn[i],
-                    False, i, mods[j])
-            if i != levels - 1:
-                add(f"downsamples.level_{i}.{nrb}", "down", chs[i], chs[i], H.RS_DOWN, model.apply_attn[i], False, i, mods[nrb])
-        add("middle.0", "mid", chs[-1], chs[-1], H.RS_NONE, False, False, levels - 1, model.middle[0])
-        add("middle.1", "midattn", chs[-1], chs[-1], H.RS_NONE, True, False, levels - 1, model.middle[1])
-        add("middle.2", "mid", chs[-1], chs[-1], H.RS_NONE, False, False, levels - 1, model.middle[2])
-        for i in range(levels - 1, -1, -1):                                   # reference unet.py:265-284
-            mods = model.upsamples[f"level_{i}"]
-            nxt = hid if i == 0 else chs[i - 1]
-            prv = chs[-1] if i == levels - 1 else chs[i + 1]
-            cins = [prv + chs[i]] + [2 * chs[i]] * (nrb - 1) + [nxt + chs[i]]
-            for j, cin in enumerate(cins):
-                add(f"upsamples.level_{i}.{j}", "up", cin, chs[i], H.RS_NONE, model.apply_attn[i], True, i, mods[j])
-            if i != 0:
-                add(f"upsamples.level_{i}.{nrb + 1}", "up", chs[i], chs[i], H.RS_UP, model.apply_attn[i], False, i, mods[nrb + 1])
-        self.plan = plan
-        # ---- static skip-stack analysis: which concat buffer does every pushed tensor land in?
-        pushes = [["in_conv", hid, None, None]]          # [producer, Cs, consumer block index, Ch]
-        sid = [0]
-        for bi, b in enumerate(plan):
-            b.push_hs = None
-            b.src_hs = None
-            b.ch_h = None
-            if b.kind == "down":
-                pushes.append([bi, b.cout, None, None])
-                sid.append(len(pushes) - 1)
-                b.push_hs = len(pushes) - 1
-            elif b.consumes:
-                k = sid.pop()
-                b.src_hs = k
-                b.ch_h = b.cin - pushes[k][1]
-                pushes[k][2], pushes[k][3] = bi, b.ch_h
-        assert not sid, "skip stack not emptied"
-        self.pushes = pushes
-        for bi, b in enumerate(plan):                    # where does each block write its output?
-            if b.kind == "down":
-                k = b.push_hs
-                b.dest = ("cat", pushes[k][2], pushes[k][3], pushes[k][1])
-            else:
-                nxt = plan[bi + 1] if bi + 1 < len(plan) else None
-                b.dest = ("cat", bi + 1, 0, b.cout) if (nxt is not None and nxt.consumes) else ("plain",)
-        self.levels = levels
-        # FiLM projections (reference unet.py:129,143: one Linear per residual block, all fed by the SAME activated
-        # embedding): blocks with equal width are run as ONE batched GEMM per pass instead of a launch-latency-bound
-        # M = batch GEMM per block.  film_slot: residual-block prefix -> (2*Cout, index inside its group)
-        self.film_groups, self.film_slot = {}, {}
-        for b in plan:
-            if b.res is not None:
-                pre = b.prefix + (".0" if b.att is not None else "")
-                grp = self.film_groups.setdefault(2 * b.cout, [])
-                self.film_slot[pre] = (2 * b.cout, len(grp))
-                grp.append(b.res)
+        self.levels = len(model.ch_multipliers)
+        # film_groups: FiLM projections (reference unet.py:129,143: one Linear per residual block, all fed by the SAME activated
+        # embedding) of equal width, run as ONE batched GEMM per pass instead of a launch-latency-bound M = batch GEMM per block;
+        # film_slot: residual-block prefix -> (2*Cout, index inside its group)
+        self.plan, self.pushes, self.film_groups = _plan(model)
+        self.film_slot = {b.res_prefix: b.film for b in self.plan if b.res is not None}
         self._pack_lru = {}               # {weight-set key: ConvPacks}, at most PACK_STATES_MAX (_pack_all)
         self._packs = None                # the ConvPacks of the forward (or backward) in flight
         self._fixed = None                # {} inside fixed_weights(): what one sampler chain packs once; None otherwise -- training repacks
@@ -319,11 +363,8 @@ class UNetEngine:
             for dy, x, dw, db in q:
                 H.gemm(dy, x, dw, M, N, K, a_kind=H.COL, b_kind=H.COL, lda=lda, ldb=ldb, ldc=ldc, splitk=_splitk(M, N, K), colsum=db)
             return
-        if H.GROUPED_AUTO_SPLIT:      # slab count that fills whole residency rounds of the chip (vd_gemm_grouped_wgrad_auto_split)
-            S = H.lib().vd_gemm_grouped_wgrad_auto_split(len(q), M, N, K, 1, 64)
-        else:
-            tiles = ((M + 63) // 64) * ((N + 63) // 64) * len(q)
-            S = max(1, min(64, 1024 // max(tiles, 1), K // 256))
+        # slab count that fills whole residency rounds of the chip (vd_gemm_grouped_wgrad_auto_split), or the per-entry rule over all tiles
+        S = H.lib().vd_gemm_grouped_wgrad_auto_split(len(q), M, N, K, 1, 64) if H.GROUPED_AUTO_SPLIT else _splitk(M, N, K, len(q))
         H.gemm_grouped_wgrad(q, M, N, K, lda, ldb, ldc, S)
 
     def _wgrad_flush(self):
@@ -374,11 +415,7 @@ class UNetEngine:
         for b in self.plan:
             if b.res is None:
                 continue
-            lh, lw = self._res_of(b.level, H0, W0)
-            if b.rs == H.RS_DOWN:
-                lh, lw = lh // 2, lw // 2
-            elif b.rs == H.RS_UP:
-                lh, lw = lh * 2, lw * 2
+            lh, lw = H._resampled(*self._res_of(b.level, H0, W0), b.rs)
             out.append((b.res.conv1.weight, B, lh, lw, b.cin, b.cout))
             out.append((b.res.conv2.weight, B, lh, lw, b.cout, b.cout))
         return out
@@ -597,17 +634,18 @@ class UNetEngine:
             H.colsum(P, B * E, nb, B * E, dta.view(-1), accumulate=True)
 
     # ------------------------------------------------------------------------------------------ residual block
-    def _res_fwd(self, blk, mod, prefix, x, films, dest, p_drop, seed, tape, x_parts=None):
+    def _res_fwd(self, blk, x, films, dest, p_drop, seed, tape, x_parts=None):
+        mod, prefix = blk.res, blk.res_prefix
         B, Hh, Ww, Cin, ldx = _chk(x)
         Cout, rs = blk.cout, blk.rs
-        Ho, Wo = (Hh // 2, Ww // 2) if rs == H.RS_DOWN else ((Hh * 2, Ww * 2) if rs == H.RS_UP else (Hh, Ww))
+        Ho, Wo = H._resampled(Hh, Ww, rs)
         a1 = self._new(x, B, Ho, Wo, Cin)
         coef1 = self._norm(x, x_parts, mod.norm1, None, 1, 0.0, 0, rs, a1, B, Hh, Ww, Cin)
         h1 = self._new(x, B, Ho, Wo, Cout)
         ph = self._part(x, B, Ho * Wo, Cout)
         rows = self._conv(a1, Cin, mod.conv1.weight, mod.conv1.bias, h1, Cout, B, Ho, Wo, Cin, Cout, stats_part=ph)
         h1_parts = self._parts(ph, Cout, Ho * Wo, rows)
-        c2, fi = self.film_slot[prefix]
+        c2, fi = blk.film
         film = films[c2][fi]                              # [B][2*Cout], contiguous slice of the group's batched GEMM output
         a2 = self._new(x, B, Ho, Wo, Cout)
         coef2 = self._norm(h1, h1_parts, mod.norm2, film, 1, p_drop, seed, H.RS_NONE, a2, B, Ho, Wo, Cout)
@@ -632,27 +670,27 @@ class UNetEngine:
                                 seed=seed, p=p_drop)
         return out_parts
 
-    def _res_bwd(self, blk, mod, prefix, ctx, dy, dx, dx_accumulate, ta, dfilms, G):
+    def _res_bwd(self, blk, ctx, dy, dx, dx_accumulate, ta, dfilms, G):
+        mod = blk.res
+        g = {s: G[name] for s, name in blk.res_names.items()}          # this block's gradient tensors by parameter-name suffix
         x, a1, h1, a2, film = ctx["x"], ctx["a1"], ctx["h1"], ctx["a2"], ctx["film"]
         B, Hh, Ww, Cin, ldx = _chk(x)
         _, Ho, Wo, Cout, lddy = _chk(dy)
         rs = blk.rs
         # conv2
-        self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, G[prefix + ".conv2.weight"], Cout, Cout,
-                        dbias=G[prefix + ".conv2.bias"])
+        self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"])
         da2 = self._new(x, B, Ho, Wo, Cout)
         self._conv(dy, lddy, mod.conv2.weight, None, da2, Cout, B, Ho, Wo, Cout, Cout, dgrad=True)
         # norm2 + FiLM + SiLU + dropout
         dh1 = self._new(x, B, Ho, Wo, Cout)
-        c2, fi = self.film_slot[prefix]
+        c2, fi = blk.film
         dfilm = dfilms[c2][fi]
         H.gn_apply_bwd(da2, Cout, h1, Cout, ctx["coef2"], mod.norm2.weight, mod.norm2.bias, film, 1, ctx["p"], ctx["seed"],
                        H.RS_NONE, None, 0, dh1, Cout, False, dfilm, None, None, False, B, Ho, Wo, Cout, GROUPS,
-                       pgb_keep=self._pgb(B, Cout, G[prefix + ".norm2.weight"], G[prefix + ".norm2.bias"]))
+                       pgb_keep=self._pgb(B, Cout, g["norm2.weight"], g["norm2.bias"]))
         del da2
         # conv1
-        self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, G[prefix + ".conv1.weight"], Cin, Cout,
-                        dbias=G[prefix + ".conv1.bias"])
+        self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"])
         da1 = self._new(x, B, Ho, Wo, Cin)
         self._conv(dh1, Cout, mod.conv1.weight, None, da1, Cin, B, Ho, Wo, Cout, Cin, dgrad=True)
         del dh1
@@ -661,7 +699,7 @@ class UNetEngine:
             xs = ctx["xs"]
             P = B * Ho * Wo
             w = mod.skip.weight
-            self._wgrad(dy, xs, G[prefix + ".skip.weight"], G[prefix + ".skip.bias"], Cout, Cin, P, lddy, _ld(xs), Cin)
+            self._wgrad(dy, xs, g["skip.weight"], g["skip.bias"], Cout, Cin, P, lddy, _ld(xs), Cin)
             dsk = self._new(x, B, Ho, Wo, Cin)
             H.gemm(dy, w, dsk, P, Cin, Cout, a_kind=H.ROW, b_kind=H.COL, lda=lddy, ldb=Cin, ldc=Cin)
         else:
@@ -675,13 +713,14 @@ class UNetEngine:
         # norm1 + SiLU (+ resample) and the sum with the skip-path gradient
         H.gn_apply_bwd(da1, Cin, x, ldx, ctx["coef1"], mod.norm1.weight, mod.norm1.bias, None, 1, 0.0, 0, rs, addt, _ld(addt),
                        dx, _ld(dx), dx_accumulate, None, None, None, False, B, Hh, Ww, Cin, GROUPS,
-                       pgb_keep=self._pgb(B, Cin, G[prefix + ".norm1.weight"], G[prefix + ".norm1.bias"]))
+                       pgb_keep=self._pgb(B, Cin, g["norm1.weight"], g["norm1.bias"]))
         # FiLM projection film = fc(ta): weight/bias gradient here (keeps the gradient-completion order); the embedding
         # gradient of all blocks is one batched GEMM at the end of backward (_film_bwd)
-        self._linear_bwd(ta, mod.fc.weight, dfilm, G[prefix + ".fc.weight"], G[prefix + ".fc.bias"], None)
+        self._linear_bwd(ta, mod.fc.weight, dfilm, g["fc.weight"], g["fc.bias"], None)
 
     # ------------------------------------------------------------------------------------------ attention block
-    def _attn_fwd(self, mod, prefix, x, dest, tape, x_parts=None):
+    def _attn_fwd(self, blk, x, dest, tape, x_parts=None):
+        mod, prefix = blk.att, blk.att_prefix
         B, Hh, Ww, C, ldx = _chk(x)
         L, nh, hd = Hh * Ww, mod.num_heads, mod.head_dim
         hid = nh * hd
@@ -718,7 +757,9 @@ class UNetEngine:
             tape[prefix] = dict(x=x, coef=coef, xn=xn, qkv=qkv, P=S, O=O, lse=lse)
         return out_parts
 
-    def _attn_bwd(self, mod, prefix, ctx, dy, dx, dx_accumulate, G):
+    def _attn_bwd(self, blk, ctx, dy, dx, dx_accumulate, G):
+        mod = blk.att
+        g = {s: G[name] for s, name in blk.att_names.items()}
         x, xn, qkv, P, O = ctx["x"], ctx["xn"], ctx["qkv"], ctx["P"], ctx["O"]
         B, Hh, Ww, C, ldx = _chk(x)
         lddy = _ld(dy)
@@ -726,7 +767,7 @@ class UNetEngine:
         hid, ld = nh * hd, 3 * nh * hd
         M = B * L
         # proj_out
-        self._wgrad(dy, O, G[prefix + ".proj_out.weight"], G[prefix + ".proj_out.bias"], C, hid, M, lddy, hid, hid)
+        self._wgrad(dy, O, g["proj_out.weight"], g["proj_out.bias"], C, hid, M, lddy, hid, hid)
         dO = self._new(x, B, L, hid)
         H.gemm(dy, mod.proj_out.weight, dO, M, hid, C, a_kind=H.ROW, b_kind=H.COL, lda=lddy, ldb=hid, ldc=hid)
         dqkv = self._new(x, B, L, ld)
@@ -750,13 +791,112 @@ class UNetEngine:
             del dP
         del dO
         # proj_in
-        self._wgrad(dqkv, xn, G[prefix + ".proj_in.weight"], G[prefix + ".proj_in.bias"], ld, C, M, ld, C, C)
+        self._wgrad(dqkv, xn, g["proj_in.weight"], g["proj_in.bias"], ld, C, M, ld, C, C)
         dxn = self._new(x, B, Hh, Ww, C)
         H.gemm(dqkv, mod.proj_in.weight, dxn, M, C, ld, a_kind=H.ROW, b_kind=H.COL, lda=ld, ldb=C, ldc=C)
         # norm (no activation) + the residual branch
         H.gn_apply_bwd(dxn, C, x, ldx, ctx["coef"], mod.norm.weight, mod.norm.bias, None, 0, 0.0, 0, H.RS_NONE, dy, lddy, dx,
                        _ld(dx), dx_accumulate, None, None, None, False, B, Hh, Ww, C, GROUPS,
-                       pgb_keep=self._pgb(B, C, G[prefix + ".norm.weight"], G[prefix + ".norm.bias"]))
+                       pgb_keep=self._pgb(B, C, g["norm.weight"], g["norm.bias"]))
+
+    # ------------------------------------------------------------------------------------------ input / output convolution
+    def _in_conv_fwd(self, x_nchw, d, tape):
+        """3x3 convolution of the (B,Cin,H,W) NCHW input into the NHWC view ``d``; returns the GroupNorm partials it left of ``d``"""
+        m = self.m
+        B, Ci, H0, W0 = x_nchw.shape
+        hid, cip = m.hid_channels, (Ci + 3) // 4 * 4
+        x4 = self._new(x_nchw, B, H0, W0, cip)
+        H.nchw_to_nhwc(x_nchw, x4, B, Ci, H0, W0, cip)
+        pp = self._part(x_nchw, B, H0 * W0, hid)
+        if pp is not None and (H0 * W0) % 64:
+            pp = None
+        xc = None
+        if cip <= THIN:
+            # thin input (3 -> hid): im2col of the 4-channel image once, then a plain K = 36 GEMM (see vd_im2col3x3)
+            xc = self._new(x_nchw, B * H0 * W0, 9 * cip)
+            H.im2col3x3(x4, cip, xc, B, H0, W0, cip)
+            H.gemm(xc, self._pack_f(m.in_conv.weight, cip), d, B * H0 * W0, hid, 9 * cip, a_kind=H.ROW, b_kind=H.ROW,
+                   lda=9 * cip, ldb=9 * cip, ldc=_ld(d), bias=m.in_conv.bias, stats=pp, stats_hw=H0 * W0)
+        else:
+            H.conv3x3(x4, cip, self._pack_f(m.in_conv.weight, cip), m.in_conv.bias, d, _ld(d), B, H0, W0, cip, hid, stats_part=pp)
+        if tape is not None:
+            tape["in"] = dict(x4=x4 if xc is None else None, xc=xc, cip=cip)
+        return self._parts(pp, hid, H0 * W0)
+
+    def _in_conv_bwd(self, ctx, dy0, G):
+        """weight and bias gradient of the input convolution"""
+        B, H0, W0, hid, lddy = _chk(dy0)
+        xc, cip, ci = ctx["xc"], ctx["cip"], self.m.in_channels
+        if xc is not None:
+            gw = self._new(dy0, hid, 9 * cip)
+            H.gemm(dy0, xc, gw, hid, 9 * cip, B * H0 * W0, a_kind=H.COL, b_kind=H.COL, lda=lddy, ldb=9 * cip, ldc=9 * cip,
+                   splitk=_splitk(hid, 9 * cip, B * H0 * W0), colsum=G["in_conv.bias"])
+            H.thin_wgrad_finish(gw, hid, cip, ci, G["in_conv.weight"])
+        else:
+            H.conv3x3_wgrad(ctx["x4"], cip, dy0, lddy, B, H0, W0, cip, hid, G["in_conv.weight"], ci, hid, dbias=G["in_conv.bias"])
+
+    def _in_conv_dgrad(self, ctx, dy0):
+        """d/dx (NCHW) of the network input"""
+        m = self.m
+        B, H0, W0, hid, lddy = _chk(dy0)
+        cip = ctx["cip"]
+        d4 = self._new(dy0, B, H0, W0, cip)
+        if cip != m.in_channels:
+            d4.zero_()
+        H.conv3x3(dy0, lddy, self._pack_d(m.in_conv.weight, hid), None, d4, cip, B, H0, W0, hid, m.in_channels)
+        dx = self._new(dy0, B, m.in_channels, H0, W0)
+        H.nhwc_to_nchw(d4, cip, dx, B, m.in_channels, H0, W0)
+        return dx
+
+    def _out_conv_fwd(self, h, h_parts, tape):
+        """GN -> SiLU -> 3x3 into a zeroed ``[B,H,W,Cp]`` (Cp = out_channels rounded up to 4)"""
+        m = self.m
+        B, H0, W0, C0, _ = _chk(h)
+        gn, conv = m.out_conv[0], m.out_conv[2]
+        a = self._new(h, B, H0, W0, C0)
+        coef = self._norm(h, h_parts, gn, None, 1, 0.0, 0, H.RS_NONE, a, B, H0, W0, C0)
+        co, cop = m.out_channels, (m.out_channels + 3) // 4 * 4
+        out = torch.zeros((B, H0, W0, cop), dtype=torch.float32, device=h.device)
+        wz = None
+        if co <= THIN:
+            # thin output (hid -> 3): z[q][co*9+tap] = a[q] . w[co][tap] as a plain GEMM, then the 9-tap gather (vd_tap_gather)
+            nz = (9 * co + 3) // 4 * 4
+            wz = self._pack_thin(conv.weight, nz)
+            z = self._new(h, B * H0 * W0, nz)
+            H.gemm(a, wz, z, B * H0 * W0, 9 * co, C0, a_kind=H.ROW, b_kind=H.ROW, lda=C0, ldb=C0, ldc=nz)
+            H.tap_gather(z, nz, conv.bias, out, cop, B, H0, W0, co)
+        else:
+            H.conv3x3(a, C0, self._pack_f(conv.weight), conv.bias, out, cop, B, H0, W0, C0, co)
+        if tape is not None:
+            tape["out"] = dict(h=h, coef=coef, a=a, wz=wz)
+        return out
+
+    def _out_conv_bwd(self, o, dout, G):
+        """gradients of the output convolution and its norm; returns the gradient of the last block's output"""
+        m = self.m
+        B, H0, W0, cop, _ = _chk(dout)
+        gn, conv = m.out_conv[0], m.out_conv[2]
+        C0, co, P0 = o["a"].shape[3], m.out_channels, B * H0 * W0
+        da = self._new(dout, B, H0, W0, C0)
+        if o["wz"] is not None:
+            wz = o["wz"]
+            nz = wz.shape[0]
+            dz = self._new(dout, P0, nz)
+            H.tap_spread(dout, cop, dz, nz, B, H0, W0, co)                   # dz[q][co*9+tap] = dout[q - off(tap)][co]
+            gz, cs = self._new(dout, nz, C0), self._new(dout, nz)
+            H.gemm(dz, o["a"], gz, nz, C0, P0, a_kind=H.COL, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0, splitk=_splitk(nz, C0, P0),
+                   colsum=cs)
+            H.thin_wgrad_finish(gz, co, C0, C0, G["out_conv.2.weight"], colsum=cs, cs_stride=9, cs_off=4, dbias=G["out_conv.2.bias"])
+            H.gemm(dz, wz, da, P0, C0, nz, a_kind=H.ROW, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0)
+            del dz
+        else:
+            H.conv3x3_wgrad(o["a"], C0, dout, cop, B, H0, W0, C0, cop, G["out_conv.2.weight"], C0, co, dbias=G["out_conv.2.bias"])
+            H.conv3x3(dout, cop, self._pack_d(conv.weight, cop), None, da, C0, B, H0, W0, cop, C0)
+        dh = self._new(dout, B, H0, W0, C0)
+        H.gn_apply_bwd(da, C0, o["h"], _ld(o["h"]), o["coef"], gn.weight, gn.bias, None, 1, 0.0, 0, H.RS_NONE, None, 0, dh, C0,
+                       False, None, None, None, False, B, H0, W0, C0, GROUPS,
+                       pgb_keep=self._pgb(B, C0, G["out_conv.0.weight"], G["out_conv.0.bias"]))
+        return dh
 
     # ------------------------------------------------------------------------------------------ whole network
     def forward(self, x_nchw, t, y, training, save):
@@ -777,92 +917,44 @@ class UNetEngine:
         films = self._film_fwd(ta, tape)
         p_drop = float(m.drop_rate) if training else 0.0
         base_seed = int(torch.empty((), dtype=torch.int64).random_().item()) if p_drop > 0 else 0
-        cip = (Ci + 3) // 4 * 4
-        x4 = self._new(x_nchw, B, H0, W0, cip)
-        H.nchw_to_nhwc(x_nchw, x4, B, Ci, H0, W0, cip)
-        # concat buffers, one per consuming up-block
-        cats = {}
-        for bi, b in enumerate(self.plan):
-            if b.consumes:
-                hh, ww = self._res_of(b.level, H0, W0)
-                cats[bi] = self._new(x_nchw, B, hh, ww, b.cin)
+        # concat buffers, one per consuming up-block; the GroupNorm partials of each channel range travel with it
+        cats = {bi: _Cat(self._new(x_nchw, B, *self._res_of(b.level, H0, W0), b.cin)) for bi, b in enumerate(self.plan) if b.consumes}
 
-        def dest_of(spec, hh, ww):
-            if spec[0] == "cat":
-                _, u, c0, c = spec
-                return cats[u][..., c0:c0 + c]
-            return self._new(x_nchw, B, hh, ww, spec[1])
+        def place(d, hh, ww):                            # the output view of a _Dest and the concat buffer it is a slice of (or None)
+            if d.cat is None:
+                return self._new(x_nchw, B, hh, ww, d.width), None
+            return cats[d.cat].buf[..., d.c0:d.c0 + d.width], cats[d.cat]
 
         p0 = self.pushes[0]
-        d = dest_of(("cat", p0[2], p0[3], p0[1]), H0, W0)
-        pp = self._part(x_nchw, B, H0 * W0, m.hid_channels)
-        if pp is not None and (H0 * W0) % 64:
-            pp = None
-        xc = None
-        if cip <= THIN:
-            # thin input (3 -> hid): im2col of the 4-channel image once, then a plain K = 36 GEMM (see vd_im2col3x3)
-            xc = self._new(x_nchw, B * H0 * W0, 9 * cip)
-            H.im2col3x3(x4, cip, xc, B, H0, W0, cip)
-            H.gemm(xc, self._pack_f(m.in_conv.weight, cip), d, B * H0 * W0, m.hid_channels, 9 * cip, a_kind=H.ROW, b_kind=H.ROW,
-                   lda=9 * cip, ldb=9 * cip, ldc=_ld(d), bias=m.in_conv.bias, stats=pp, stats_hw=H0 * W0)
-        else:
-            H.conv3x3(x4, cip, self._pack_f(m.in_conv.weight, cip), m.in_conv.bias, d, _ld(d), B, H0, W0, cip, m.hid_channels,
-                      stats_part=pp)
-        cat_parts = {p0[2]: {p0[3]: self._parts(pp, m.hid_channels, H0 * W0)}}      # consumer block -> {channel offset: partials}
-        hs_top, h = d, None
-        top_parts, h_parts = cat_parts[p0[2]][p0[3]], None
+        hs_top, cat = place(_Dest(p0.consumer, p0.ch, p0.cs), H0, W0)
+        top_parts = cat.parts[p0.ch] = self._in_conv_fwd(x_nchw, hs_top, tape)
+        h = h_parts = None
         for bi, b in enumerate(self.plan):
-            if b.kind == "down":
+            if b.in_hs is not None:
                 inp, inp_parts = hs_top, top_parts
-            elif b.kind in ("mid", "midattn"):
-                inp, inp_parts = (hs_top, top_parts) if h is None else (h, h_parts)
             elif b.consumes:
-                inp = cats[bi]
-                pa, pb = cat_parts.get(bi, {}).get(0), cat_parts.get(bi, {}).get(b.ch_h)
-                inp_parts = pa + pb if (pa is not None and pb is not None) else None
+                inp, inp_parts = cats[bi].buf, cats[bi].joined(b.ch_h)
             else:
                 inp, inp_parts = h, h_parts
-            _, ih, iw, _, _ = _chk(inp)
-            oh, ow = (ih // 2, iw // 2) if b.rs == H.RS_DOWN else ((ih * 2, iw * 2) if b.rs == H.RS_UP else (ih, iw))
-            spec = b.dest if b.dest[0] == "cat" else ("plain", b.cout)
-            out = dest_of(spec, oh, ow)
-            if b.kind == "midattn":
-                out_parts = self._attn_fwd(b.att, b.prefix, inp, out, tape, inp_parts)
+            oh, ow = H._resampled(inp.shape[1], inp.shape[2], b.rs)
+            out, cat = place(b.dest, oh, ow)
+            if b.res is None:
+                out_parts = self._attn_fwd(b, inp, out, tape, inp_parts)
             elif b.att is not None:
                 mid = self._new(x_nchw, B, oh, ow, b.cout)
-                mid_parts = self._res_fwd(b, b.res, b.prefix + ".0", inp, films, mid, p_drop, base_seed + 2 * bi + 1, tape, inp_parts)
-                out_parts = self._attn_fwd(b.att, b.prefix + ".1", mid, out, tape, mid_parts)
+                mid_parts = self._res_fwd(b, inp, films, mid, p_drop, base_seed + b.seed, tape, inp_parts)
+                out_parts = self._attn_fwd(b, mid, out, tape, mid_parts)
             else:
-                out_parts = self._res_fwd(b, b.res, b.prefix, inp, films, out, p_drop, base_seed + 2 * bi + 1, tape, inp_parts)
-            if spec[0] == "cat":
-                cat_parts.setdefault(spec[1], {})[spec[2]] = out_parts
+                out_parts = self._res_fwd(b, inp, films, out, p_drop, base_seed + b.seed, tape, inp_parts)
+            if cat is not None:
+                cat.parts[b.dest.c0] = out_parts
             if b.kind == "down":
                 hs_top, top_parts = out, out_parts
             else:
                 h, h_parts = out, out_parts
-        # out_conv: GN -> SiLU -> 3x3
-        C0 = m.hid_channels * m.ch_multipliers[0]
-        gn, conv = m.out_conv[0], m.out_conv[2]
-        a = self._new(h, B, H0, W0, C0)
-        coef = self._norm(h, h_parts, gn, None, 1, 0.0, 0, H.RS_NONE, a, B, H0, W0, C0)
-        co = m.out_channels
-        cop = (co + 3) // 4 * 4
-        out = torch.zeros((B, H0, W0, cop), dtype=torch.float32, device=h.device)
-        wz = None
-        if co <= THIN:
-            # thin output (hid -> 3): z[q][co*9+tap] = a[q] . w[co][tap] as a plain GEMM, then the 9-tap gather (vd_tap_gather)
-            nz = (9 * co + 3) // 4 * 4
-            wz = self._pack_thin(conv.weight, nz)
-            z = self._new(h, B * H0 * W0, nz)
-            H.gemm(a, wz, z, B * H0 * W0, 9 * co, C0, a_kind=H.ROW, b_kind=H.ROW, lda=C0, ldb=C0, ldc=nz)
-            H.tap_gather(z, nz, conv.bias, out, cop, B, H0, W0, co)
-            del z
-        else:
-            H.conv3x3(a, C0, self._pack_f(conv.weight), conv.bias, out, cop, B, H0, W0, C0, co)
+        out = self._out_conv_fwd(h, h_parts, tape)
         if tape is not None:
             tape["ta"] = ta
-            tape["in"] = dict(x4=x4 if xc is None else None, xc=xc, cip=cip)
-            tape["out"] = dict(h=h, coef=coef, a=a, wz=wz)
             tape["packs"] = self._packs
         return out, tape
 
@@ -886,61 +978,32 @@ class UNetEngine:
         """The names ``backward_steps`` yields, in order (static: a function of the plan): the output convolution, the last block of every
         (UNet level, down / middle / up) group -- of every block under VD_READY_PER_BLOCK when a listener joins -- the input convolution,
         and None for the end of backward (GroupNorm parameters and the embeddings finish there)."""
-        pts = ["out_conv.2.bias"]
-        grp = lambda q: (q.level, "mid" if q.kind.startswith("mid") else q.kind)
-        for bi in range(len(self.plan) - 1, -1, -1):
-            b = self.plan[bi]
-            nxt = self.plan[bi - 1] if bi > 0 else None
-            if nxt is None or grp(nxt) != grp(b):
-                pts.append(b.prefix + ".proj_in.bias" if b.kind == "midattn" else (b.prefix + (".0" if b.att is not None else "") + ".fc.bias"))
-        return pts + ["in_conv.bias", None]
+        return ["out_conv.2.bias"] + [b.report for b in reversed(self.plan) if b.ends_group] + ["in_conv.bias", None]
 
     def grad_segments(self):
         """[(boundary name, [parameter names])] in BACKWARD order: segment j's gradients are final when ``backward_steps`` yields its
         boundary; the last segment (input convolution, every GroupNorm scale / shift, the embeddings) is final when the pass ends
         (boundary None).  The cut points of the chain of autograd nodes of models/unet.py."""
         if self._segments is None:
-            bounds = [p for p in self.progress_points() if p not in ("in_conv.bias", None)] + [None]
-            order, segs, i = self.completion_order(), [], 0
-            for bnd in bounds:
-                names = []
-                while i < len(order):
-                    names.append(order[i])
-                    i += 1
-                    if order[i - 1] == bnd:
-                        break
-                segs.append((bnd, names))
-            assert i == len(order) and all(n for _, n in segs)
-            self._segments = segs
+            bounds = self.progress_points()[:-2]             # (the input convolution finishes with the rest)
+            segs, names = [], []
+            for n in self.completion_order():
+                names.append(n)
+                if n in bounds:
+                    segs.append((n, names))
+                    names = []
+            self._segments = segs + [(None, names)]
+            assert [bnd for bnd, _ in segs] == bounds and all(n for _, n in self._segments)
         return self._segments
 
     def completion_order(self):
         """Parameter names in the order ``backward_steps`` finishes their gradients: block by block from the output back (the
         matmul-shaped gradients, i.e. all the bytes), then the GroupNorm scales / shifts of the whole network (their per-image terms
         are summed by one launch at the end of backward: _pgb_finish), then the embeddings."""
-        names = ["out_conv.2.weight", "out_conv.2.bias"]
-        norms = ["out_conv.0.weight", "out_conv.0.bias"]
+        back = self.plan[::-1]
+        names = ["out_conv.2.weight", "out_conv.2.bias"] + [n for b in back for n in b.grads] + ["in_conv.weight", "in_conv.bias"] + \
+                ["out_conv.0.weight", "out_conv.0.bias"] + [n for b in back for n in b.norm_grads]
         have = dict(self.m.named_parameters())
-
-        def res(p):
-            out = [p + s for s in (".conv2.weight", ".conv2.bias", ".conv1.weight", ".conv1.bias")]
-            norms.extend(p + s for s in (".norm2.weight", ".norm2.bias", ".norm1.weight", ".norm1.bias"))
-            if p + ".skip.weight" in have:
-                out += [p + ".skip.weight", p + ".skip.bias"]
-            return out + [p + ".fc.weight", p + ".fc.bias"]
-
-        def att(p):
-            norms.extend(p + s for s in (".norm.weight", ".norm.bias"))
-            return [p + s for s in (".proj_out.weight", ".proj_out.bias", ".proj_in.weight", ".proj_in.bias")]
-
-        for b in reversed(self.plan):
-            if b.kind == "midattn":
-                names += att(b.prefix)
-            elif b.att is not None:
-                names += att(b.prefix + ".1") + res(b.prefix + ".0")
-            else:
-                names += res(b.prefix)
-        names += ["in_conv.weight", "in_conv.bias"] + norms
         seen = set(names)
         names += [k for k in have if k not in seen]          # embeddings: finished last
         assert sorted(names) == sorted(have), "completion order does not cover the parameter set"
@@ -960,9 +1023,8 @@ class UNetEngine:
 
     def _backward(self, tape, dout, G, need_dx=False, join=False):
         """dout: NHWC ``[B,H,W,Cp]`` gradient of the padded output (padding channels zero)."""
-        m = self.m
         self._join_at_progress = bool(join)                    # a listener consumes gradients at every yield: finished means finished on every stream
-        B, H0, W0, cop, _ = _chk(dout)
+        B = dout.shape[0]
         self._packs = tape["packs"]                            # the images THIS forward packed (another forward may have run since)
         ta = tape["ta"]
         dta = torch.zeros_like(ta)
@@ -974,100 +1036,43 @@ class UNetEngine:
             if self._side_stream is None or self._side_stream.device != dout.device:
                 self._side_stream = torch.cuda.Stream(device=dout.device)
             self._side = self._side_stream
-        # ---- out_conv
-        C0 = m.hid_channels * m.ch_multipliers[0]
-        gn, conv = m.out_conv[0], m.out_conv[2]
-        o = tape["out"]
-        co = m.out_channels
-        P0 = B * H0 * W0
-        da = self._new(dout, B, H0, W0, C0)
-        if o["wz"] is not None:
-            wz = o["wz"]
-            nz = wz.shape[0]
-            dz = self._new(dout, P0, nz)
-            H.tap_spread(dout, cop, dz, nz, B, H0, W0, co)                   # dz[q][co*9+tap] = dout[q - off(tap)][co]
-            gz, cs = self._new(dout, nz, C0), self._new(dout, nz)
-            H.gemm(dz, o["a"], gz, nz, C0, P0, a_kind=H.COL, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0, splitk=_splitk(nz, C0, P0),
-                   colsum=cs)
-            H.thin_wgrad_finish(gz, co, C0, C0, G["out_conv.2.weight"], colsum=cs, cs_stride=9, cs_off=4, dbias=G["out_conv.2.bias"])
-            H.gemm(dz, wz, da, P0, C0, nz, a_kind=H.ROW, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0)
-            del dz
-        else:
-            H.conv3x3_wgrad(o["a"], C0, dout, cop, B, H0, W0, C0, cop, G["out_conv.2.weight"], C0, co, dbias=G["out_conv.2.bias"])
-            H.conv3x3(dout, cop, self._pack_d(conv.weight, cop), None, da, C0, B, H0, W0, cop, C0)
-        dh = self._new(dout, B, H0, W0, C0)
-        H.gn_apply_bwd(da, C0, o["h"], _ld(o["h"]), o["coef"], gn.weight, gn.bias, None, 1, 0.0, 0, H.RS_NONE, None, 0, dh, C0,
-                       False, None, None, None, False, B, H0, W0, C0, GROUPS,
-                       pgb_keep=self._pgb(B, C0, G["out_conv.0.weight"], G["out_conv.0.bias"]))
-        del da
+        dh_cur = self._out_conv_bwd(tape["out"], dout, G)      # gradient of the running `h`
         yield "out_conv.2.bias"                # (the GroupNorm parameter gradients are finished by ONE launch at the end: _pgb_finish)
-        # ---- blocks in reverse
         dskip = {}                     # hs id -> gradient view (written by the consuming up-block)
-        dh_cur = dh                    # gradient of the running `h`
-        for bi in range(len(self.plan) - 1, -1, -1):
-            b = self.plan[bi]
-            first_ctx = tape[b.prefix + ".0"] if (b.att is not None and b.kind != "midattn") else tape[b.prefix]
-            xin = first_ctx["x"]
-            Bx, ih, iw, cin, _ = _chk(xin)
-            if b.kind == "down":
-                dy = dskip.pop(b.push_hs)                       # total gradient of the tensor this block pushed
-            else:
-                dy = dh_cur
-            # where does the input gradient go?  Blocks that read the top of the skip stack (every down block and
-            # middle.0) accumulate into the slot the consuming up-block already filled; everything else gets a fresh buffer.
-            if b.kind == "down" or b.prefix == "middle.0":
-                dxbuf, acc = dskip[self._hs_feeding(bi)], True
-            else:
-                dxbuf, acc = self._new(dout, Bx, ih, iw, cin), False
-            if b.kind == "midattn":
-                self._attn_bwd(b.att, b.prefix, tape[b.prefix], dy, dxbuf, acc, G)
+        for b in reversed(self.plan):
+            dy = dskip.pop(b.push_hs) if b.kind == "down" else dh_cur       # a down block: total gradient of the tensor it pushed
+            # the input gradient of a block that read the top of the skip stack joins what the consuming up-block already wrote there
+            acc = b.in_hs is not None
+            dxbuf = dskip[b.in_hs] if acc else self._new(dout, *tape[b.res_prefix or b.att_prefix]["x"].shape)
+            if b.res is None:
+                self._attn_bwd(b, tape[b.att_prefix], dy, dxbuf, acc, G)
             elif b.att is not None:
-                dmid = self._new(dout, *tape[b.prefix + ".1"]["x"].shape)
-                self._attn_bwd(b.att, b.prefix + ".1", tape[b.prefix + ".1"], dy, dmid, False, G)
-                self._res_bwd(b, b.res, b.prefix + ".0", tape[b.prefix + ".0"], dmid, dxbuf, acc, ta, dfilms, G)
+                dmid = self._new(dout, *tape[b.att_prefix]["x"].shape)
+                self._attn_bwd(b, tape[b.att_prefix], dy, dmid, False, G)
+                self._res_bwd(b, tape[b.res_prefix], dmid, dxbuf, acc, ta, dfilms, G)
                 del dmid
             else:
-                self._res_bwd(b, b.res, b.prefix, tape[b.prefix], dy, dxbuf, acc, ta, dfilms, G)
-            # the deferred weight-gradient GEMMs of a level run when backward leaves it; only then is everything up to this
-            # block's last tensor final (gradient-bucket overlap: trainer.GradReducer.ready)
-            nxt = self.plan[bi - 1] if bi > 0 else None
-            grp = lambda q: (q.level, "mid" if q.kind.startswith("mid") else q.kind)
-            # with a gradient reducer listening and H.READY_PER_BLOCK, the queue is flushed (and the gradients declared final) after EVERY
-            # block instead of every UNet level: buckets leave as early as they can (33 report points instead of 7 for CIFAR) at the price
-            # of ungrouped 1x1 / linear weight gradients and a side-stream join per block (measured cost: DESIGN section 4)
-            if nxt is None or grp(nxt) != grp(b) or (self._join_at_progress and H.READY_PER_BLOCK):
+                self._res_bwd(b, tape[b.res_prefix], dy, dxbuf, acc, ta, dfilms, G)
+            # the deferred weight-gradient GEMMs of a level run when backward leaves it; only then is everything up to this block's last
+            # tensor final (gradient-bucket overlap: trainer.GradReducer.ready).  With a gradient reducer listening and H.READY_PER_BLOCK the
+            # queue is flushed (and the gradients declared final) after EVERY block instead: buckets leave as early as they can (28 report
+            # points instead of 7 for CIFAR) at the price of ungrouped 1x1 / linear weight gradients and a side-stream join per block
+            # (measured cost: DESIGN section 4)
+            if b.ends_group or (self._join_at_progress and H.READY_PER_BLOCK):
                 self._wgrad_flush()
                 if self._join_at_progress:
                     self._side_join()
-                yield (b.prefix + ".proj_in.bias" if b.kind == "midattn" else (b.prefix + (".0" if b.att is not None else "") + ".fc.bias"))
-            if b.kind == "up" and b.consumes:
+                yield b.report
+            if b.consumes:
                 dh_cur = dxbuf[..., :b.ch_h]
                 dskip[b.src_hs] = dxbuf[..., b.ch_h:]
             elif not acc:
                 dh_cur = dxbuf
-        # ---- in_conv
         dy0 = dskip.pop(0)
         assert not dskip
-        xc, cip = tape["in"]["xc"], tape["in"]["cip"]
-        hid = m.hid_channels
-        if xc is not None:
-            gw = self._new(dout, hid, 9 * cip)
-            H.gemm(dy0, xc, gw, hid, 9 * cip, P0, a_kind=H.COL, b_kind=H.COL, lda=_ld(dy0), ldb=9 * cip, ldc=9 * cip,
-                   splitk=_splitk(hid, 9 * cip, P0), colsum=G["in_conv.bias"])
-            H.thin_wgrad_finish(gw, hid, cip, m.in_channels, G["in_conv.weight"])
-        else:
-            H.conv3x3_wgrad(tape["in"]["x4"], cip, dy0, _ld(dy0), B, H0, W0, cip, hid, G["in_conv.weight"], m.in_channels, hid,
-                            dbias=G["in_conv.bias"])
+        self._in_conv_bwd(tape["in"], dy0, G)
         yield "in_conv.bias"
-        dx = None
-        if need_dx:
-            d4 = self._new(dout, B, H0, W0, cip)
-            if cip != m.in_channels:
-                d4.zero_()
-            H.conv3x3(dy0, _ld(dy0), self._pack_d(m.in_conv.weight, m.hid_channels), None, d4, cip, B, H0, W0, m.hid_channels,
-                      m.in_channels)
-            dx = self._new(dout, B, m.in_channels, H0, W0)
-            H.nhwc_to_nchw(d4, cip, dx, B, m.in_channels, H0, W0)
+        dx = self._in_conv_dgrad(tape["in"], dy0) if need_dx else None
         self._pgb_finish()
         self._film_bwd(dfilms, tape["film_w"], dta)
         self._embed_bwd(tape["embed"], dta, G)
@@ -1077,10 +1082,3 @@ class UNetEngine:
         self._wq = None
         yield None
         return dx
-
-    def _hs_feeding(self, bi):
-        """id of the skip-stack entry that block ``bi`` reads as its input (the stack top at that time)."""
-        b = self.plan[bi]
-        if b.kind == "down":
-            return b.push_hs - 1
-        return len(self.pushes) - 1          # middle.0 reads the last pushed tensor
