@@ -404,6 +404,37 @@ int vd_bpd_bwd(const float* x0, const float* xt, const float* out, const float* 
 int vd_sample_step(const float* xt, const float* out, const float* noise, const float* k, const float* k_dev,
                    int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip,
                    float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* progressive distillation (Salimans & Ho 2022): a student with N sampling steps regresses, in x-space, on the result of two
+ * deterministic DDIM steps of a teacher on the 2N grid, t -> t' = t - 1/(2N) -> t'' = t - 1/N.  Three launches around the two teacher
+ * forwards and the student forward.  coef[n][20] (device), per sample, computed on the host in fp64 from the fp32-rounded
+ * log-SNRs, every slot rounded once on its own:
+ *    0  1  2   a0 b0x b0e of the TEACHER at t :  x_hat  = clip?(a0*z_t  + b0x*out (+ b0e*out_eps))
+ *    3  4      c1 c2 of the DDIM step t' <- t :  z_t'   = c1*z_t + c2*x_hat
+ *    5  6  7   a0 b0x b0e of the teacher at t':  x_hat' = clip?(a0*z_t' + b0x*out (+ b0e*out_eps))
+ *    8  9      w1 w2, w1 + w2 = 1            :  x_tilde = w1*x_hat + w2*x_hat'   (w2 = c2(t''<-t')/c2(t''<-t); (0, 1) where t'' = 0)
+ *   10 11 12   a0 b0x b0e of the STUDENT at t :  x_stud = a0*z_t + b0x*out (+ b0e*out_eps)
+ *   13         omega, the loss weight of the sample       14  w_guide of the teacher
+ *   15         logsnr(t): vd_q_sample's argument, kept beside the weights made from it; no vd_distill_* kernel reads it
+ *   16 17 18   a0 - 1 of slots 0, 5, 10                   19  c1 + c2 - 1
+ * Slots 16..19 serve the residual x_stud - x_tilde, which is assembled from each prediction's difference from the state it was made
+ * from, (a0 - 1)*z + b0x*out (+ b0e*out_eps), never from the predictions themselves: at high log-SNR they all lie within 1e-3..1e-5 of
+ * z_t, where one fp32 ulp of a weight near 1 is up to 1e-3 of the residual (cf. slot 7 of vd_bpd_terms).
+ * With cfg the teacher outputs have 2n rows, cond/uncond interleaved as in vd_sample_step, and every teacher prediction is
+ * guided in x-space after the optional clip: x = x_c + w_guide (x_c - x_u).  Outputs of a "both" network have 2C channels.
+ * Any C*HW; 64-bit element offsets.  dwordx4 accesses when C*HW is a multiple of 4 and all bases are 16-byte aligned, scalar otherwise. */
+/* x_hat, d_hat = x_hat - z_t (difference form), z_t' (n rows each) and, when zdup is given (cfg only), z_t' duplicated to 2n interleaved
+ * rows = the next teacher input */
+int vd_distill_mid(const float* zt, const float* teacher_out, const float* coef, int32_t teacher_out_type, int32_t cfg, int32_t clip,
+                   float* xhat, float* dhat, float* zmid, float* zdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* teacher_out = the teacher's output at (z_t', t').  loss[n] = omega * mean_{c,h,w}((x_stud - x_tilde)^2), one workgroup per sample,
+ * fixed summation order (bitwise reproducible); resid (n, C, HW) = x_stud - x_tilde for the backward pass; xtilde optional (xhat is
+ * read only when it is asked for). */
+int vd_distill_loss_fwd(const float* xhat, const float* dhat, const float* zmid, const float* teacher_out, const float* zt,
+                        const float* student_out, const float* coef, int32_t teacher_out_type, int32_t student_out_type, int32_t cfg,
+                        int32_t clip, float* loss, float* resid, float* xtilde, int32_t n, int32_t C, int32_t HW, void* stream);
+/* dout = gloss[b] * omega_b * 2/(C*HW) * resid * b0x   (channels C..2C of a "both" student: * b0e) */
+int vd_distill_loss_bwd(const float* resid, const float* coef, const float* gloss, int32_t student_out_type, float* dout,
+                        int32_t n, int32_t C, int32_t HW, void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */

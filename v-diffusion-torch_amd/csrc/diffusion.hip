@@ -41,13 +41,14 @@ __global__ void q_sample_kernel(const float* x0, const float* eps, const float* 
     }
 }
 
-__device__ __forceinline__ float block_sum(float v, float* sh) {
+template <typename T>
+__device__ __forceinline__ T block_sum(T v, T* sh) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) sh[w] = v;
     __syncthreads();
-    float t = 0.f;
+    T t = 0;
     for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += sh[i];
     __syncthreads();
     return t;
@@ -244,6 +245,153 @@ inline int grid_for(long long total) {
     return (int)(g < 1 ? 1 : g);
 }
 
+// ---- progressive distillation (Salimans & Ho 2022): two DDIM steps of a teacher on the 2N grid become the regression target of one
+// student step on the N grid.  coef[b][20], per sample (host, fp64, rounded once; layout in include/vdiff_hip.h):
+//   0..2  teacher weights at t:   x_hat  = a0*z_t  + b0x*o (+ b0e*o_eps)         3,4  z_t' = c1*z_t + c2*x_hat
+//   5..7  teacher weights at t':  x_hat' = a0*z_t' + b0x*o (+ b0e*o_eps)         8,9  x_tilde = w1*x_hat + w2*x_hat'  (w1 + w2 = 1)
+//   10..12 student weights at t    13 omega   14 w_guide   15 logsnr(t), not read here
+//   16,17,18  a0 - 1 of the three predictions, 19  c1 + c2 - 1, each rounded on its own
+// Every prediction is formed twice: directly (what the next network pass and the caller see) and as its DIFFERENCE from the state it
+// was predicted from, (a0 - 1)*z + b0x*o (+ b0e*o_eps).  The residual x_student - x_tilde is assembled from the differences alone:
+// at high log-SNR all predictions sit within 1e-3 ... 1e-5 of z_t, and through the direct forms one fp32 ulp of a weight near 1 is
+// up to 1e-3 of the residual (the a0 - 1 slot of the bound-term kernels, for the same reason).
+// V = floats per lane and access: 4 (dwordx4) when C*HW is a multiple of 4 and every base is 16-byte aligned -- a vector then never
+// straddles two samples or the two halves of a "both" output -- else 1.
+enum { DK = 20 };
+
+template <int V> __device__ __forceinline__ void ldv(const float* p, float (&r)[V]) {
+    if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
+    else r[0] = *p;
+}
+
+template <int V> __device__ __forceinline__ void stv(float* p, const float (&r)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else *p = r[0];
+}
+
+// guided x0 prediction x of elements [i, i + V) of sample b, and d = x - z in difference form, from a network output of n*(1+cfg)
+// rows (cond, uncond interleaved): the arithmetic of sample_step_kernel's last step -- clip each prediction, then x_c + w (x_c - x_u)
+template <int V>
+__device__ __forceinline__ void guided_x0(const float* out, long long b, long long N, long long i, int type, int cfg, int clip, float a0,
+                                          float a0m1, float b0x, float b0e, float w, const float (&z)[V], float (&x)[V], float (&d)[V]) {
+    const int mul = 1 + cfg, Co = type == OUT_BOTH ? 2 : 1;
+    float pr[2][V], df[2][V];
+    for (int u = 0; u < mul; ++u) {
+        const float* ob = out + (b * mul + u) * Co * N + i;
+        float o[V], oe[V];
+        ldv<V>(ob, o);
+        if (type == OUT_BOTH) ldv<V>(ob + N, oe);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float e = type == OUT_BOTH ? b0e * oe[j] : 0.f;
+            float x0h = a0 * z[j] + b0x * o[j] + e;
+            float dx = a0m1 * z[j] + b0x * o[j] + e;
+            if (clip && (x0h < -1.f || x0h > 1.f)) { x0h = fminf(fmaxf(x0h, -1.f), 1.f); dx = x0h - z[j]; }
+            pr[u][j] = x0h; df[u][j] = dx;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < V; ++j) {
+        x[j] = cfg ? pr[0][j] + w * (pr[0][j] - pr[1][j]) : pr[0][j];
+        d[j] = cfg ? df[0][j] + w * (df[0][j] - df[1][j]) : df[0][j];
+    }
+}
+
+struct DistillMidArgs {
+    const float* zt; const float* out; const float* coef; int type, cfg, clip; float* xhat; float* dhat; float* zmid; float* zdup;
+    int n; long long N;
+};
+
+// teacher prediction at t (x_hat, and d_hat = x_hat - z_t) and the DDIM step to t' = t - 1/(2N); zdup (optional) = z_t' on 2n interleaved
+// rows, the next guided teacher input
+template <int V>
+__global__ void distill_mid_kernel(const DistillMidArgs p) {
+    const long long N = p.N, total = (long long)p.n * N / V;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        const float* k = p.coef + DK * b;
+        float z[V], x[V], d[V], zm[V];
+        ldv<V>(p.zt + e, z);
+        guided_x0<V>(p.out, b, N, i, p.type, p.cfg, p.clip, k[0], k[16], k[1], k[2], k[14], z, x, d);
+        const float c1 = k[3], c2 = k[4];
+#pragma unroll
+        for (int j = 0; j < V; ++j) zm[j] = c1 * z[j] + c2 * x[j];
+        stv<V>(p.xhat + e, x);
+        stv<V>(p.dhat + e, d);
+        stv<V>(p.zmid + e, zm);
+        if (p.zdup) { stv<V>(p.zdup + 2 * b * N + i, zm); stv<V>(p.zdup + (2 * b + 1) * N + i, zm); }
+    }
+}
+
+struct DistillLossArgs {
+    const float* xhat; const float* dhat; const float* zmid; const float* tout; const float* zt; const float* sout; const float* coef;
+    int ttype, stype, cfg, clip; int n; long long N;
+};
+
+// one workgroup per sample, fixed summation order: loss[b] = omega * mean(resid^2), resid = x_student - x_tilde from the differences:
+//   z_t' - z_t = (c1 + c2 - 1) z_t + c2 d_hat,  x_hat' - z_t = d_hat' + (z_t' - z_t),  x_tilde - z_t = w1 d_hat + w2 (x_hat' - z_t)
+template <int V>
+__global__ __launch_bounds__(256) void distill_loss_fwd_kernel(const DistillLossArgs p, float* loss, float* resid, float* xtilde) {
+    __shared__ double sh[8];
+    const long long b = blockIdx.x, N = p.N;
+    const float* k = p.coef + DK * b;
+    const float c2 = k[4], w1 = k[8], w2 = k[9], sa0m1 = k[18], sb0x = k[11], sb0e = k[12], c12m1 = k[19];
+    const float* sb = p.sout + b * (p.stype == OUT_BOTH ? 2 : 1) * N;
+    double acc = 0.0;                 // squares summed in fp64 (free under the loads): the loss carries the residuals' error, not the sum's
+    for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)blockDim.x * V) {
+        float z[V], zm[V], dh[V], xp[V], dp[V], so[V], soe[V], r[V];
+        ldv<V>(p.zt + b * N + i, z);
+        ldv<V>(p.zmid + b * N + i, zm);
+        ldv<V>(p.dhat + b * N + i, dh);
+        guided_x0<V>(p.tout, b, N, i, p.ttype, p.cfg, p.clip, k[5], k[17], k[6], k[7], k[14], zm, xp, dp);
+        ldv<V>(sb + i, so);
+        if (p.stype == OUT_BOTH) ldv<V>(sb + N + i, soe);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float dz = c12m1 * z[j] + c2 * dh[j];
+            const float dt = w1 * dh[j] + w2 * (dp[j] + dz);
+            const float ds = sa0m1 * z[j] + sb0x * so[j] + (p.stype == OUT_BOTH ? sb0e * soe[j] : 0.f);
+            r[j] = ds - dt;
+            acc += (double)r[j] * (double)r[j];
+        }
+        stv<V>(resid + b * N + i, r);
+        if (xtilde) {                                  // the target itself, in the direct (convex) form
+            float xh[V], xt[V];
+            ldv<V>(p.xhat + b * N + i, xh);
+#pragma unroll
+            for (int j = 0; j < V; ++j) xt[j] = w1 * xh[j] + w2 * xp[j];
+            stv<V>(xtilde + b * N + i, xt);
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (threadIdx.x == 0) loss[b] = (float)((double)k[13] * (acc / (double)N));
+}
+
+// dout = gloss[b] * omega_b * 2/N * resid * b0x (second half of a "both" student: * b0e)
+template <int V>
+__global__ void distill_loss_bwd_kernel(const float* resid, const float* coef, const float* gloss, int stype, float* dout, int n,
+                                        long long N) {
+    const long long total = (long long)n * N / V;
+    const int Co = stype == OUT_BOTH ? 2 : 1;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        const float* k = coef + DK * b;
+        const float g = gloss[b] * k[13] * 2.f / (float)N, bx = k[11], be = k[12];
+        float r[V], d[V];
+        ldv<V>(resid + e, r);
+#pragma unroll
+        for (int j = 0; j < V; ++j) d[j] = g * r[j] * bx;
+        stv<V>(dout + b * Co * N + i, d);
+        if (stype == OUT_BOTH) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) d[j] = g * r[j] * be;
+            stv<V>(dout + b * Co * N + N + i, d);
+        }
+    }
+}
+
+template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
+
 }  // namespace
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
@@ -309,5 +457,56 @@ extern "C" int vd_bpd_bwd(const float* x0, const float* xt, const float* out, co
     hipLaunchKernelGGL(bpd_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, use_kl, gloss,
                        dout);
     VD_LAUNCH_CHECK("bpd_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_distill_mid(const float* zt, const float* out, const float* coef, int32_t teacher_type, int32_t cfg, int32_t clip,
+                              float* xhat, float* dhat, float* zmid, float* zdup, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3, "vd_distill_mid: bad model_out_type %d", teacher_type);
+    VD_REQUIRE(zt && out && coef && xhat && dhat && zmid, "vd_distill_mid: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_mid: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_REQUIRE(!zdup || cfg, "vd_distill_mid: the duplicated state is the guided teacher's input (cfg = 1)");
+    const long long N = (long long)C * HW;
+    DistillMidArgs p = {zt, out, coef, teacher_type, cfg ? 1 : 0, clip ? 1 : 0, xhat, dhat, zmid, zdup, n, N};
+    if (N % 4 == 0 && all_aligned16(zt, out, xhat, dhat, zmid, zdup))
+        hipLaunchKernelGGL(distill_mid_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(distill_mid_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("distill_mid_kernel");
+    return 0;
+}
+
+extern "C" int vd_distill_loss_fwd(const float* xhat, const float* dhat, const float* zmid, const float* teacher_out, const float* zt,
+                                   const float* student_out, const float* coef, int32_t teacher_type, int32_t student_type, int32_t cfg,
+                                   int32_t clip, float* loss, float* resid, float* xtilde, int32_t n, int32_t C, int32_t HW,
+                                   void* stream) {
+    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3 && student_type >= 0 && student_type <= 3,
+               "vd_distill_loss_fwd: bad model_out_type (%d,%d)", teacher_type, student_type);
+    VD_REQUIRE(dhat && zmid && teacher_out && zt && student_out && coef && loss && resid && (xhat || !xtilde),
+               "vd_distill_loss_fwd: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_fwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    DistillLossArgs p = {xhat, dhat, zmid, teacher_out, zt, student_out, coef, teacher_type, student_type, cfg ? 1 : 0, clip ? 1 : 0, n, N};
+    if (N % 4 == 0 && all_aligned16(xhat, dhat, zmid, teacher_out, zt, student_out, resid, xtilde))
+        hipLaunchKernelGGL(distill_loss_fwd_kernel<4>, dim3(n), dim3(256), 0, (hipStream_t)stream, p, loss, resid, xtilde);
+    else
+        hipLaunchKernelGGL(distill_loss_fwd_kernel<1>, dim3(n), dim3(256), 0, (hipStream_t)stream, p, loss, resid, xtilde);
+    VD_LAUNCH_CHECK("distill_loss_fwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const float* gloss, int32_t student_type, float* dout,
+                                   int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(student_type >= 0 && student_type <= 3, "vd_distill_loss_bwd: bad model_out_type %d", student_type);
+    VD_REQUIRE(resid && coef && gloss && dout, "vd_distill_loss_bwd: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_bwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    if (N % 4 == 0 && all_aligned16(resid, dout))
+        hipLaunchKernelGGL(distill_loss_bwd_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, resid, coef, gloss,
+                           student_type, dout, n, N);
+    else
+        hipLaunchKernelGGL(distill_loss_bwd_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, resid, coef, gloss,
+                           student_type, dout, n, N);
+    VD_LAUNCH_CHECK("distill_loss_bwd_kernel");
     return 0;
 }

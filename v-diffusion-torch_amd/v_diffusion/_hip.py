@@ -119,6 +119,9 @@ _SIGNATURES = {
     "vd_bpd_terms": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_bpd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vd_sample_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_distill_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -788,6 +791,20 @@ def sample_step(xt, out, noise, k8, mot, cfg, last, clip, xn, xdup, n, Cc, HW, k
     arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
     _check(lib().vd_sample_step(ptr(xt), ptr(out), ptr(noise), arr, ptr(k_dev), mot, int(cfg), int(last), int(clip), ptr(xn),
                                 ptr(xdup), n, Cc, HW, stream()), "vd_sample_step")
+
+
+def distill_mid(zt, tout, coef, tmot, cfg, clip, xhat, dhat, zmid, zdup, n, Cc, HW):
+    _check(lib().vd_distill_mid(ptr(zt), ptr(tout), ptr(coef), tmot, int(cfg), int(clip), ptr(xhat), ptr(dhat), ptr(zmid), ptr(zdup),
+                                n, Cc, HW, stream()), "vd_distill_mid")
+
+
+def distill_loss_fwd(xhat, dhat, zmid, tout, zt, sout, coef, tmot, smot, cfg, clip, loss, resid, xtilde, n, Cc, HW):
+    _check(lib().vd_distill_loss_fwd(ptr(xhat), ptr(dhat), ptr(zmid), ptr(tout), ptr(zt), ptr(sout), ptr(coef), tmot, smot, int(cfg), int(clip),
+                                     ptr(loss), ptr(resid), ptr(xtilde), n, Cc, HW, stream()), "vd_distill_loss_fwd")
+
+
+def distill_loss_bwd(resid, coef, gloss, smot, dout, n, Cc, HW):
+    _check(lib().vd_distill_loss_bwd(ptr(resid), ptr(coef), ptr(gloss), smot, ptr(dout), n, Cc, HW, stream()), "vd_distill_loss_bwd")
 
 
 def sumsq(g, out1):

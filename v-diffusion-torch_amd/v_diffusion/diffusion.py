@@ -229,6 +229,23 @@ def _both_coefs(l32):
     return s1.sqrt(), s0, -(s1 * s0).sqrt()
 
 
+def _pred_coefs64(model_out_type, l32):
+    """(a0, b0x, b0e) of ``_pred_coefs`` for a (B,) vector of fp32 log-SNRs, as fp64 tensors: the closed forms evaluated in fp64, for
+    the per-sample coefficient tables (the caller rounds once)."""
+    l = l32.double()
+    s1, s0 = torch.sigmoid(l), torch.sigmoid(-l)
+    z = torch.zeros_like(l)
+    if model_out_type == "v":
+        return s1.sqrt(), -s0.sqrt(), z
+    if model_out_type == "x0":
+        return z, torch.ones_like(l), z
+    if model_out_type == "eps":
+        return s1.rsqrt(), -torch.exp(-0.5 * l), z
+    if model_out_type == "both":
+        return _both_coefs(l32)
+    raise NotImplementedError(model_out_type)
+
+
 def _device_ctx(device):
     """make ``device`` the current HIP device for the duration of a sampler call (kernels use its current stream)"""
     device = torch.device(device)
@@ -456,19 +473,7 @@ class GaussianDiffusion:
         # prediction weights in fp64 from the fp32 log-SNR, rounded once; slot 7 carries a0 - 1, rounded on its own: the squared error
         # of x0_hat is taken from (a0 - 1)*x_t + (x_t - x_0) + ..., which stays well conditioned where x0_hat - x_0 is 1e-3 ... 1e-5
         # of x_0 (logsnr >= 12.9) -- through a0 itself one fp32 ulp of the weight is up to 1e-3 of that difference
-        l = lt.double()
-        s1, s0 = torch.sigmoid(l), torch.sigmoid(-l)
-        z = torch.zeros_like(l)
-        if self.model_out_type == "v":
-            a0, b0x, b0e = s1.sqrt(), -s0.sqrt(), z
-        elif self.model_out_type == "x0":
-            a0, b0x, b0e = z, torch.ones_like(l), z
-        elif self.model_out_type == "eps":
-            a0, b0x, b0e = s1.rsqrt(), -torch.exp(-0.5 * l), z
-        elif self.model_out_type == "both":
-            a0, b0x, b0e = _both_coefs(lt)
-        else:
-            raise NotImplementedError(self.model_out_type)
+        a0, b0x, b0e = _pred_coefs64(self.model_out_type, lt)
         return torch.stack([a0.float(), b0x.float(), b0e.float(), c1, c2, tlv, mlv, (a0 - 1.0).float()], dim=1).contiguous()
 
     def _loss_term_bpd(self, model_out, x_0, x_t, logsnr_s, logsnr_t, clip_denoised, return_pred=False):

@@ -277,6 +277,19 @@ class UNet(nn.Module):
         self._grads_ready_hook = None
         self._tokens = {}
 
+    def detached_copy(self):
+        """A deep copy that shares nothing with this module: every parameter in a compact storage of its own (``Parameter.__deepcopy__``
+        clones the data, so a view of a flat store becomes a tensor of the parameter's size, not a copy of the store), and none of this
+        module's run state -- engine, gradient slots, tokens are built again on first use.  That run state is taken off ``self`` for the
+        duration of the copy and put back: not to be called while a forward or backward of this module is in flight."""
+        import copy
+        keep = {k: self.__dict__[k] for k in ("_engine", "_flat_grad_views", "_grad_pool", "_grads_ready_hook", "_tokens")}
+        self._engine, self._flat_grad_views, self._grad_pool, self._grads_ready_hook, self._tokens = None, None, {}, None, {}
+        try:
+            return copy.deepcopy(self)
+        finally:
+            self.__dict__.update(keep)
+
     # ------------------------------------------------------------------ engine plumbing
     def engine(self):
         if self._engine is None:
