@@ -435,6 +435,25 @@ int vd_distill_loss_fwd(const float* xhat, const float* dhat, const float* zmid,
 /* dout = gloss[b] * omega_b * 2/(C*HW) * resid * b0x   (channels C..2C of a "both" student: * b0e) */
 int vd_distill_loss_bwd(const float* resid, const float* coef, const float* gloss, int32_t student_out_type, float* dout,
                         int32_t n, int32_t C, int32_t HW, void* stream);
+/* one reverse step of DPM-Solver++(2M) (Lu et al. 2022, data-prediction form): the second-order multistep solver of the
+ * probability-flow ODE in log-SNR time, for a batch that shares the step.  xt, hist, xn: n images (NCHW); out: n*(1+cfg) images,
+ * cond/uncond interleaved when cfg, 2C channels for a "both" network; xdup (optional, cfg only): 2n images.
+ * k: 8 floats {a0, b0x, b0e, c1, c2, c2rho, w_guide, 0}, host (k) or device (k_dev), exactly one of the two as in vd_sample_step.
+ * c1 = sigma_s/sigma_t and c2 = alpha_s (1 - e^-h) are the DDIM weights of the step t -> s, h = (logsnr_s - logsnr_t)/2, and
+ * c2rho = c2 * h/(2 h_prev) is a slot of its own (rounded once from fp64, not fl(c2)*fl(rho)).  Evaluation order, all in fp32,
+ * per element:
+ *   x_c  = clip?(a0*xt + b0x*out_c (+ b0e*out_c,eps))     and x_u likewise from the odd rows when cfg (clip per branch, then guide)
+ *   g    = cfg ? x_c + w_guide*(x_c - x_u) : x_c
+ *   xn   = c1*xt + c2*g + c2rho*(g - hist)
+ *   hist = g                                              (read, then overwritten in place: the next step's previous prediction)
+ *   xdup = xn on rows 2b and 2b+1                         (the next guided network input)
+ * There is no first- or last-step flag: c2rho = 0 makes the step DDIM (the first step of a chain, whose hist the host zero-fills, and
+ * every step of order 1), and the row (c1, c2, c2rho) = (0, 1, 0) returns g, the guided x0 prediction every sampler here ends on.
+ * xn may alias xt; hist is a buffer of its own.  Any C*HW; 64-bit element offsets; dwordx4 accesses when C*HW is a multiple of 4
+ * and all bases are 16-byte aligned, scalar otherwise. */
+int vd_solver_step(const float* xt, const float* out, float* hist, const float* k, const float* k_dev,
+                   int32_t model_out_type, int32_t cfg, int32_t clip,
+                   float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */

@@ -3,6 +3,7 @@
 //   train_loss (mse) forward/backward  diffusion.py:466-490,520-541 ; flat_mean functions.py:102-104
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
+//   progressive distillation and the DPM-Solver++(2M) reverse step: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 #include "common.h"
 
@@ -392,6 +393,54 @@ __global__ void distill_loss_bwd_kernel(const float* resid, const float* coef, c
 
 template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
 
+// ---- DPM-Solver++(2M) (Lu et al. 2022, data-prediction form): one reverse step of the probability-flow ODE in log-SNR time from the
+// guided x0 prediction g of this step and the one of the step before (hist).  k[8] = {a0, b0x, b0e, c1, c2, c2*rho, w_guide, 0} with
+// c1, c2 the DDIM weights of the step and rho = h / (2 h_prev); c2*rho = 0 gives the DDIM step, (c1, c2, c2*rho) = (0, 1, 0) the
+// guided x0 prediction itself (the last row of a chain).  Evaluation order, every operation in fp32:
+//   x_u = a0*xt + b0x*o (+ b0e*o_eps), clipped when asked, per branch;   g = x_c + w*(x_c - x_u)  (g = x_c without cfg)
+//   xn  = c1*xt + c2*g + c2rho*(g - hist);   hist <- g;   xdup rows 2b, 2b+1 <- xn
+// Each thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
+struct SolverArgs {
+    const float* xt; const float* out; float* hist; float k[8]; const float* kdev;
+    int type, cfg, clip; float* xn; float* xdup; int n; long long N;
+};
+
+template <int V>
+__global__ void solver_step_kernel(const SolverArgs p) {
+    const long long N = p.N, total = (long long)p.n * N / V;
+    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
+    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], c2r = kp[5], w = kp[6];
+    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float z[V], h[V], pr[2][V], g[V], xn[V];
+        ldv<V>(p.xt + e, z);
+        ldv<V>(p.hist + e, h);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
+            if (u >= mul) break;
+            const float* ob = p.out + (b * mul + u) * Co * N + i;
+            float o[V], oe[V];
+            ldv<V>(ob, o);
+            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float x0h = a0 * z[j] + b0x * o[j] + (p.type == OUT_BOTH ? b0e * oe[j] : 0.f);
+                if (p.clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
+                pr[u][j] = x0h;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            g[j] = p.cfg ? pr[0][j] + w * (pr[0][j] - pr[1][j]) : pr[0][j];
+            xn[j] = c1 * z[j] + c2 * g[j] + c2r * (g[j] - h[j]);
+        }
+        stv<V>(p.hist + e, g);
+        stv<V>(p.xn + e, xn);
+        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+    }
+}
+
 }  // namespace
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
@@ -508,5 +557,26 @@ extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const 
         hipLaunchKernelGGL(distill_loss_bwd_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, resid, coef, gloss,
                            student_type, dout, n, N);
     VD_LAUNCH_CHECK("distill_loss_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_solver_step(const float* xt, const float* out, float* hist, const float* k, const float* k_dev, int32_t type,
+                              int32_t cfg, int32_t clip, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_solver_step: pass the coefficients either as host k or as device k_dev");
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_solver_step: bad model_out_type %d", type);
+    VD_REQUIRE(xt && out && hist && xn, "vd_solver_step: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_solver_step: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_REQUIRE(!xdup || cfg, "vd_solver_step: the duplicated state is the guided network's input (cfg = 1)");
+    VD_REQUIRE(hist != xt && hist != xn, "vd_solver_step: hist is a buffer of its own");
+    const long long N = (long long)C * HW;
+    SolverArgs p = {};
+    p.xt = xt; p.out = out; p.hist = hist; p.kdev = k_dev;
+    for (int i = 0; i < 8; ++i) p.k[i] = k ? k[i] : 0.f;
+    p.type = type; p.cfg = cfg ? 1 : 0; p.clip = clip ? 1 : 0; p.xn = xn; p.xdup = xdup; p.n = n; p.N = N;
+    if (N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup))
+        hipLaunchKernelGGL(solver_step_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(solver_step_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("solver_step_kernel");
     return 0;
 }

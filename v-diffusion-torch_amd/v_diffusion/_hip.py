@@ -122,6 +122,7 @@ _SIGNATURES = {
     "vd_distill_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -805,6 +806,13 @@ def distill_loss_fwd(xhat, dhat, zmid, tout, zt, sout, coef, tmot, smot, cfg, cl
 
 def distill_loss_bwd(resid, coef, gloss, smot, dout, n, Cc, HW):
     _check(lib().vd_distill_loss_bwd(ptr(resid), ptr(coef), ptr(gloss), smot, ptr(dout), n, Cc, HW, stream()), "vd_distill_loss_bwd")
+
+
+def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=None):
+    """k8: 8 host floats, or None with k_dev = device tensor of 8 floats (graph-replayable form)"""
+    arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
+    _check(lib().vd_solver_step(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
+                                n, Cc, HW, stream()), "vd_solver_step")
 
 
 def sumsq(g, out1):

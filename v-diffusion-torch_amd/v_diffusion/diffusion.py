@@ -793,6 +793,17 @@ class GaussianDiffusion:
         return x.cpu()
 
     @torch.inference_mode()
+    def p_sample_solver(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=2, spacing="time",
+                        clip_denoised=True, use_graph=False):
+        """Deterministic reverse chain with the DPM-Solver++(2M) multistep solver (extension, v_diffusion/solver.py): ``order=2`` adds
+        to every DDIM step a correction from the previous step's x0 prediction -- same network calls, second-order error in the log-SNR
+        step -- and ``order=1`` is DDIM.  ``steps=None`` = ``sample_timesteps``; ``spacing`` = "time" (tau_i = i/steps) or "logsnr"
+        (uniform log-SNR steps).  Only x_T is drawn: the first draw of the seeded generator, the x_T ``p_sample`` starts from.
+        ``use_graph=True`` replays one captured HIP graph per step.  Returns a CPU tensor."""
+        from .solver import p_sample_solver
+        return p_sample_solver(self, denoise_fn, shape, noise, label, device, seed, steps, order, spacing, clip_denoised, use_graph).cpu()
+
+    @torch.inference_mode()
     def p_sample_uint8_async(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, use_ddim=False,
                              use_graph=None):
         """The sampler plumbing of reference generate.py:143-150 without its host round trips: the chain

@@ -1,0 +1,214 @@
+"""DPM-Solver++(2M) (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models", data-prediction
+form): a second-order multistep solver of the probability-flow ODE in log-SNR time.  It needs no training and runs any checkpoint the
+DDIM sampler runs, with the same one network evaluation per step.
+
+With lambda = logsnr/2 and, for the step t -> s, h = lambda_s - lambda_t > 0, the DDIM weights of ``logsnr_to_posterior_ddim(eta=0)`` are
+c1 = sigma_s/sigma_t and c2 = alpha_s (1 - e^-h), and
+
+    order 1 (DDIM):  x_s = c1 x_t + c2 x_hat_t
+    order 2 (2M):    x_s = c1 x_t + c2 [x_hat_t + rho (x_hat_t - x_hat_prev)],   rho = h / (2 h_prev)
+
+x_hat_prev is the (guided) x0 prediction of the step before: one more image of state, no further network call.
+
+What runs where: the weights are fp64 host arithmetic on the fp32-rounded log-SNRs, each slot rounded once into a (steps, 8) table
+(``solver_coefs``); everything per element is one fused launch per step (vd_solver_step in csrc/diffusion.hip).  The first step of a
+chain has no previous prediction: its row carries c2 rho = 0 and the sampler zero-fills the history image, so one kernel -- and one
+captured graph -- serves every step.  The last row is (c1, c2, c2 rho) = (0, 1, 0): the chain ends on the guided x0 prediction, as every
+sampler of this package does.  MI355X only: CPU tensors raise.
+"""
+import contextlib
+from collections import OrderedDict
+
+import torch
+import torch.nn.functional as F
+
+from . import _hip
+from .diffusion import F64, _device_ctx, _pred_coefs, logsnr_to_posterior_ddim, stable_log1mexp
+
+# columns of the coefficient table (include/vdiff_hip.h, vd_solver_step)
+K = 8
+A0, B0X, B0E, C1, C2, C2RHO, W_GUIDE, _PAD = range(K)
+
+BISECTIONS = 64            # halvings of [0, 1]: the bracket is at the fp64 resolution of tau long before the last one
+PROBES = 1025              # uniform probe times of the monotonicity check
+GRAPH_CACHE_MAX = 4
+
+
+def _grid(logsnr_fn, steps, spacing):
+    """the steps + 1 grid times tau_0 = 0 < ... < tau_steps = 1 as python floats"""
+    if spacing == "time":
+        return [i / steps for i in range(steps + 1)]               # the grid (and the division) of ``_step_coefs``
+    if spacing != "logsnr":
+        raise ValueError(f"spacing must be 'time' or 'logsnr', got {spacing!r}")
+    f = lambda t: logsnr_fn(t.clone()).to(F64)                     # a rescaling schedule rewrites its argument: probe on clones
+    probe = f(torch.linspace(0.0, 1.0, PROBES, dtype=F64))
+    if not bool((probe[1:] < probe[:-1]).all()):
+        raise ValueError("spacing='logsnr' needs a strictly decreasing logsnr_fn on [0, 1]")
+    ends = f(torch.tensor([0.0, 1.0], dtype=F64))
+    frac = torch.arange(1, steps, dtype=F64) / steps
+    want = ends[0] + (ends[1] - ends[0]) * frac                    # logsnr(tau_i), linear in i
+    lo, hi = torch.zeros_like(want), torch.ones_like(want)
+    for _ in range(BISECTIONS):
+        mid = 0.5 * (lo + hi)
+        right = f(mid) > want                                      # decreasing: the root lies to the right of mid
+        lo, hi = torch.where(right, mid, lo), torch.where(right, hi, mid)
+    tau = [0.0] + (0.5 * (lo + hi)).tolist() + [1.0]
+    if steps > 1:
+        at = f(torch.tensor(tau, dtype=F64))
+        if not (all(a < b for a, b in zip(tau, tau[1:])) and bool((at[1:] < at[:-1]).all())):
+            raise ValueError("spacing='logsnr' needs a strictly decreasing logsnr_fn on [0, 1]")
+    return tau
+
+
+def _check(steps, order):
+    if steps < 1:
+        raise ValueError(f"steps must be >= 1, got {steps}")
+    if order not in (1, 2):
+        raise ValueError(f"order must be 1 (DDIM) or 2 (DPM-Solver++ 2M), got {order!r}")
+
+
+def _rows(logsnr_fn, tau, order, model_out_type, w_guide):
+    """the table rows in the order a chain executes them, i = steps - 1 ... 0: ((8,) fp32 row, network time) one at a time, so that a
+    sampler builds row i on the host while the GPU is busy with step i + 1 (a whole table up front is ~0.2 ms of host time per row
+    in front of the first launch)"""
+    steps = len(tau) - 1
+    h_prev = None
+    for i in reversed(range(steps)):
+        st = torch.tensor([tau[i], tau[i + 1]], dtype=F64)
+        l = logsnr_fn(st)                                          # may rewrite st in place
+        t_net = float(st[1])
+        ls32, lt32 = l[0:1].float(), l[1:2].float()
+        c1, c2, _ = logsnr_to_posterior_ddim(ls32, lt32, eta=0.)
+        a0, b0x, b0e = _pred_coefs(model_out_type, lt32[0])
+        ls, lt = ls32.double(), lt32.double()
+        h = 0.5 * float(ls - lt)
+        row = [a0, b0x, b0e, float(c1), float(c2), 0.0, float(w_guide), 0.0]
+        if i == 0:
+            row[C1], row[C2] = 0.0, 1.0
+        elif order == 2 and h_prev is not None:
+            # c2 before its rounding (the expression of logsnr_to_posterior_ddim) times rho, rounded once below
+            row[C2RHO] = float(torch.exp(stable_log1mexp(0.5 * (lt - ls)) + 0.5 * F.logsigmoid(ls))) * (h / (2.0 * h_prev))
+        h_prev = h
+        yield torch.tensor(row, dtype=F64).to(torch.float32), t_net
+
+
+def solver_coefs(logsnr_fn, steps, order=2, spacing="time", model_out_type="v", w_guide=0.):
+    """``(table, t_net)``: the (steps, 8) fp32 table of vd_solver_step, row i = the step tau_{i+1} -> tau_i with the columns named
+    above, and the (steps,) fp64 times the network is called with, tau_{i+1} as ``logsnr_fn`` left it (a rescaling schedule rewrites its
+    argument; the rule of ``GaussianDiffusion._step_coefs``).  Pure torch on the CPU.
+
+    ``spacing="time"``: tau_i = i/steps, the grid of every sampler here.  ``spacing="logsnr"``: logsnr(tau_i) linear in i between
+    logsnr(0) and logsnr(1) (uniform steps h: the grid the solver's error analysis assumes), tau_i by fp64 bisection, ends exactly 0, 1.
+
+    The arithmetic is ``_step_coefs``'s: per row ``logsnr_fn`` sees the pair (tau_i, tau_{i+1}), the log-SNRs are rounded to fp32 (the image
+    dtype), a0, b0x, b0e come from ``_pred_coefs`` and c1, c2 from ``logsnr_to_posterior_ddim(eta=0)`` -- order 1 is bit for bit the DDIM
+    sampler's numbers.  h_i = (l_s - l_t)/2 and rho_i = h_i/(2 h_{i+1}) are fp64 from those fp32 values; c2 rho is the fp64 product
+    rounded once.  rho = 0 on the first executed row (i = steps - 1), on every row of order 1, and on row 0, which is (0, 1, 0)."""
+    steps = int(steps)
+    _check(steps, order)
+    rows = list(_rows(logsnr_fn, _grid(logsnr_fn, steps, spacing), order, model_out_type, w_guide))[::-1]
+    return torch.stack([r for r, _ in rows]).contiguous(), torch.tensor([t for _, t in rows], dtype=F64)
+
+
+def _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device):
+    """(graph, state, pinned packs) of one reverse step -- network forward + vd_solver_step on device-resident coefficients -- from
+    this object's own small LRU cache"""
+    B, C = shape[0], shape[1]
+    HW = int(shape[2]) * int(shape[3])
+    mot = _hip.OUT_TYPES[gd.model_out_type]
+    key = ("solver", id(denoise_fn), tuple(shape), bool(cfg), bool(clip), gd.model_out_type, None if y_in is None else tuple(y_in.shape),
+           hash(tuple(p.data_ptr() for p in net.parameters())) if isinstance(net, torch.nn.Module) else None)
+    cache = gd.__dict__.setdefault("_solver_graphs", OrderedDict())
+    entry = cache.get(key)
+    if entry is not None:
+        cache.move_to_end(key)
+        return entry
+    rows = B * (1 + cfg)
+    st = dict(x=torch.zeros(shape, dtype=torch.float32, device=device),
+              hist=torch.zeros(shape, dtype=torch.float32, device=device),
+              t=torch.zeros((rows,), dtype=F64, device=device),
+              k=torch.zeros((K,), dtype=torch.float32, device=device),
+              y=None if y_in is None else torch.zeros_like(y_in))
+    st["xin"] = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=device) if cfg else st["x"]
+
+    def body():
+        out = denoise_fn(st["xin"], st["t"], st["y"]).to(torch.float32).contiguous()
+        _hip.solver_step(st["x"], out, st["hist"], None, mot, cfg, clip, st["x"], st["xin"] if cfg else None, B, C, HW, k_dev=st["k"])
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):                  # warm-up outside capture (lazy initialisation, workspace growth)
+        body()
+    torch.cuda.current_stream(device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    # the graph's pack / convolution nodes hold raw pointers into the forward's ConvPacks: the entry keeps that object alive
+    eng = net.engine() if hasattr(net, "engine") else None
+    while len(cache) >= GRAPH_CACHE_MAX:
+        cache.popitem(last=False)
+    entry = cache[key] = (graph, st, None if eng is None else eng.packs)
+    return entry
+
+
+def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=2, spacing="time",
+                    clip_denoised=True, use_graph=False):
+    """the reverse chain of ``GaussianDiffusion.p_sample_solver`` (see there); returns the final image batch on the device"""
+    steps = gd.sample_timesteps if steps is None else int(steps)
+    _check(steps, order)
+    if gd.model_var_type == "learned":
+        raise NotImplementedError("model_var_type='learned'")
+    if gd.x0eps_coef:
+        raise NotImplementedError("x0eps_coef=True with the multistep solver")
+    device = torch.device(gd._default_device(denoise_fn) if device is None else device)
+    shape = tuple(shape)
+    with _device_ctx(device):
+        generator = None if seed is None else torch.Generator(device).manual_seed(seed)
+        if noise is None:
+            x_t = torch.randn(shape, device=device, generator=generator)      # the only draw: p_sample's x_T for this seed
+        else:
+            x_t = noise.to(device=device, dtype=torch.float32).contiguous().clone()
+        if label is not None:
+            label = label.to(device)
+        cfg = gd._use_cfg(label)
+        if cfg:
+            y_in = label.repeat_interleave(2, dim=0).clone()
+            y_in[1::2] = 0                                                     # unconditional rows, as _sample_loop builds them
+        else:
+            y_in = label
+        B, C = shape[0], shape[1]
+        HW = int(shape[2]) * int(shape[3])
+        rows = B * (1 + cfg)
+        net = getattr(denoise_fn, "module", denoise_fn)
+        if use_graph:
+            graph, st, _ = _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, bool(clip_denoised), device)
+            st["x"].copy_(x_t)
+            st["hist"].zero_()
+            if cfg:
+                st["xin"].copy_(x_t.repeat_interleave(2, dim=0))
+            if y_in is not None:
+                st["y"].copy_(y_in)
+            table, t_net = solver_coefs(gd.logsnr_fn, steps, order, spacing, gd.model_out_type, gd.w_guide)
+            ktab, t_net = table.to(device), t_net.tolist()
+            for i in reversed(range(steps)):
+                st["t"].fill_(t_net[i])
+                st["k"].copy_(ktab[i])
+                graph.replay()
+            return st["x"].clone()
+        mot = _hip.OUT_TYPES[gd.model_out_type]
+        hist = torch.zeros_like(x_t)
+        x_next = torch.empty_like(x_t)
+        x_in = x_t.repeat_interleave(2, dim=0) if cfg else x_t
+        x_in_next = torch.empty_like(x_in) if cfg else None
+        tau = _grid(gd.logsnr_fn, steps, spacing)
+        eng = net.engine() if hasattr(net, "engine") else None
+        with (eng.fixed_weights() if eng is not None else contextlib.nullcontext()):   # the weights do not change inside one chain
+            for k8, t_net in _rows(gd.logsnr_fn, tau, order, gd.model_out_type, gd.w_guide):      # solver_coefs' rows, last one first
+                t_in = torch.full((rows,), t_net, dtype=F64, device=device)
+                out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
+                _hip.solver_step(x_t, out, hist, k8.tolist(), mot, cfg, clip_denoised, x_next, x_in_next, B, C, HW)
+                x_t, x_next = x_next, x_t
+                if cfg:
+                    x_in, x_in_next = x_in_next, x_in
+                else:
+                    x_in = x_t
+        return x_t
