@@ -68,7 +68,8 @@ typedef struct vd_gemm_desc {
     int32_t H, W, Cin;          /* image geometry for VD_IM2COL                                     */
     int32_t splitk;             /* >1: K is split over `splitk` slabs in ws, then reduced into C    */
     float*  ws; int64_t ws_bytes;
-    int32_t tile;               /* 0 = auto; 128, 64, 12864 (128x64), 64128 (64x128) force the block tile */
+    int32_t tile;               /* 0 = auto; 128, 64, 12864 (128x64), 64128 (64x128) force the block tile;  */
+                                /*   128256: the 128x256 split-operand form (N % 256 == 0, no split-K)     */
     float*  colsum;             /* optional, VD_COL A only: colsum[m] (+)= sum_k A[k][m] (bias gradient of a */
     int32_t colsum_accumulate;  /*   weight-gradient GEMM, computed from the tiles already staged); batch = 1  */
     float*  stats;              /* optional, forward launches: GroupNorm partials of the OUTPUT rows, laid out  */
@@ -94,6 +95,14 @@ int vd_gemm(const vd_gemm_desc* d, void* stream);
  * (bf16(x) rounds to Inf, the residual x - Inf poisons the products); pieces below the smallest normal bf16 are flushed. */
 int vd_gemm_last_tile(void);
 int vd_gemm_split_forms(void);   /* 1: the split-operand forms are in effect for this process (VD_GEMM_SPLIT, default 1), 0: fp32 MFMA everywhere */
+/* The 128x256 split-operand form gemm_split_kernel<128,256,a_kind,b_kind,false,16,TR> (code ..16128256): plain and batched ROW/ROW launches
+ * that would run the 128x128 KT = 16 split form take it when N % 256 == 0 and ceil(M/128) * (N/256) * batch is at least two workgroups per CU.
+ * Same row tile, same statistics chunks, bit-identical results.  tile = 128 keeps the 128x128 form, tile = 128256 forces the wide one at any
+ * N % 256 == 0 for ROW/ROW, ROW/COL and COL/COL operands (ROW/COL loses on it per launch and is not dispatched by itself: FINDINGS.md);
+ * VD_GEMM_BN256=0 (read once per process) is the A/B switch back to the 128x128 tiles everywhere.
+ * vd_gemm_plan_tile: the vd_gemm_last_tile code such a launch WOULD report, from the host plan alone (no device): contiguous aligned operands,
+ * no bias / residual; stats != 0: the launch emits GroupNorm partials.  -1 (vd_last_error) where vd_gemm would refuse the request. */
+int vd_gemm_plan_tile(int32_t M, int32_t N, int32_t K, int32_t a_kind, int32_t b_kind, int32_t batch, int32_t tile, int32_t stats);
 /* `count` (<= 36) same-shape weight-gradient GEMMs in ONE launch -- the 1x1-convolution / linear weight gradients of the blocks of one
  * UNet level (autograd of modules.py:79-80,141-144 w.r.t. the weight), whose operands live in unrelated buffers:
  *   C[e][M][N] (pitch ldc) = A[e]^T B[e],  A[e] = dY [K][M] (pitch lda), B[e] = X [K][N] (pitch ldb)   (= vd_gemm with COL / COL kinds)

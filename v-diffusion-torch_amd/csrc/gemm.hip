@@ -452,8 +452,12 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
     // ds_read_b64 and block a takes element a, i.e. MFMA block a owns the interleaved rows {2i + a} instead of
     // {32a + i}.  Halves the LDS instructions of the weight-gradient kernels; only the output row/column map changes.
     constexpr bool A2 = (AK == VD_COL) && (MT == 2);
-    constexpr bool B2 = (BK != VD_ROW) && (NT == 2);
+    // (NT == 4, the 128x256 form: one ds_read_b128 of columns 4i .. 4i+3, block b owns the columns {4i + b})
+    constexpr bool B2 = (BK != VD_ROW) && (NT == 2 || NT == 4);
     typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef std::conditional_t<NT == 4, f32x4, f32x2> f32xNT;      // the NT interleaved columns of one lane
+    static_assert(NT <= 2 || (SPL && KT == 16 && !SPLITK && !GROUPED && AK != VD_IM2COL && BK != VD_IM2COL),
+                  "256-column tiles: split-operand KT = 16 forms of plain / batched launches only");
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -698,8 +702,9 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
         if (B2) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const f32x2 v = *reinterpret_cast<const f32x2*>(bs + (8 * s + 4 * lh + j) * BN + wn + 2 * li);
-                fb[0][j] = v[0]; fb[NT - 1][j] = v[1];
+                const f32xNT v = *reinterpret_cast<const f32xNT*>(bs + (8 * s + 4 * lh + j) * BN + wn + NT * li);
+#pragma unroll
+                for (int b = 0; b < NT; ++b) fb[b][j] = v[b];
             }
         } else {
 #pragma unroll
@@ -755,8 +760,9 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
         if (B2) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const f32x2 v = *reinterpret_cast<const f32x2*>(bs + (16 * s + 8 * lh + j) * BN + wn + 2 * li);
-                fb[0][j] = v[0]; fb[NT - 1][j] = v[1];
+                const f32xNT v = *reinterpret_cast<const f32xNT*>(bs + (16 * s + 8 * lh + j) * BN + wn + NT * li);
+#pragma unroll
+                for (int b = 0; b < NT; ++b) fb[b][j] = v[b];
             }
         } else {
 #pragma unroll
@@ -786,27 +792,36 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
                 if (ISSUE_IN) issue_tiles(buf ^ 1, P);
                 prep_tiles(kt_prep, P);
             }
-            bf16x8 ah[MT], am[MT], al[MT], bh[NT], bm[NT], bl[NT];
+            // the B blocks are split and multiplied NBB at a time (as in wgrad_planes256_kernel): at NT = 4 that keeps 24 registers of B
+            // pieces live beside the 128 accumulators instead of 48; every accumulator still sees its six products in the same order
+            constexpr int NBB = NT > 2 ? 2 : NT;
+            bf16x8 ah[MT], am[MT], al[MT];
 #pragma unroll
             for (int a = 0; a < MT; ++a) split8(fa[a], ah[a], am[a], al[a]);
 #pragma unroll
-            for (int b = 0; b < NT; ++b) split8(fb[b], bh[b], bm[b], bl[b]);
-            if (AK == VD_COL && do_cs) {
-                asm volatile("" ::: "memory");
+            for (int b0 = 0; b0 < NT; b0 += NBB) {
+                bf16x8 bh[NBB], bm[NBB], bl[NBB];
+#pragma unroll
+                for (int b = 0; b < NBB; ++b) split8(fb[b0 + b], bh[b], bm[b], bl[b]);
+                if (b0 + NBB == NT) {
+                    if (AK == VD_COL && do_cs) {
+                        asm volatile("" ::: "memory");
+#pragma unroll
+                        for (int a = 0; a < MT; ++a)
+                            csum[a] += ((fa[a][0] + fa[a][1]) + (fa[a][2] + fa[a][3])) + ((fa[a][4] + fa[a][5]) + (fa[a][6] + fa[a][7]));
+                    }
+                    if (s + 1 < S) load_frags8(as, bs, s + 1, fa, fb);
+                }
 #pragma unroll
                 for (int a = 0; a < MT; ++a)
-                    csum[a] += ((fa[a][0] + fa[a][1]) + (fa[a][2] + fa[a][3])) + ((fa[a][4] + fa[a][5]) + (fa[a][6] + fa[a][7]));
-            }
-            if (s + 1 < S) load_frags8(as, bs, s + 1, fa, fb);
 #pragma unroll
-            for (int a = 0; a < MT; ++a)
-#pragma unroll
-                for (int b = 0; b < NT; ++b) {
-#define VD_MF(X, Y) acc[a][b] = TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(Y[b], X[a], acc[a][b], 0, 0, 0) \
-                                    : __builtin_amdgcn_mfma_f32_32x32x16_bf16(X[a], Y[b], acc[a][b], 0, 0, 0)
-                    VD_MF(al, bh); VD_MF(ah, bl); VD_MF(am, bm); VD_MF(am, bh); VD_MF(ah, bm); VD_MF(ah, bh);
+                    for (int b = 0; b < NBB; ++b) {
+#define VD_MF(X, Y) acc[a][b0 + b] = TR ? __builtin_amdgcn_mfma_f32_32x32x16_bf16(Y[b], X[a], acc[a][b0 + b], 0, 0, 0) \
+                                         : __builtin_amdgcn_mfma_f32_32x32x16_bf16(X[a], Y[b], acc[a][b0 + b], 0, 0, 0)
+                        VD_MF(al, bh); VD_MF(ah, bl); VD_MF(am, bm); VD_MF(am, bh); VD_MF(ah, bm); VD_MF(ah, bh);
 #undef VD_MF
-                }
+                    }
+            }
         }
     };
 
@@ -931,14 +946,15 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
     if (TR) {
         // lane (li, lh): row = block row li; register quad q of block b holds columns 8q + 4lh .. +3 of that block.  With
         // interleaved column ownership (B2: block b owns columns 2i + b) the four consecutive columns 16q + 8lh + 4h .. +3 of
-        // the wave's 64 are {block 0, block 1} x registers {4q + 2h, 4q + 2h + 1}.  Either way 8 quads per row block.
+        // the wave's 64 are {block 0, block 1} x registers {4q + 2h, 4q + 2h + 1}.  Either way 8 quads per row block.  With four interleaved
+        // blocks (NT == 4: block b owns columns 4i + b) register r of the four blocks IS a quad: columns 4 ((r & 3) + 8 (r >> 2) + 4 lh) .. +3.
         typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
         const f32x4 al4 = {p.alpha, p.alpha, p.alpha, p.alpha};
         constexpr int NQ = 4 * NT;
-        // the 8 column quads of a row block are handled in two halves of 4: bias / residual / offset staging for all 8 at once
+        // the 8 (NT == 4: 16) column quads of a row block are handled 4 at a time: bias / residual / offset staging for all 8 at once
         // (72 live registers beside the 64 accumulators) spilled to scratch under the 128-VGPR cap of the 4-workgroups-per-CU
         // KT = 16 forms (11-60 spilled VGPRs, tests/test_host_cpu.py::test_no_kernel_spills_to_scratch)
-        constexpr int NQH = NQ > 4 ? NQ / 2 : NQ;
+        constexpr int NQH = 4;
 #pragma unroll
         for (int a = 0; a < MT; ++a) {
             const int rowl = wm + (A2 ? 2 * li + a : 32 * a + li);
@@ -949,7 +965,8 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
 #pragma unroll
                 for (int ee = 0; ee < NQH; ++ee) {
                     const int e = e0 + ee;
-                    const int ncol = B2 ? wn + 16 * (e >> 1) + 8 * lh + 4 * (e & 1) : wn + 32 * (e >> 2) + 8 * (e & 3) + 4 * lh;
+                    const int ncol = (B2 && NT == 4) ? wn + 4 * ((e & 3) + 8 * (e >> 2) + 4 * lh)
+                                     : B2 ? wn + 16 * (e >> 1) + 8 * lh + 4 * (e & 1) : wn + 32 * (e >> 2) + 8 * (e & 3) + 4 * lh;
                     const int n = n0 + ncol;
                     const bool nok = (BK == VD_IM2COL) ? (ci0 + ncol < p.Cin) : (n < p.N);
                     vocs[ee] = nok ? (unsigned)(rowl * ldc4 + ncol * 4) : OOB;
@@ -966,7 +983,8 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
                 for (int ee = 0; ee < NQH; ++ee) {
                     const int e = e0 + ee;
                     f32x4 v;
-                    if (B2) {
+                    if constexpr (B2 && NT == 4) v = f32x4{acc[a][0][e], acc[a][1][e], acc[a][2][e], acc[a][3][e]};
+                    else if (B2) {
                         const int r0 = 4 * (e >> 1) + 2 * (e & 1);
                         v = f32x4{acc[a][0][r0], acc[a][NT - 1][r0], acc[a][0][r0 + 1], acc[a][NT - 1][r0 + 1]};
                     } else {
@@ -986,7 +1004,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
     const bool want_stats = !SPLITK && p.stats != nullptr && !(PB(p) & 32), edge = rows_valid < BM;       // both uniform
 #pragma unroll
     for (int b = 0; b < NT; ++b) {
-        const int ncol = wn + (B2 ? 2 * li + b : 32 * b + li);
+        const int ncol = wn + (B2 ? NT * li + b : 32 * b + li);
         const int n = n0 + ncol;
         const bool nok = (BK == VD_IM2COL) ? (ci0 + ncol < p.Cin) : (n < p.N);
         const unsigned voc = nok ? (unsigned)(row_lane * ldc4 + ncol * 4) : OOB;
@@ -1401,17 +1419,75 @@ void launch_k16_tr(const GemmArgs& a, dim3 grid, hipStream_t st, bool k16, bool 
     else launch_dma<SPL, BM, BN, AK, BK, SPLITK, 32, false, false>(a, NoGroup{}, grid, st);
 }
 
-template <int BM, int BN, int AK, int BK, bool SPLITK>
-void launch(const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
+// ---- the 128x256 split-operand form (gemm_split_kernel<128, 256, ..., 16, TR>) of plain and batched launches: 4 waves as 2 (m) x 2 (n), a
+// 64x128 wave tile -- what wgrad_planes256_kernel has per wave: 6 split8 per 48 MFMAs (5.5 vector instructions per MFMA gap instead of 7.3),
+// a quarter fewer LDS-read bytes and half the barriers per MFMA -- and per workgroup a quarter fewer DMA bytes per MFMA (every A element is
+// read and split once at N = 256).  The row tile stays 128, so the GroupNorm partials ([image][64-row chunk][2][N]) and every caller are
+// as with the 128x128 form, and the arithmetic is the same instruction sequence per output element: the results are bit-identical.
+// Two LDS stages of 384 x 16 floats = 48 KB: two workgroups per CU (VD_SPL_BLOCKS).
+constexpr int TILE_WIDE = 128256;      // vd_gemm_desc.tile: force the form (any N % 256 == 0)
+static bool wide_on() {                // VD_GEMM_BN256=0 (read once, like VD_PLANES256): the A/B switch back to the 128x128 tiles
+    static const bool on = !(getenv("VD_GEMM_BN256") && atoi(getenv("VD_GEMM_BN256")) == 0);
+    return on;
+}
+// 32-bit byte offsets inside one 128 x 256 block tile stay inside the descriptor range (dma_in_range covers 128 x 128)
+bool wide_in_range(const GemmArgs& a) {
+    const long long lim = 0x70000000LL / 4;
+    return 256LL * a.lda + 256 < lim && 256LL * a.ldb + 256 < lim && 128LL * a.ldc + 256 < lim && 128LL * a.ldr + 256 < lim;
+}
+
+// what a vd_gemm launch runs, decided ONCE here from the shape, the operand kinds and the process-wide switches: run_gemm launches by
+// it, vd_gemm_plan_tile answers from it without a device
+struct GemmPlan { int tile; bool wide; int bm, bn; long long nm, nn; int ktile; bool k16, spl; };
+int plan_gemm(const GemmArgs& a, int ak, int bk, int batch, int splitk, int requested, GemmPlan* out) {
+    static const char* env = getenv("VD_GEMM_TILE");        // experiments only (choose_tile reads it the same way)
+    const int forced = (env && requested == 0) ? atoi(env) : requested;
+    const bool conv = ak == VD_IM2COL, wgrad = bk == VD_IM2COL, want_wide = forced == TILE_WIDE;
+    GemmPlan P;
+    P.tile = want_wide ? 0 : choose_tile(a.M, wgrad ? a.Cin : a.N, wgrad, (long long)batch * splitk, forced);
+    P.bm = TILES[P.tile].bm; P.bn = TILES[P.tile].bn;
+    P.nm = (a.M + P.bm - 1) / P.bm;
+    P.nn = wgrad ? 9LL * ((a.Cin + P.bn - 1) / P.bn) : (a.N + P.bn - 1) / P.bn;
+    P.ktile = ktile_for(a, P.tile, P.nm * P.nn * batch, splitk > 1, wgrad && (long long)a.K >= WGRAD_WIDE_PIXELS, wgrad && splitk <= 1);
     // the only tile with a KT = 16 instantiation; an unsplit conv weight gradient never takes it (ktile_for): those two
     // instantiations carried 11 spilled VGPRs, so they are not built at all
-    constexpr bool has16 = BM == 128 && BN == 128 && !(BK == VD_IM2COL && !SPLITK);
-    const bool k16 = has16 && ktile == 16;
-    const bool tr = use_dma(a) && use_tr(a, BK == VD_IM2COL);
+    P.k16 = P.tile == 0 && !(wgrad && splitk <= 1) && P.ktile == 16;
     // split-operand forms (SPL): the 128-row tiles of every operand kind without im2col addressing
+    P.spl = P.bm == 128 && !conv && !wgrad && use_dma(a) && split_forms();
+    // the 128x256 form: ROW/ROW launches where the 128x128 KT = 16 split form would run, N is a multiple of 256 and the launch still gives
+    // every CU two workgroups (M = 32 768, N = 256: 256 workgroups would leave half the chip without one); an explicit tile request wins
+    const bool kinds = (ak == VD_ROW && (bk == VD_ROW || bk == VD_COL)) || (ak == VD_COL && bk == VD_COL);
+    const bool can = P.spl && P.tile == 0 && splitk <= 1 && kinds && a.N % 256 == 0 && wide_in_range(a);
+    VD_REQUIRE(requested != TILE_WIDE || can, "vd_gemm: tile = %d needs the split-operand forms, N %% 256 == 0 (N=%d), ROW/ROW, ROW/COL or COL/COL operands "
+               "and no split-K", TILE_WIDE, a.N);
+    // (ROW/ROW only by itself: per launch the ROW/COL input-gradient shapes LOSE 8-13 % on the wide form and no COL/COL launch of the step
+    // qualifies -- FINDINGS.md; those kinds run it on request)
+    const bool natural = forced == 0 && wide_on() && ak == VD_ROW && bk == VD_ROW && P.k16 && P.nm * (a.N / 256) * batch >= 2LL * vd_cu_count();
+    P.wide = can && (want_wide || natural);
+    if (P.wide) { P.bn = 256; P.nn = a.N / 256; P.ktile = 16; P.k16 = true; }
+    *out = P;
+    return 0;
+}
+// the launch's transposed-epilogue choice and its last-tile code (after run_gemm has pointed a.C at the split-K slabs)
+bool plan_tr(const GemmArgs& a, bool wgrad) { return use_dma(a) && use_tr(a, wgrad); }
+int plan_code(const GemmArgs& a, const GemmPlan& P, bool tr) { return vd_tile_code(tr, P.spl, use_dma(a) ? (P.k16 ? 16 : 32) : 0, P.bm, P.bn); }
+
+template <int AK, int BK>
+void launch_wide(const GemmArgs& a, const GemmPlan& P, dim3 grid, hipStream_t st) {
+    const bool tr = plan_tr(a, false);
+    vd_g_last_tile = plan_code(a, P, tr);
+    if (tr) launch_dma<true, 128, 256, AK, BK, false, 16, true, false>(a, NoGroup{}, grid, st);
+    else launch_dma<true, 128, 256, AK, BK, false, 16, false, false>(a, NoGroup{}, grid, st);
+}
+
+template <int BM, int BN, int AK, int BK, bool SPLITK>
+void launch(const GemmArgs& a, dim3 grid, hipStream_t st, const GemmPlan& P) {
+    constexpr bool has16 = BM == 128 && BN == 128 && !(BK == VD_IM2COL && !SPLITK);
     constexpr bool has_spl = BM == 128 && AK != VD_IM2COL && BK != VD_IM2COL;
-    const bool spl = has_spl && use_dma(a) && split_forms();
-    vd_g_last_tile = vd_tile_code(tr, spl, use_dma(a) ? (k16 ? 16 : 32) : 0, BM, BN);
+    const bool k16 = has16 && P.k16;
+    const bool tr = plan_tr(a, BK == VD_IM2COL);
+    const bool spl = has_spl && P.spl;
+    vd_g_last_tile = plan_code(a, P, tr);
     if constexpr (has_spl) {
         if (spl) return launch_k16_tr<true, BM, BN, AK, BK, SPLITK, (has16 ? 16 : 32)>(a, grid, st, k16, tr);
     }
@@ -1420,17 +1496,17 @@ void launch(const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
 }
 
 template <int AK, int BK, bool SPLITK>
-void launch_tile2(int t, const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
-    if (t == 0) launch<128, 128, AK, BK, SPLITK>(a, grid, st, ktile);
-    else if (t == 1) launch<128, 64, AK, BK, SPLITK>(a, grid, st, ktile);
-    else if (t == 2) launch<64, 128, AK, BK, SPLITK>(a, grid, st, ktile);
-    else launch<64, 64, AK, BK, SPLITK>(a, grid, st, ktile);
+void launch_tile2(const GemmPlan& P, const GemmArgs& a, dim3 grid, hipStream_t st) {
+    if (P.tile == 0) launch<128, 128, AK, BK, SPLITK>(a, grid, st, P);
+    else if (P.tile == 1) launch<128, 64, AK, BK, SPLITK>(a, grid, st, P);
+    else if (P.tile == 2) launch<64, 128, AK, BK, SPLITK>(a, grid, st, P);
+    else launch<64, 64, AK, BK, SPLITK>(a, grid, st, P);
 }
 
 template <int AK, int BK>
-void launch_tile(int t, bool splitk, const GemmArgs& a, dim3 grid, hipStream_t st, int ktile) {
-    if (splitk) launch_tile2<AK, BK, true>(t, a, grid, st, ktile);
-    else launch_tile2<AK, BK, false>(t, a, grid, st, ktile);
+void launch_tile(const GemmPlan& P, bool splitk, const GemmArgs& a, dim3 grid, hipStream_t st) {
+    if (splitk) launch_tile2<AK, BK, true>(P, a, grid, st);
+    else launch_tile2<AK, BK, false>(P, a, grid, st);
 }
 
 int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
@@ -1474,17 +1550,17 @@ int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
 #endif
     VD_REQUIRE((a.probe & 16) || !(d.colsum && (ak != VD_COL || batch > 1)), "vd_gemm: colsum needs a COL-kind A operand and batch 1");
 
-    const int tile = choose_tile(d.M, wgrad ? d.Cin : d.N, wgrad, (long long)batch * splitk, d.tile);
-    const int tbm = TILES[tile].bm, tbn = TILES[tile].bn;
-    const long long nm = (d.M + tbm - 1) / tbm;
-    const long long nn = wgrad ? 9LL * ((d.Cin + tbn - 1) / tbn) : (d.N + tbn - 1) / tbn;
+    GemmPlan P;
+    if (plan_gemm(a, ak, bk, batch, splitk, d.tile, &P)) return 1;
+    const int tbm = P.bm;
+    const long long nm = P.nm, nn = P.nn;
     VD_REQUIRE(nm <= 65535, "vd_gemm: too many row tiles (%lld)", nm);
     if (d.stats && !(a.probe & 32)) {
         VD_REQUIRE(batch == 1 && splitk == 1 && !wgrad && bk == VD_ROW && ak != VD_COL, "vd_gemm: output statistics need a plain forward launch");
         VD_REQUIRE(d.stats_hw > 0 && d.stats_hw % (tbm / 2) == 0 && d.M % d.stats_hw == 0,
                    "vd_gemm: output statistics need H*W (%d) to be a multiple of half the row tile (%d)", d.stats_hw, tbm / 2);
     }
-    const int ktile = ktile_for(a, tile, nm * nn * batch, splitk > 1, wgrad && (long long)d.K >= WGRAD_WIDE_PIXELS, wgrad && splitk <= 1);
+    const int ktile = P.ktile;
     a.kt_total = conv ? 9 * ((d.Cin + ktile - 1) / ktile) : (d.K + ktile - 1) / ktile;
     a.kt_per_split = a.kt_total;
 
@@ -1499,10 +1575,10 @@ int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
         float* cpart = d.ws + used * a.slab_stride;          // per-slab bias-gradient partials live behind the slabs
         if (d.colsum && !(a.probe & 16)) a.colsum = cpart;      // (probe builds write timestamps through colsum)
         dim3 grid(nn, nm, used);
-        if (ak == VD_COL && bk == VD_COL) launch_tile<VD_COL, VD_COL>(tile, true, a, grid, st, ktile);
-        else if (ak == VD_COL && bk == VD_IM2COL) launch_tile<VD_COL, VD_IM2COL>(tile, true, a, grid, st, ktile);
-        else if (ak == VD_ROW && bk == VD_ROW) launch_tile<VD_ROW, VD_ROW>(tile, true, a, grid, st, ktile);
-        else if (ak == VD_ROW && bk == VD_COL) launch_tile<VD_ROW, VD_COL>(tile, true, a, grid, st, ktile);
+        if (ak == VD_COL && bk == VD_COL) launch_tile<VD_COL, VD_COL>(P, true, a, grid, st);
+        else if (ak == VD_COL && bk == VD_IM2COL) launch_tile<VD_COL, VD_IM2COL>(P, true, a, grid, st);
+        else if (ak == VD_ROW && bk == VD_ROW) launch_tile<VD_ROW, VD_ROW>(P, true, a, grid, st);
+        else if (ak == VD_ROW && bk == VD_COL) launch_tile<VD_ROW, VD_COL>(P, true, a, grid, st);
         else VD_REQUIRE(false, "vd_gemm: split-K not built for kinds (%d,%d)", ak, bk);
         VD_LAUNCH_CHECK("gemm_kernel(splitk)");
         if (!wgrad && !(a.probe & 16)) {   // plain reduce here; the conv wgrad caller reduces with the OIHW transposition itself
@@ -1514,12 +1590,19 @@ int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
         return 0;
     }
     dim3 grid(nn, nm, batch);
-    if (ak == VD_ROW && bk == VD_ROW) launch_tile<VD_ROW, VD_ROW>(tile, false, a, grid, st, ktile);
-    else if (ak == VD_ROW && bk == VD_COL) launch_tile<VD_ROW, VD_COL>(tile, false, a, grid, st, ktile);
-    else if (ak == VD_COL && bk == VD_COL) launch_tile<VD_COL, VD_COL>(tile, false, a, grid, st, ktile);
-    else if (ak == VD_COL && bk == VD_ROW) launch_tile<VD_COL, VD_ROW>(tile, false, a, grid, st, ktile);
-    else if (ak == VD_IM2COL && bk == VD_ROW) launch_tile<VD_IM2COL, VD_ROW>(tile, false, a, grid, st, ktile);
-    else if (ak == VD_COL && bk == VD_IM2COL) launch_tile<VD_COL, VD_IM2COL>(tile, false, a, grid, st, ktile);
+    if (P.wide) {
+        if (ak == VD_ROW && bk == VD_ROW) launch_wide<VD_ROW, VD_ROW>(a, P, grid, st);
+        else if (ak == VD_ROW) launch_wide<VD_ROW, VD_COL>(a, P, grid, st);
+        else launch_wide<VD_COL, VD_COL>(a, P, grid, st);
+        VD_LAUNCH_CHECK("gemm_split_kernel(128x256)");
+        return 0;
+    }
+    if (ak == VD_ROW && bk == VD_ROW) launch_tile<VD_ROW, VD_ROW>(P, false, a, grid, st);
+    else if (ak == VD_ROW && bk == VD_COL) launch_tile<VD_ROW, VD_COL>(P, false, a, grid, st);
+    else if (ak == VD_COL && bk == VD_COL) launch_tile<VD_COL, VD_COL>(P, false, a, grid, st);
+    else if (ak == VD_COL && bk == VD_ROW) launch_tile<VD_COL, VD_ROW>(P, false, a, grid, st);
+    else if (ak == VD_IM2COL && bk == VD_ROW) launch_tile<VD_IM2COL, VD_ROW>(P, false, a, grid, st);
+    else if (ak == VD_COL && bk == VD_IM2COL) launch_tile<VD_COL, VD_IM2COL>(P, false, a, grid, st);
     else VD_REQUIRE(false, "vd_gemm: unsupported operand kinds (%d,%d)", ak, bk);
     VD_LAUNCH_CHECK("gemm_kernel");
     return 0;
@@ -1673,6 +1756,26 @@ int vd_gemm_grouped_wgrad_kblk(const float* const* A, const float* const* B, flo
 
 thread_local int vd_g_last_tile = 0;
 extern "C" int vd_gemm_last_tile(void) { return vd_g_last_tile; }
+
+/* the last-tile code a plain or batched vd_gemm launch of this shape would report, from the host plan alone (no device, no launch):
+ * contiguous 16-byte-aligned operands (lda = K or M, ldb = K or N, ldc = N by kind), no bias / residual, batch and head strides multiples
+ * of 4; stats != 0: the launch emits GroupNorm partials (plain epilogue).  -1 (and vd_last_error) where vd_gemm would refuse the request. */
+extern "C" int vd_gemm_plan_tile(int32_t M, int32_t N, int32_t K, int32_t a_kind, int32_t b_kind, int32_t batch, int32_t tile, int32_t stats) {
+    if (!(M > 0 && N > 0 && K > 0 && a_kind >= VD_ROW && a_kind <= VD_COL && b_kind >= VD_ROW && b_kind <= VD_COL)) {
+        vd_set_error("vd_gemm_plan_tile: plain operand kinds and a non-empty problem only");
+        return -1;
+    }
+    float* const aligned = reinterpret_cast<float*>(uintptr_t(4096));      // (never dereferenced: the plan looks at alignment only)
+    GemmArgs a = {};
+    a.A = a.B = aligned; a.C = aligned;
+    a.M = M; a.N = N; a.K = K;
+    a.lda = a_kind == VD_ROW ? K : M; a.ldb = b_kind == VD_ROW ? K : N; a.ldc = N;
+    a.nh = 1; a.alpha = 1.f; a.lgW = a.lgHW = -1;
+    a.stats = stats ? aligned : nullptr;
+    GemmPlan P;
+    if (plan_gemm(a, a_kind, b_kind, batch > 0 ? batch : 1, 1, tile, &P)) return -1;
+    return plan_code(a, P, plan_tr(a, false));
+}
 
 extern "C" int vd_gemm(const vd_gemm_desc* d, void* stream) {
     VD_REQUIRE(d != nullptr, "vd_gemm: null descriptor");

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("VDIFF_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvdiff_hip.so")   # (override: A/B builds)
 
 ROW, COL, IM2COL = 0, 1, 2
+TILE_WIDE = 128256            # gemm(tile=...): force the 128x256 split-operand form (N % 256 == 0); 128 keeps the 128x128 tiles
 RS_NONE, RS_DOWN, RS_UP = 0, 1, 2
 OUT_TYPES = {"v": 0, "x0": 1, "eps": 2, "both": 3}
 REWEIGHTS = {"constant": 0, "snr": 1, "snr_trunc": 2, "snr_1plus": 3}
@@ -41,6 +42,7 @@ _SIGNATURES = {
     "vd_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
     "vd_gemm_last_tile": (C.c_int, []),
     "vd_gemm_split_forms": (C.c_int, []),
+    "vd_gemm_plan_tile": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
     "vd_gemm_grouped_wgrad_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
     "vd_gemm_grouped_wgrad_auto_split": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
     "vd_gemm_grouped_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _sz, _vp]),
