@@ -463,6 +463,35 @@ int vd_distill_loss_bwd(const float* resid, const float* coef, const float* glos
 int vd_solver_step(const float* xt, const float* out, float* hist, const float* k, const float* k_dev,
                    int32_t model_out_type, int32_t cfg, int32_t clip,
                    float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3; the companion Lu et al. 2022 recommend for the data-prediction
+ * solver under guidance).  kth[b] = the element of rank r (0-based, ascending) of |x[b, 0..N)|, for n rows of N floats, 0 <= r < N.
+ * Order: the bit pattern of |x| as an unsigned integer -- -0 = +0, denormals order as numbers, +Inf above every finite value, a NaN
+ * above +Inf (where numpy.partition puts it).  The result is one of the row's own values, exact and bitwise reproducible: a radix
+ * select (four passes of 8 bits, LDS histograms, integer counts, no floating-point atomics).  One workgroup owns one row and waits
+ * on no other workgroup.  There is one code path for every N <= VD_KTH_MAX_ROW (no size boundary between forms other than the access
+ * width: dwordx4 when N is a multiple of 4 and x is 16-byte aligned, scalar otherwise; one workgroup is 1024 threads, so rows of more
+ * than 1024 accesses take more than one trip per pass). */
+#define VD_KTH_MAX_ROW 2147483647LL
+int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, float* kth, void* stream);
+/* vd_solver_step with the guided prediction thresholded dynamically instead of each branch clipped to [-1, 1]: ONE launch, same table
+ * row, same aliasing rules, same host-or-device coefficient forms, same access forms.  Per sample, over its N = C*HW elements:
+ *   x_c, x_u = a0*xt + b0x*out (+ b0e*out_eps)            per branch, NOT clipped
+ *   g        = cfg ? x_c + w_guide*(x_c - x_u) : x_c
+ *   s_raw    = the element of rank r of |g|               (vd_abs_kth_rows' order and selection, inside this launch)
+ *   s        = min(max(s_raw, 1), s_max)                  s_max >= 1, +Inf for no cap; a NaN s_raw stays a NaN
+ *   g'       = min(max(g, -s), s) / s                     IEEE fp32 division
+ *   xn       = c1*xt + c2*g' + c2rho*(g' - hist);   hist = g';   xdup = xn on rows 2b and 2b+1
+ * r is the caller's: r = min(N-1, ceil(q*(N-1))) for the quantile q in (0, 1], computed once in fp64 on the host
+ * (v_diffusion.threshold_rank) -- the "higher" order statistic, a value of the sample itself, where Imagen interpolates a percentile;
+ * the two differ by at most the gap between two neighbouring order statistics.  q = 1: s_raw = max|g|, a pure rescale.
+ * An s that is NaN or Inf makes that sample's outputs NaN or 0; other samples are unaffected.  A NaN element of g passes through.
+ * s_out (optional, n floats) receives s.  One workgroup owns one sample from its first read to its last write (it re-reads the
+ * sample's input rows once per selection pass and once more for the update; they stay in L2) and waits on no other workgroup: the
+ * launch is HIP-graph capturable and has no workspace.  Every pass evaluates g by the same fused operations, so the element that
+ * holds s_raw > 1 maps to exactly +-1; with s_max = 1 and cfg = 0 the result equals vd_solver_step(clip = 1) bit for bit. */
+int vd_solver_step_dyn(const float* xt, const float* out, float* hist, const float* k, const float* k_dev,
+                       int32_t model_out_type, int32_t cfg, int64_t r, float s_max, float* s_out,
+                       float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */

@@ -3,7 +3,7 @@
 //   train_loss (mse) forward/backward  diffusion.py:466-490,520-541 ; flat_mean functions.py:102-104
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
-//   progressive distillation and the DPM-Solver++(2M) reverse step: no counterpart in the reference
+//   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 #include "common.h"
 
@@ -441,6 +441,161 @@ __global__ void solver_step_kernel(const SolverArgs p) {
     }
 }
 
+// ---- dynamic thresholding (Saharia et al. 2022, section 2.3) of the solver's guided x0 prediction: s = the element of rank r of |g|
+// over the sample, clamped to [1, s_max]; g' = clamp(g, -s, s) / s.  The rank-r element is found by a radix select over the bit
+// pattern of |g| (as unsigned integers the patterns order like the numbers, +Inf above every finite value, NaNs above +Inf): four
+// passes of 8 bits from the top, each a 256-bin LDS histogram of the elements that still match the prefix, a scan for the bin that
+// holds the rank, and a narrowing of prefix and rank.  Integer counting only: the result is exact and bitwise reproducible.
+// ONE WORKGROUP OWNS ONE ROW from its first read to its last write, and nothing here can wait on another workgroup (no global
+// counter, ticket, spin or atomic): every pass re-reads the row's inputs, which are at most a few hundred KB and stay in L2.
+// The histogram exists in KTH_COPIES copies, lane l counting into copy l % KTH_COPIES with the copies one bank apart: the top bits
+// of |g| fall into a handful of bins, and 64 lanes adding to one LDS word serialise.
+enum { KTH_BINS = 256, KTH_COPIES = 8, KTH_PITCH = KTH_BINS + 1, KTH_THREADS = 1024 };
+
+struct KthShared { uint32_t hist[KTH_COPIES * KTH_PITCH]; uint32_t prefix, rank; };
+
+// bit pattern of the element of rank r (0-based, ascending) of |e_0|, ..., |e_{N-1}|, where prod(i, e) produces the elements
+// [i, i + V) and must produce the same bits each time it is asked.  Called by every thread of the workgroup; r < N < 2^31.
+template <int V, class Prod>
+__device__ __forceinline__ uint32_t abs_kth_select(const Prod& prod, long long N, uint32_t r, KthShared& sh) {
+    const int lane = threadIdx.x & 63;
+    uint32_t prefix = 0, mask = 0;
+#pragma unroll 1
+    for (int shift = 24; shift >= 0; shift -= 8) {
+        for (int t = threadIdx.x; t < KTH_COPIES * KTH_PITCH; t += blockDim.x) sh.hist[t] = 0;
+        __syncthreads();
+        uint32_t* mine = sh.hist + (threadIdx.x % KTH_COPIES) * KTH_PITCH;
+        for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)blockDim.x * V) {
+            float e[V];
+            prod(i, e);
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                const uint32_t key = __float_as_uint(e[j]) & 0x7fffffffu;
+                if ((key & mask) == prefix) atomicAdd(mine + ((key >> shift) & (KTH_BINS - 1)), 1u);
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x < 64) {                              // wave 0: lane l owns bins 4l .. 4l+3
+            uint32_t c[4], tot = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                c[q] = 0;
+#pragma unroll
+                for (int u = 0; u < KTH_COPIES; ++u) c[q] += sh.hist[u * KTH_PITCH + 4 * lane + q];
+                tot += c[q];
+            }
+            uint32_t upto = tot;                             // inclusive scan over the lanes
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t v = __shfl_up(upto, o, 64);
+                if (lane >= o) upto += v;
+            }
+            const uint32_t before = upto - tot;
+            if (r >= before && r < upto) {                   // true on exactly one lane: the counts sum to the elements still matching
+                uint32_t rr = r - before;
+                int q = 0;
+#pragma unroll
+                for (int t = 0; t < 3; ++t)
+                    if (q == t && rr >= c[t]) { rr -= c[t]; q = t + 1; }
+                sh.prefix = prefix | ((uint32_t)(4 * lane + q) << shift);
+                sh.rank = rr;
+            }
+        }
+        __syncthreads();
+        prefix = sh.prefix; r = sh.rank; mask |= (uint32_t)(KTH_BINS - 1) << shift;
+    }
+    return prefix;
+}
+
+template <int V> struct RowProd {
+    const float* row;
+    __device__ __forceinline__ void operator()(long long i, float (&e)[V]) const { ldv<V>(row + i, e); }
+};
+
+template <int V>
+__global__ __launch_bounds__(KTH_THREADS) void abs_kth_rows_kernel(const float* x, long long N, uint32_t r, float* kth) {
+    __shared__ KthShared sh;
+    const RowProd<V> prod = {x + (long long)blockIdx.x * N};
+    const uint32_t key = abs_kth_select<V>(prod, N, r, sh);
+    if (threadIdx.x == 0) kth[blockIdx.x] = __uint_as_float(key);
+}
+
+// The selection passes and the final pass must see the same bits of g, and with s_max = 1 and no guidance the step must reproduce
+// solver_step_kernel(clip = 1) bit for bit: the three expressions below are written once, with contraction off and the fused
+// operations spelled out -- the grouping the compiler gives solver_step_kernel's expressions.
+__device__ __forceinline__ float dyn_x0(float a0, float b0x, float b0e, bool both, float z, float o, float oe) {
+#pragma clang fp contract(off)
+    const float e = both ? b0e * oe : 0.f;
+    return __builtin_fmaf(b0x, o, a0 * z) + e;
+}
+
+__device__ __forceinline__ float dyn_guide(float w, float xc, float xu) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(w, xc - xu, xc);
+}
+
+__device__ __forceinline__ float dyn_update(float c1, float c2, float c2r, float z, float g, float h) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(c2r, g - h, __builtin_fmaf(c1, z, c2 * g));
+}
+
+// unclipped guided x0 prediction g of elements [i, i + V) of one sample, and the state z it was predicted from
+template <int V> struct GuidedProd {
+    const float* xt; const float* oc; const float* ou;       // the sample's row of xt, its cond and uncond output rows (ou unused without cfg)
+    long long N; bool both, cfg; float a0, b0x, b0e, w;
+    __device__ __forceinline__ void eval(long long i, float (&z)[V], float (&g)[V]) const {
+        float o[V], oe[V] = {};
+        ldv<V>(xt + i, z);
+        ldv<V>(oc + i, o);
+        if (both) ldv<V>(oc + N + i, oe);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g[j] = dyn_x0(a0, b0x, b0e, both, z[j], o[j], oe[j]);
+        if (cfg) {
+            ldv<V>(ou + i, o);
+            if (both) ldv<V>(ou + N + i, oe);
+#pragma unroll
+            for (int j = 0; j < V; ++j) g[j] = dyn_guide(w, g[j], dyn_x0(a0, b0x, b0e, both, z[j], o[j], oe[j]));
+        }
+    }
+    __device__ __forceinline__ void operator()(long long i, float (&g)[V]) const { float z[V]; eval(i, z, g); }
+};
+
+struct SolverDynArgs {
+    const float* xt; const float* out; float* hist; float k[8]; const float* kdev;
+    int type, cfg; uint32_t r; float s_max; float* s_out; float* xn; float* xdup; int n; long long N;
+};
+
+// one workgroup per sample.  No thread writes before every thread has left the last selection pass (its closing barrier), and a
+// thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
+template <int V>
+__global__ __launch_bounds__(KTH_THREADS) void solver_step_dyn_kernel(const SolverDynArgs p) {
+    __shared__ KthShared sh;
+    const long long b = blockIdx.x, N = p.N;
+    const float* kp = p.kdev ? p.kdev : p.k;
+    const float c1 = kp[3], c2 = kp[4], c2r = kp[5];
+    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    const GuidedProd<V> prod = {p.xt + b * N, p.out + (b * mul) * Co * N, p.out + (b * mul + p.cfg) * Co * N, N,
+                                p.type == OUT_BOTH, p.cfg != 0, kp[0], kp[1], kp[2], kp[6]};
+    const float s_raw = __uint_as_float(abs_kth_select<V>(prod, N, p.r, sh));
+    const float s = s_raw != s_raw ? s_raw : fminf(fmaxf(s_raw, 1.f), p.s_max);       // a NaN of rank r stays one
+    if (threadIdx.x == 0 && p.s_out) p.s_out[b] = s;
+    for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)blockDim.x * V) {
+        float z[V], g[V], h[V], xn[V];
+        prod.eval(i, z, g);
+        ldv<V>(p.hist + b * N + i, h);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float c = g[j] < -s ? -s : (g[j] > s ? s : g[j]);                         // a NaN passes through
+            if (s != 1.f) c = c / s;                                                  // IEEE division; c / 1 = c
+            g[j] = c;
+            xn[j] = dyn_update(c1, c2, c2r, z[j], c, h[j]);
+        }
+        stv<V>(p.hist + b * N + i, g);
+        stv<V>(p.xn + b * N + i, xn);
+        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+    }
+}
+
 }  // namespace
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
@@ -578,5 +733,43 @@ extern "C" int vd_solver_step(const float* xt, const float* out, float* hist, co
     else
         hipLaunchKernelGGL(solver_step_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
     VD_LAUNCH_CHECK("solver_step_kernel");
+    return 0;
+}
+
+extern "C" int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, float* kth, void* stream) {
+    VD_REQUIRE(x && kth, "vd_abs_kth_rows: null pointer");
+    VD_REQUIRE(n > 0 && N > 0, "vd_abs_kth_rows: empty batch or row (n=%d, N=%lld)", n, (long long)N);
+    VD_REQUIRE(N <= VD_KTH_MAX_ROW, "vd_abs_kth_rows: rows of at most %lld elements (N=%lld)", (long long)VD_KTH_MAX_ROW, (long long)N);
+    VD_REQUIRE(r >= 0 && r < N, "vd_abs_kth_rows: rank %lld outside [0, %lld)", (long long)r, (long long)N);
+    if (N % 4 == 0 && vd_aligned16(x))
+        hipLaunchKernelGGL(abs_kth_rows_kernel<4>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, x, (long long)N, (uint32_t)r, kth);
+    else
+        hipLaunchKernelGGL(abs_kth_rows_kernel<1>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, x, (long long)N, (uint32_t)r, kth);
+    VD_LAUNCH_CHECK("abs_kth_rows_kernel");
+    return 0;
+}
+
+extern "C" int vd_solver_step_dyn(const float* xt, const float* out, float* hist, const float* k, const float* k_dev, int32_t type,
+                                  int32_t cfg, int64_t r, float s_max, float* s_out, float* xn, float* xdup, int32_t n, int32_t C,
+                                  int32_t HW, void* stream) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_solver_step_dyn: pass the coefficients either as host k or as device k_dev");
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_solver_step_dyn: bad model_out_type %d", type);
+    VD_REQUIRE(xt && out && hist && xn, "vd_solver_step_dyn: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_solver_step_dyn: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_REQUIRE(!xdup || cfg, "vd_solver_step_dyn: the duplicated state is the guided network's input (cfg = 1)");
+    VD_REQUIRE(hist != xt && hist != xn, "vd_solver_step_dyn: hist is a buffer of its own");
+    VD_REQUIRE(s_max >= 1.f, "vd_solver_step_dyn: s_max must be >= 1 (+Inf for no cap), got %g", (double)s_max);
+    const long long N = (long long)C * HW;
+    VD_REQUIRE(N <= VD_KTH_MAX_ROW, "vd_solver_step_dyn: images of at most %lld elements (C*HW=%lld)", (long long)VD_KTH_MAX_ROW, N);
+    VD_REQUIRE(r >= 0 && r < N, "vd_solver_step_dyn: rank %lld outside [0, %lld)", (long long)r, N);
+    SolverDynArgs p = {};
+    p.xt = xt; p.out = out; p.hist = hist; p.kdev = k_dev;
+    for (int i = 0; i < 8; ++i) p.k[i] = k ? k[i] : 0.f;
+    p.type = type; p.cfg = cfg ? 1 : 0; p.r = (uint32_t)r; p.s_max = s_max; p.s_out = s_out; p.xn = xn; p.xdup = xdup; p.n = n; p.N = N;
+    if (N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup))
+        hipLaunchKernelGGL(solver_step_dyn_kernel<4>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(solver_step_dyn_kernel<1>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("solver_step_dyn_kernel");
     return 0;
 }

@@ -16,9 +16,10 @@ import sys
 from .diffusion import GaussianDiffusion, get_logsnr_schedule
 from .distill import DistillationDiffusion, distill_coefs
 from .models.unet import UNet
-from .solver import solver_coefs
+from .solver import dynamic_threshold, solver_coefs, threshold_rank
 
-_HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusion", "distill_coefs", "solver_coefs"]
+_HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusion", "distill_coefs", "solver_coefs", "threshold_rank",
+        "dynamic_threshold"]
 _DELEGATED = ["get_dataloader", "DATA_INFO", "dict2str", "seed_all", "update_config", "fill_with_defaults", "Trainer",
               "Evaluator", "DummyScheduler"]
 _ref_pkg = None

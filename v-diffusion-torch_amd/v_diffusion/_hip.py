@@ -125,6 +125,8 @@ _SIGNATURES = {
     "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_abs_kth_rows": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
+    "vd_solver_step_dyn": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -815,6 +817,18 @@ def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=No
     arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
     _check(lib().vd_solver_step(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
                                 n, Cc, HW, stream()), "vd_solver_step")
+
+
+def abs_kth_rows(x, n, N, r, kth):
+    """kth[b] = the element of rank r of |x[b]| over n rows of N floats (vd_abs_kth_rows: exact radix select)"""
+    _check(lib().vd_abs_kth_rows(ptr(x), n, int(N), int(r), ptr(kth), stream()), "vd_abs_kth_rows")
+
+
+def solver_step_dyn(xt, out, hist, k8, mot, cfg, r, s_max, s_out, xn, xdup, n, Cc, HW, k_dev=None):
+    """solver_step with the guided prediction thresholded at its rank-r magnitude (s_max = inf: no cap); s_out optional, n floats"""
+    arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
+    _check(lib().vd_solver_step_dyn(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(r), float(s_max), ptr(s_out),
+                                    ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_solver_step_dyn")
 
 
 def sumsq(g, out1):

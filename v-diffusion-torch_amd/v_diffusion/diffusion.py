@@ -794,14 +794,22 @@ class GaussianDiffusion:
 
     @torch.inference_mode()
     def p_sample_solver(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=2, spacing="time",
-                        clip_denoised=True, use_graph=False):
+                        clip_denoised=True, use_graph=False, dynamic_quantile=0.995, dynamic_max=None):
         """Deterministic reverse chain with the DPM-Solver++(2M) multistep solver (extension, v_diffusion/solver.py): ``order=2`` adds
         to every DDIM step a correction from the previous step's x0 prediction -- same network calls, second-order error in the log-SNR
         step -- and ``order=1`` is DDIM.  ``steps=None`` = ``sample_timesteps``; ``spacing`` = "time" (tau_i = i/steps) or "logsnr"
         (uniform log-SNR steps).  Only x_T is drawn: the first draw of the seeded generator, the x_T ``p_sample`` starts from.
-        ``use_graph=True`` replays one captured HIP graph per step.  Returns a CPU tensor."""
+        ``use_graph=True`` replays one captured HIP graph per step.  Returns a CPU tensor.
+
+        ``clip_denoised``: True clips each branch's x0 prediction to [-1, 1] before guidance, False clips nothing, and "dynamic"
+        thresholds the GUIDED prediction g per sample (Saharia et al. 2022): s = the magnitude of rank
+        ``threshold_rank(C*H*W, dynamic_quantile)`` of |g|, at least 1 and at most ``dynamic_max`` (None: no cap),
+        g' = clamp(g, -s, s) / s -- inside the step's one launch, eager or captured.  The rank is the "higher" order statistic, a value
+        of the sample itself, not Imagen's interpolated percentile (they differ by at most the gap between neighbouring order statistics).
+        A NaN or infinite s makes that sample NaN or 0 and leaves the others alone."""
         from .solver import p_sample_solver
-        return p_sample_solver(self, denoise_fn, shape, noise, label, device, seed, steps, order, spacing, clip_denoised, use_graph).cpu()
+        return p_sample_solver(self, denoise_fn, shape, noise, label, device, seed, steps, order, spacing, clip_denoised, use_graph,
+                               dynamic_quantile, dynamic_max).cpu()
 
     @torch.inference_mode()
     def p_sample_uint8_async(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, use_ddim=False,

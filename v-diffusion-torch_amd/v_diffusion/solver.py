@@ -15,8 +15,16 @@ What runs where: the weights are fp64 host arithmetic on the fp32-rounded log-SN
 chain has no previous prediction: its row carries c2 rho = 0 and the sampler zero-fills the history image, so one kernel -- and one
 captured graph -- serves every step.  The last row is (c1, c2, c2 rho) = (0, 1, 0): the chain ends on the guided x0 prediction, as every
 sampler of this package does.  MI355X only: CPU tensors raise.
+
+Thresholding.  ``clip_denoised=True`` clips each branch's x0 prediction to [-1, 1] before guidance, so the guided prediction
+g = x_c + w (x_c - x_u) still reaches 1 + 2w.  ``clip_denoised="dynamic"`` is Imagen's dynamic thresholding (Saharia et al. 2022, section
+2.3) of g itself, the companion Lu et al. recommend for this solver: per sample s = the magnitude of rank r of |g|, raised to at least 1
+(and capped at ``dynamic_max``), g' = clamp(g, -s, s) / s, and the update and the history use g'.  r = ``threshold_rank(N, quantile)`` is
+the "higher" order statistic -- a value of the sample, found exactly by a radix select inside the step's one launch
+(vd_solver_step_dyn) -- where Imagen interpolates a percentile; the two differ by at most the gap between neighbouring order statistics.
 """
 import contextlib
+import math
 from collections import OrderedDict
 
 import torch
@@ -110,13 +118,72 @@ def solver_coefs(logsnr_fn, steps, order=2, spacing="time", model_out_type="v", 
     return torch.stack([r for r, _ in rows]).contiguous(), torch.tensor([t for _, t in rows], dtype=F64)
 
 
+def threshold_rank(N, quantile):
+    """the 0-based ascending rank r = min(N - 1, ceil(quantile (N - 1))) of the magnitude dynamic thresholding takes as s, for a sample
+    of N elements and a quantile in (0, 1]: the rank ``numpy.quantile(..., method="higher")`` returns.  fp64 host arithmetic, once."""
+    N, q = int(N), float(quantile)
+    if N < 1:
+        raise ValueError(f"N must be >= 1, got {N}")
+    if not 0.0 < q <= 1.0:
+        raise ValueError(f"quantile must be in (0, 1], got {quantile!r}")
+    return min(N - 1, math.ceil(q * (N - 1)))
+
+
+def _threshold_max(max_value):
+    """s_max as the kernels take it: +Inf for no cap"""
+    s_max = math.inf if max_value is None else float(max_value)
+    if not s_max >= 1.0:
+        raise ValueError(f"the cap of the dynamic threshold must be >= 1, got {max_value!r}")
+    return s_max
+
+
+def _clip_mode(clip_denoised, N, dynamic_quantile, dynamic_max):
+    """True / False (static clip of each branch, or none: vd_solver_step), or ("dynamic", r, s_max) (vd_solver_step_dyn)"""
+    if isinstance(clip_denoised, str):
+        if clip_denoised != "dynamic":
+            raise ValueError(f"clip_denoised must be True, False or 'dynamic', got {clip_denoised!r}")
+        return ("dynamic", threshold_rank(N, dynamic_quantile), _threshold_max(dynamic_max))
+    return bool(clip_denoised)
+
+
+def _step(clip, x, out, hist, k8, mot, cfg, xn, xdup, B, C, HW, k_dev=None):
+    """the step's one launch for a clip mode of ``_clip_mode``"""
+    if isinstance(clip, tuple):
+        _hip.solver_step_dyn(x, out, hist, k8, mot, cfg, clip[1], clip[2], None, xn, xdup, B, C, HW, k_dev=k_dev)
+    else:
+        _hip.solver_step(x, out, hist, k8, mot, cfg, clip, xn, xdup, B, C, HW, k_dev=k_dev)
+
+
+def dynamic_threshold(x, quantile=0.995, max_value=None):
+    """``(x', s)``: dynamic thresholding of a (B, ...) fp32 tensor on the GPU by the solver's rule, per sample over all other
+    dimensions: s = min(max(the magnitude of rank ``threshold_rank(N, quantile)``, 1), max_value), x' = clamp(x, -s, s) / s.  The order
+    statistic is vd_abs_kth_rows' (exact); s has shape (B,).  CPU tensors raise."""
+    if x.dim() < 1 or x.shape[0] < 1 or x.numel() == 0:
+        raise ValueError(f"dynamic_threshold needs a non-empty (B, ...) tensor, got shape {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"dynamic_threshold takes fp32, got {x.dtype}")
+    B = x.shape[0]
+    N = x.numel() // B
+    r, s_max = threshold_rank(N, quantile), _threshold_max(max_value)
+    if not x.is_cuda:
+        raise RuntimeError("dynamic_threshold: the tensor must live on an MI355X (there is no CPU path)")
+    with _device_ctx(x.device):
+        xc = x.contiguous()
+        s = torch.empty((B,), dtype=torch.float32, device=x.device)
+        _hip.abs_kth_rows(xc, B, N, r, s)
+        s = s.clamp(min=1.0, max=s_max)                              # (a NaN stays one)
+        sb = s.reshape((B,) + (1,) * (x.dim() - 1))
+        return torch.maximum(torch.minimum(xc, sb), -sb) / sb, s
+
+
 def _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device):
-    """(graph, state, pinned packs) of one reverse step -- network forward + vd_solver_step on device-resident coefficients -- from
-    this object's own small LRU cache"""
+    """(graph, state, pinned packs) of one reverse step -- network forward + the step's launch on device-resident coefficients -- from
+    this object's own small LRU cache.  ``clip`` is ``_clip_mode``'s: the rank and the cap of the dynamic threshold are launch
+    arguments, not table data, so they are part of the key."""
     B, C = shape[0], shape[1]
     HW = int(shape[2]) * int(shape[3])
     mot = _hip.OUT_TYPES[gd.model_out_type]
-    key = ("solver", id(denoise_fn), tuple(shape), bool(cfg), bool(clip), gd.model_out_type, None if y_in is None else tuple(y_in.shape),
+    key = ("solver", id(denoise_fn), tuple(shape), bool(cfg), clip, gd.model_out_type, None if y_in is None else tuple(y_in.shape),
            hash(tuple(p.data_ptr() for p in net.parameters())) if isinstance(net, torch.nn.Module) else None)
     cache = gd.__dict__.setdefault("_solver_graphs", OrderedDict())
     entry = cache.get(key)
@@ -133,7 +200,7 @@ def _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device):
 
     def body():
         out = denoise_fn(st["xin"], st["t"], st["y"]).to(torch.float32).contiguous()
-        _hip.solver_step(st["x"], out, st["hist"], None, mot, cfg, clip, st["x"], st["xin"] if cfg else None, B, C, HW, k_dev=st["k"])
+        _step(clip, st["x"], out, st["hist"], None, mot, cfg, st["x"], st["xin"] if cfg else None, B, C, HW, k_dev=st["k"])
     side = torch.cuda.Stream(device)
     side.wait_stream(torch.cuda.current_stream(device))
     with torch.cuda.stream(side):                  # warm-up outside capture (lazy initialisation, workspace growth)
@@ -151,16 +218,17 @@ def _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device):
 
 
 def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=2, spacing="time",
-                    clip_denoised=True, use_graph=False):
+                    clip_denoised=True, use_graph=False, dynamic_quantile=0.995, dynamic_max=None):
     """the reverse chain of ``GaussianDiffusion.p_sample_solver`` (see there); returns the final image batch on the device"""
     steps = gd.sample_timesteps if steps is None else int(steps)
     _check(steps, order)
+    shape = tuple(shape)
+    clip = _clip_mode(clip_denoised, int(shape[1]) * int(shape[2]) * int(shape[3]), dynamic_quantile, dynamic_max)
     if gd.model_var_type == "learned":
         raise NotImplementedError("model_var_type='learned'")
     if gd.x0eps_coef:
         raise NotImplementedError("x0eps_coef=True with the multistep solver")
     device = torch.device(gd._default_device(denoise_fn) if device is None else device)
-    shape = tuple(shape)
     with _device_ctx(device):
         generator = None if seed is None else torch.Generator(device).manual_seed(seed)
         if noise is None:
@@ -180,7 +248,7 @@ def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, 
         rows = B * (1 + cfg)
         net = getattr(denoise_fn, "module", denoise_fn)
         if use_graph:
-            graph, st, _ = _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, bool(clip_denoised), device)
+            graph, st, _ = _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device)
             st["x"].copy_(x_t)
             st["hist"].zero_()
             if cfg:
@@ -205,7 +273,7 @@ def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, 
             for k8, t_net in _rows(gd.logsnr_fn, tau, order, gd.model_out_type, gd.w_guide):      # solver_coefs' rows, last one first
                 t_in = torch.full((rows,), t_net, dtype=F64, device=device)
                 out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
-                _hip.solver_step(x_t, out, hist, k8.tolist(), mot, cfg, clip_denoised, x_next, x_in_next, B, C, HW)
+                _step(clip, x_t, out, hist, k8.tolist(), mot, cfg, x_next, x_in_next, B, C, HW)
                 x_t, x_next = x_next, x_t
                 if cfg:
                     x_in, x_in_next = x_in_next, x_in
