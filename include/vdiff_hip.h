@@ -555,6 +555,39 @@ int    vd_fid_accum(const float* x, int64_t n, int32_t d, int64_t ldx, const dou
 int    vd_atb_f64(const double* A, const double* B, double* C, int64_t k, int32_t m, int32_t n, int64_t lda, int64_t ldb, int64_t ldc,
                   void* stream);
 
+/* ------------------------------------------------------------------ KID polynomial-kernel sums and Inception Score (kid.hip)
+ * fp64 from fp32 rows, one fused pass, no n x n buffer, no atomics, every reduction in a fixed order: the same call gives bitwise
+ * identical results.
+ * vd_kid_sums: for subset s let X_s[i] = x[ix[s mx + i]] (row pitch ldx floats) and Y_s[j] = y[iy[s my + j]]; with
+ *   k(a, b) = (gamma <a, b> + coef0)^degree,
+ *   out[s][0] = sum over positions i != j of k(X_s[i], X_s[j]),  out[s][1] = the same over Y_s,
+ *   out[s][2] = sum over all (i, j) of k(X_s[i], Y_s[j]).
+ *   "Diagonal" means equal positions: an index that occurs twice in a subset is legal and its pair is counted.  A null ix (iy)
+ *   means the identity and needs subsets == 1 and mx == nx (my == ny).  The features are widened to fp64 and multiplied on
+ *   v_mfma_f64_16x16x4_f64, so every product is exact; the dot product accumulates over d in index order, gamma s + coef0 is one
+ *   fp64 multiplication and one addition, the power degree - 1 left-to-right multiplications.  One workgroup owns a 64 x 64 tile
+ *   of one Gram of one subset across all of d and writes one partial to ws; XX and YY run the lower triangle of tiles and double
+ *   the off-diagonal partials; a second kernel adds each Gram's partials in a fixed order.
+ *   Domain: d a positive multiple of 16; ldx, ldy >= d and multiples of 4; x, y, out, ws 16-byte aligned; 1 <= subsets <= 65535;
+ *   2 <= mx <= nx, 2 <= my <= ny; 1 <= degree <= 8; ws of vd_kid_ws_bytes(subsets, mx, my) bytes (8 per tile; 0 = bad shape).
+ *   PRECONDITION the library cannot check: every index in ix lies in [0, nx) and every index in iy in [0, ny) -- they are device
+ *   memory, and a row gathered through an index out of range is read out of bounds.  Callers hand over only index arrays whose
+ *   range they have checked on the host (the Python binding builds the device array itself from such a host array).
+ * vd_is_scores: split k = rows [k n / splits, (k + 1) n / splits) (integer division) of logits[n][classes] (row pitch ld floats);
+ *   per row p = softmax in fp64 with the row maximum subtracted; scores[k] = exp(mean_i sum_c p_ic (log p_ic - log pbar_c)), pbar the
+ *   split's mean row; 0 log 0 = 0 (a -inf logit, an underflowed probability, a class without mass in the split).  A NaN logit
+ *   makes its own split's score NaN and no other.  A workgroup walks a fixed chunk of 64 rows of one split and leaves the chunk's
+ *   column sums of p and its sum of p log p in ws; a second kernel adds the chunks in order and finishes each split.
+ *   Domain: classes >= 2 (any; no granule), ld >= classes, 1 <= splits <= 65535, splits <= n <= 2^40, logits 4-byte and scores, ws
+ *   8-byte aligned, ws of vd_is_ws_bytes(n, classes, splits) bytes (0 = bad shape). */
+size_t vd_kid_ws_bytes(int32_t subsets, int32_t mx, int32_t my);
+int    vd_kid_sums(const float* x, int64_t nx, int64_t ldx, const float* y, int64_t ny, int64_t ldy, int32_t d, const int32_t* ix,
+                   const int32_t* iy, int32_t subsets, int32_t mx, int32_t my, double gamma, double coef0, int32_t degree,
+                   double* out /* [subsets][3] */, void* ws, size_t ws_bytes, void* stream);
+size_t vd_is_ws_bytes(int64_t n, int32_t classes, int32_t splits);
+int    vd_is_scores(const float* logits, int64_t n, int32_t classes, int64_t ld, int32_t splits, double* scores /* [splits] */, void* ws,
+                    size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,7 @@ There is NO fallback: a missing library, a CPU tensor or a non-zero return code 
 import ctypes as C
 import os
 
+import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -141,6 +142,10 @@ _SIGNATURES = {
     "vd_fid_shift": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
     "vd_fid_accum": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
     "vd_atb_f64": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _vp]),
+    "vd_kid_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "vd_kid_sums": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _sz, _vp]),
+    "vd_is_ws_bytes": (_sz, [_i64, _i32, _i32]),
+    "vd_is_scores": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
 }
 EXPORTS = tuple(_SIGNATURES)
 # extra entry points of libvdiff_hip_probe.so (built with -DVD_PROBES; tests/probe/*.py load it through VDIFF_HIP_LIB): bound when
@@ -957,3 +962,54 @@ def atb_f64(A, B):
     Cm = torch.empty(m, n, dtype=torch.float64, device=A.device)
     _check(lib().vd_atb_f64(pa, pb, Cm.data_ptr(), k, m, n, lda, ldb, n, stream()), "vd_atb_f64")
     return Cm
+
+
+# ----------------------------------------------------------------------------------------------- KID sums / Inception Score (kid.hip)
+def kid_indices(idx, n, what="indices"):
+    """a host index array as kid_sums takes it: a numpy int32 array [subsets, m] with every value in [0, n).  Raises ValueError
+    otherwise; touches no device.  The kernels gather rows through these values unchecked (include/vdiff_hip.h), so this check is
+    the only thing between a bad index and an out-of-bounds read."""
+    if not isinstance(idx, np.ndarray) or idx.dtype != np.int32 or idx.ndim != 2 or idx.shape[0] < 1 or idx.shape[1] < 1:
+        raise ValueError(f"{what} must be a numpy int32 array of shape [subsets, subset_size], got "
+                         f"{getattr(idx, 'dtype', type(idx).__name__)} {getattr(idx, 'shape', ())}")
+    lo, hi = int(idx.min()), int(idx.max())
+    if lo < 0 or hi >= n:
+        raise ValueError(f"{what} must lie in [0, {n}): found {lo if lo < 0 else hi}")
+    return np.ascontiguousarray(idx)
+
+
+def kid_sums(x, y, ix=None, iy=None, degree=3, gamma=None, coef0=1.0):
+    """fp64 device tensor [subsets, 3]: per subset the polynomial-kernel sums (XX over positions i != j, YY likewise, XY over all
+    pairs) of the rows x[ix[s]] and y[iy[s]] of the fp32 device features x[nx, d], y[ny, d] (include/vdiff_hip.h).  ix, iy: host
+    int32 numpy arrays [subsets, m], or None for all rows of that set in order (then the other side is None or has one subset).
+    Their shape and range are checked here, on the host, and the device copies are made here: there is no other way to hand
+    indices to the kernel.  gamma=None means 1 / d."""
+    px, nx, d, ldx = _dev_rows(x, torch.float32, "features")
+    py, ny, dy, ldy = _dev_rows(y, torch.float32, "features")
+    if dy != d or x.device != y.device:
+        raise HipError(f"the two feature sets need one feature length and one device: {tuple(x.shape)} vs {tuple(y.shape)}")
+    if ix is not None:
+        ix = kid_indices(ix, nx, "ix")
+    if iy is not None:
+        iy = kid_indices(iy, ny, "iy")
+    subsets = ix.shape[0] if ix is not None else (iy.shape[0] if iy is not None else 1)
+    if iy is not None and iy.shape[0] != subsets:
+        raise ValueError(f"ix and iy hold different numbers of subsets: {subsets} vs {iy.shape[0]}")
+    mx = ix.shape[1] if ix is not None else nx
+    my = iy.shape[1] if iy is not None else ny
+    dix = torch.from_numpy(ix).to(x.device) if ix is not None else None
+    diy = torch.from_numpy(iy).to(x.device) if iy is not None else None
+    out = torch.empty(subsets, 3, dtype=torch.float64, device=x.device)
+    ws = workspace(lib().vd_kid_ws_bytes(subsets, mx, my), x.device, "kid")
+    _check(lib().vd_kid_sums(px, nx, ldx, py, ny, ldy, d, ptr(dix), ptr(diy), subsets, mx, my, 1.0 / d if gamma is None else float(gamma),
+                             float(coef0), int(degree), out.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream()), "vd_kid_sums")
+    return out
+
+
+def is_scores(logits, splits):
+    """fp64 device tensor [splits]: the Inception Score of each split of the fp32 device logits [n, classes] (include/vdiff_hip.h)"""
+    pl, n, classes, ld = _dev_rows(logits, torch.float32, "logits")
+    scores = torch.empty(max(int(splits), 1), dtype=torch.float64, device=logits.device)
+    ws = workspace(lib().vd_is_ws_bytes(n, classes, int(splits)), logits.device, "is")
+    _check(lib().vd_is_scores(pl, n, classes, ld, int(splits), scores.data_ptr(), ws.data_ptr(), ws.numel() * 4, stream()), "vd_is_scores")
+    return scores

@@ -5,7 +5,9 @@ csrc/metrics.hip.  The FID names (InceptionStatistics, get_precomputed, calc_fd)
 checkout named by ``VDIFF_REFERENCE_ROOT`` (``v_diffusion_ref.metrics``) like the control-plane names of the parent package, so
 the reference's ``eval.py --metrics pr fid`` runs unchanged with this package first on ``sys.path``.  With ``VDIFF_NATIVE_FID=1``
 in the environment they resolve to this package's own fid_score module (fp64 statistics and products on the kernels of
-csrc/fid.hip) instead and are always listed.  ``import v_diffusion`` does not import this subpackage."""
+csrc/fid.hip) instead and are always listed.  The Kernel Inception Distance and the Inception Score, which the reference does not
+have, live in the submodules ``kid_score`` and ``inception_score`` (kernels of csrc/kid.hip) and are not star-imported.
+``import v_diffusion`` does not import this subpackage."""
 import importlib
 import os
 
