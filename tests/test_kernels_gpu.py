@@ -438,7 +438,10 @@ def test_plain_resample_and_backward(H, rs):
 
 @pytest.mark.parametrize("geom", [(4, 128, 16, 16), (3, 192, 64, 64)])
 def test_dropout_mask_is_consistent_and_bernoulli(H, geom):
-    """(64x64: the SPLIT single-pass backward regenerates the mask per sibling workgroup from the element index of its pixel range)"""
+    """The mask here is read off the kernel's own forward (tests/test_gn_dropout_gpu.py replays it from the generator instead, and runs the
+    SPLIT, wide-slab and 1024-thread forms).  Backward forms of these two shapes: (4,128,16,16) the plain single-pass kernel, 256 threads,
+    8 pixels per thread, non-temporal 32-channel slabs; (3,192,64,64) has 24-channel slabs (96-byte rows), which stay on the two-pass
+    form (chan_reduce_kernel<1> + gn_bwd_apply_kernel) -- not SPLIT."""
     (nimg, Cc, Hh, Ww), p = geom, 0.2
     x = rnd(nimg, Cc, Hh, Ww, seed=1) + 3.0            # keep activations away from 0
     gamma, beta = torch.ones(Cc), torch.zeros(Cc)
@@ -457,14 +460,24 @@ def test_dropout_mask_is_consistent_and_bernoulli(H, geom):
     assert ((y2 != 0) != keep).float().mean().item() > 0.2           # a different seed gives a different mask
     # replay the mask through the torch reference: backward must use the same mask
     mask = from_nhwc(keep.float() / (1 - p), Cc).double()
-    xs = x.double().requires_grad_(True)
     dy = rnd(nimg, Cc, Hh, Ww, seed=2)
-    (F.group_norm(xs, 32, gamma.double(), beta.double(), 1e-6) * mask).backward(dy.double())
+
+    def run(dt):
+        xs, g, b_ = (v.to(dt).requires_grad_(True) for v in (x, gamma, beta))
+        (F.group_norm(xs, 32, g, b_, 1e-6) * mask.to(dt)).backward(dy.to(dt))
+        return xs, g.grad, b_.grad
+    (xs, dg64, db64), (_, dg32, db32) = run(torch.float64), run(torch.float32)
     dx = torch.empty(nimg, Hh, Ww, Cc, device=DEV)
     dg, db = torch.empty(Cc, device=DEV), torch.empty(Cc, device=DEV)
     H.gn_apply_bwd(nhwc(dy), Cc, xd, Cc, coef, gamma.to(DEV), beta.to(DEV), None, 0, p, 1234, 0, None, 0, dx, Cc, False, None,
                    dg, db, False, nimg, Hh, Ww, Cc)
+    torch.cuda.synchronize()
+    k = H.lib().vd_gn_bwd_last_kernel()
+    assert k == {(128, 256): 1080256, (192, 4096): -1}[(Cc, Hh * Ww)], k
     close(from_nhwc(dx, Cc), xs.grad, None, floor=2e-5, name="dropout bwd")
+    # dgamma / dbeta under the yardstick of test_gn_forward_backward: 6 x the error of torch's own fp32 autograd + 5e-6 of the scale
+    close(dg, dg64, dg32, slack=6, floor=5e-6, name="dropout dgamma")
+    close(db, db64, db32, slack=6, floor=5e-6, name="dropout dbeta")
 
 
 # ------------------------------------------------------------------------------------------------ small kernels

@@ -3,11 +3,15 @@
 
 Stated tolerance: UNet output max-abs <= 2e-5 (+ rtol 1e-4), gradients rel-L2 <= 1e-4."""
 import os
+import sys
 from unittest import mock
 
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import dropout_ref                                                # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -337,6 +341,73 @@ def test_training_mode_dropout_runs_and_differs(vd):
     model.eval()
     with torch.no_grad():
         assert not torch.equal(model(x, t, y), a.detach())
+
+
+class _Masks(dict):
+    """drop_masks of oracle.unet_ref.unet_forward that remembers which keys were looked up"""
+
+    def __init__(self, *a):
+        super().__init__(*a)
+        self.asked = []
+
+    def get(self, key, default=None):
+        self.asked.append(key)
+        return super().get(key, default)
+
+
+@pytest.mark.parametrize("name", ["tinyA", "tinyC"])
+def test_tiny_unet_with_dropout_vs_oracle(vd, name):
+    """Training mode with drop_rate = 0.3 against the oracle, forward and every parameter gradient, inside the bounds of
+    test_tiny_unet_vs_golden_and_oracle (output 2e-5; gradients L2 <= 1e-4 |ref| + 1e-6 gmax).  The keep masks are not read off the
+    engine: each residual block's mask is replayed on the host (tests/dropout_ref.py) from the seed the engine draws -- base seed from
+    torch's default generator plus the block's seed index -- at the block's OUTPUT resolution (the second norm runs after the
+    resampling in front of conv1), and handed to the oracle keyed by the block's residual prefix."""
+    from oracle import unet_ref, detrand
+    from oracle.cases import TINY, make_inputs
+    from v_diffusion import _hip
+    case = TINY[name]
+    cfg, B, R, label = dict(case["cfg"], drop_rate=0.3), case["B"], case["R"], case["label"]
+    model, sd = _build(vd, cfg, train=True)
+    eng = model.engine()
+    x, t, y = make_inputs(cfg, B, R, label)
+    gout = detrand.normal("gout", (B, cfg["out_channels"], R, R), 1)
+    torch.manual_seed(4321)
+    base_seed = int(torch.empty((), dtype=torch.int64).random_().item())       # the draw of UNetEngine.forward
+    torch.manual_seed(4321)
+    out = model(x.to(DEV), t.to(DEV), None if y is None else y.to(DEV))
+    (out * gout.to(DEV)).sum().backward()
+    torch.cuda.synchronize()
+    masks = _Masks()
+    res_blocks = [b for b in eng.plan if b.res is not None]
+    for b in res_blocks:
+        Ho, Wo = _hip._resampled(*eng._res_of(b.level, R, R), b.rs)
+        m = dropout_ref.keep_scale(base_seed + b.seed, cfg["drop_rate"], B, Ho * Wo, b.cout)
+        assert 0.5 < (m != 0).mean() < 0.9                       # (p = 0.3)
+        masks[b.res_prefix] = torch.from_numpy(m).reshape(B, Ho, Wo, b.cout).permute(0, 3, 1, 2).contiguous()
+    assert len(masks) == len(res_blocks) == sum(1 for k in sd if k.endswith(".norm2.weight"))
+    sdo = {k: v.clone().requires_grad_(True) for k, v in sd.items()}
+    oo = unet_ref.unet_forward(sdo, cfg, x, t, y, train=True, drop_masks=masks)
+    assert sorted(masks.asked) == sorted(masks.keys()), "the oracle did not look up exactly the replayed masks"
+    (oo * gout).sum().backward()
+    err = (out.detach().cpu() - oo.detach()).abs().max().item()
+    print(f"{name}: output max-abs error {err:.3e}")
+    assert err <= 2e-5, f"output differs from the oracle by {err:.3e}"
+    gmax = max(v.grad.double().norm().item() for v in sdo.values())
+    worst = 0.0
+    for k, p in model.named_parameters():
+        ref = sdo[k].grad.double()
+        e = (p.grad.double().cpu() - ref).norm().item()
+        worst = max(worst, e / (1e-4 * ref.norm().item() + 1e-6 * gmax))
+        assert e <= 1e-4 * ref.norm().item() + 1e-6 * gmax, f"{k}: L2 error {e:.3e} vs |grad| {ref.norm().item():.3e}"
+    print(f"{name}: worst gradient err/tol {worst:.3f}")
+    # the masks matter: the same network without them is far outside the bound
+    with torch.no_grad():
+        plain = unet_ref.unet_forward(sd, cfg, x, t, y)
+        assert (plain - oo.detach()).abs().max().item() > 1e-3
+        model.eval()
+        oe = model(x.to(DEV), t.to(DEV), None if y is None else y.to(DEV))
+        ee = (oe.cpu() - plain).abs().max().item()
+        assert ee <= 2e-5, f"eval-mode output differs from the oracle by {ee:.3e}"
 
 
 def test_rejects_cpu_tensors(vd):
