@@ -19,6 +19,12 @@
 // both for "16 lanes read the same chunk of 16 rows" (first products) and "16 lanes read the 16 chunks of one row" (second).
 // Per 64-key tile and wave (D = 64): 128 MFMAs forward, 192 dQ, 256 dK/dV against ~35 VALU instructions per lane for the softmax.
 // Everything is fixed-order (no atomics): bitwise reproducible.
+//
+// One logit, three kernels.  All of them form the raw dot product s = q . k on UNSCALED fragments, the k-slots in the same order, so s is
+// the same bits in the forward, in dQ and in dK/dV; the factor sl2 = scale * log2(e) enters only inside the fused multiply-add of the
+// exponent, exp2(fma(s, sl2, -m)) / exp2(fma(s, sl2, -lse)), which rounds once.  P recomputed in the backward therefore differs from the
+// forward's only by the rounding of lse itself.  (Folding sl2 into q in the forward and dQ but into k in dK/dV rounded the two s apart by
+// several ulp(s): at logits of +-190 that put 5 x torch's fp32 error into dV -- tests/test_attn_stress_gpu.py, family `peaked`.)
 #include "common.h"
 
 namespace {
@@ -101,7 +107,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs p) {
     const float sl2 = p.scale * LOG2E;
     f32x4 qf[NC];
 #pragma unroll
-    for (int c4 = 0; c4 < NC; ++c4) qf[c4] = *reinterpret_cast<const f32x4*>(qb + (long long)(q0 + li) * p.ld + 16 * c4 + 4 * lq) * sl2;
+    for (int c4 = 0; c4 < NC; ++c4) qf[c4] = *reinterpret_cast<const f32x4*>(qb + (long long)(q0 + li) * p.ld + 16 * c4 + 4 * lq);
     TileLoader<D> ldr;
     ldr.init(wave, lane, p.ld);
     const int nt = p.L / BK;
@@ -139,7 +145,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs p) {
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
             for (int r = 0; r < 4; ++r) mx = fmaxf(mx, s[blk][r]);
-        mx = red_lq_max(mx);
+        mx = red_lq_max(mx) * sl2;                                  // sl2 > 0: the maximum commutes with the scaling
         const float mn = fmaxf(m, mx);
         const float alpha = __builtin_amdgcn_exp2f(m - mn);
         m = mn;
@@ -147,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_kernel(const AttnArgs p) {
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) { s[blk][r] = __builtin_amdgcn_exp2f(s[blk][r] - mn); ps += s[blk][r]; }
+            for (int r = 0; r < 4; ++r) { s[blk][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[blk][r], sl2, -mn)); ps += s[blk][r]; }
         lsum = lsum * alpha + ps;
 #pragma unroll
         for (int g = 0; g < NG; ++g)
@@ -203,7 +209,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
         const float* drow = p.dout + (row0 + q0 + li) * p.lddo + h * D;
 #pragma unroll
         for (int c4 = 0; c4 < NC; ++c4) {
-            qf[c4] = *reinterpret_cast<const f32x4*>(qb + (long long)(q0 + li) * p.ld + 16 * c4 + 4 * lq) * sl2;
+            qf[c4] = *reinterpret_cast<const f32x4*>(qb + (long long)(q0 + li) * p.ld + 16 * c4 + 4 * lq);
             dof[c4] = *reinterpret_cast<const f32x4*>(drow + 16 * c4 + 4 * lq);
             const f32x4 of = *reinterpret_cast<const f32x4*>(orow + 16 * c4 + 4 * lq);
 #pragma unroll
@@ -251,7 +257,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(const AttnArgs p) {
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) s[blk][r] = __builtin_amdgcn_exp2f(s[blk][r] - lse) * (dp[blk][r] - dl);
+            for (int r = 0; r < 4; ++r) s[blk][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[blk][r], sl2, -lse)) * (dp[blk][r] - dl);
 #pragma unroll
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
@@ -297,7 +303,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
     f32x4 kf[NC], vf[NC];
 #pragma unroll
     for (int c4 = 0; c4 < NC; ++c4) {
-        kf[c4] = *reinterpret_cast<const f32x4*>(kb + (long long)(k0 + li) * p.ld + 16 * c4 + 4 * lq) * sl2;
+        kf[c4] = *reinterpret_cast<const f32x4*>(kb + (long long)(k0 + li) * p.ld + 16 * c4 + 4 * lq);
         vf[c4] = *reinterpret_cast<const f32x4*>(vb + (long long)(k0 + li) * p.ld + 16 * c4 + 4 * lq);
     }
     TileLoader<D> ldq, ldo;
@@ -346,7 +352,7 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(const AttnArgs p) {
         for (int blk = 0; blk < NB; ++blk)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                s[blk][r] = __builtin_amdgcn_exp2f(s[blk][r] - lse4[blk][r]);     // P
+                s[blk][r] = __builtin_amdgcn_exp2f(__builtin_fmaf(s[blk][r], sl2, -lse4[blk][r]));     // P
                 dp[blk][r] = s[blk][r] * (dp[blk][r] - dl4[blk][r]);               // dS / scale
             }
 #pragma unroll
