@@ -492,6 +492,34 @@ int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, float* kth,
 int vd_solver_step_dyn(const float* xt, const float* out, float* hist, const float* k, const float* k_dev,
                        int32_t model_out_type, int32_t cfg, int64_t r, float s_max, float* s_out,
                        float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* one reverse step of RePaint inpainting (Lugmayr et al. 2022) in log-SNR terms, ONE launch: vd_sample_step for the unknown region, a
+ * draw from q(x_s | x_known) for the known region, and their merge by the mask.  xt, noise, known, knoise, xn: n images (NCHW); out:
+ * n*(1+cfg) images, cond/uncond interleaved when cfg, 2C channels for a "both" network; mask: n x mask_c x HW floats in [0, 1] with
+ * mask_c = 1 (shared by the channels) or C, 1 = keep the known image; xdup (optional, cfg only): 2n images.
+ * k: 10 floats, host (k) or device (k_dev), exactly one of the two as in vd_sample_step: k[0..7] = vd_sample_step's
+ * {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3}, k[8], k[9] = {ak, bk}, the alpha and sigma of the state the step lands on ((1, 0) for
+ * the last step, which returns a prediction).  Evaluation order, all in fp32, per element:
+ *   x0h  = clip?(a0*xt + b0x*out (+ b0e*out_eps))           per branch
+ *   mean = last_step ? x0h : c1*xt + c2*x0h + c3*out
+ *   v    = cfg ? mean_c + w_guide*(mean_c - mean_u) : mean_c
+ *   u    = v + noise_scale*noise                            (u = v when noise is null)   -- vd_sample_step's value, same expressions
+ *   kn   = ak*known + bk*knoise                             (kn = ak*known when knoise is null)
+ *   xn   = m == 1 ? kn : m == 0 ? u : m*kn + (1 - m)*u
+ *   xdup = xn on rows 2b and 2b+1                           (the next guided network input)
+ * The two ends of the mask are selections, not products: a NaN or Inf of the branch not chosen does not reach xn.  With the host form,
+ * a null noise needs k[5] == 0 and a null knoise k[9] == 0.  xn may alias xt (each thread reads all it needs before it writes).  No
+ * workspace, no LDS, no waiting on another workgroup; HIP-graph capturable with k_dev.  Any C*HW; 64-bit element offsets; dwordx4
+ * accesses when C*HW is a multiple of 4, all bases are 16-byte aligned and, for mask_c = 1, HW is a multiple of 4 (a vector then
+ * straddles neither two samples, nor the two halves of a "both" output, nor two channels of the shared mask), scalar otherwise. */
+int vd_inpaint_step(const float* xt, const float* out, const float* noise, const float* known, const float* mask, const float* knoise,
+                    const float* k, const float* k_dev, int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip,
+                    int32_t mask_c, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* the forward transition q(x_t | x_s) of any length in one launch: xn = a*x + b*noise over n rows of N floats, k = {a, b} host or k_dev
+ * device, exactly one of the two.  For s < t: a = alpha_t/alpha_s, b^2 = sigma_t^2 (1 - e^(logsnr_t - logsnr_s)) (v_diffusion.jump_coefs):
+ * a jump of j grid steps is one Gaussian draw, not j.  xdup (optional): xn on rows 2b and 2b+1, the next guided network input.  xn may
+ * alias x.  Access forms as above: dwordx4 when N is a multiple of 4 and all bases are 16-byte aligned, scalar otherwise. */
+int vd_forward_jump(const float* x, const float* noise, const float* k, const float* k_dev, float* xn, float* xdup, int32_t n, int64_t N,
+                    void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */

@@ -3,7 +3,8 @@
 //   train_loss (mse) forward/backward  diffusion.py:466-490,520-541 ; flat_mean functions.py:102-104
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
-//   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form: no counterpart in the reference
+//   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
+//   jump: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 #include "common.h"
 
@@ -596,6 +597,100 @@ __global__ __launch_bounds__(KTH_THREADS) void solver_step_dyn_kernel(const Solv
     }
 }
 
+// ---- RePaint inpainting (Lugmayr et al. 2022) in log-SNR terms: sample_step_kernel's reverse step for the unknown region, a draw from
+// q(x_s | x_known) for the known one, and their merge by the mask, in one launch.  k[10] = sample_step_kernel's eight
+// {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3} and {ak, bk}, the alpha and sigma of the state the step lands on.  Evaluation order,
+// every operation in fp32, u sample_step_kernel's expressions term by term:
+//   x0h = a0*xt + b0x*o (+ b0e*o_eps), clipped when asked, per branch;   mean = last ? x0h : c1*xt + c2*x0h + c3*o
+//   v = cfg ? mean_c + w*(mean_c - mean_u) : mean_c;   u = v + noise_scale*noise  (when noise is given)
+//   kn = ak*known + bk*knoise  (ak*known when knoise is null)
+//   xn = m == 1 ? kn : m == 0 ? u : m*kn + (1 - m)*u;   xdup rows 2b, 2b+1 <- xn
+// The two ends of the mask SELECT: a NaN or Inf of the branch not chosen does not reach xn.  full = the mask has C channels (else one,
+// shared by the sample's channels: a vector of V elements must then lie inside one channel, HW % V == 0).
+// Each thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
+// The wide and the scalar form must give the same bits (a caller's buffers decide between them), so the expressions are written once,
+// with contraction off and the fused operations spelled out.
+__device__ __forceinline__ float inp_mean(float a0, float b0x, float b0e, float c1, float c2, float c3, bool both, bool clip, bool last,
+                                          float z, float o, float oe) {
+#pragma clang fp contract(off)
+    float x0h = __builtin_fmaf(b0x, o, a0 * z) + (both ? b0e * oe : 0.f);
+    if (clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
+    return last ? x0h : __builtin_fmaf(c3, o, __builtin_fmaf(c2, x0h, c1 * z));
+}
+
+__device__ __forceinline__ float inp_merge(float m, float kn, float u) {
+#pragma clang fp contract(off)
+    return m == 1.f ? kn : (m == 0.f ? u : __builtin_fmaf(1.f - m, u, m * kn));
+}
+
+__device__ __forceinline__ float inp_axpby(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(b, y, a * x);
+}
+
+struct InpaintArgs {
+    const float* xt; const float* out; const float* noise; const float* known; const float* mask; const float* knoise;
+    float k[10]; const float* kdev; int type, cfg, last, clip, full; float* xn; float* xdup; int n; long long N, HW;
+};
+
+template <int V>
+__global__ void inpaint_step_kernel(const InpaintArgs p) {
+    const long long N = p.N, total = (long long)p.n * N / V;
+    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
+    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
+    const float ak = kp[8], bk = kp[9];
+    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float z[V], kw[V], m[V], nz[V], kz[V], mean[2][V], xn[V];
+        ldv<V>(p.xt + e, z);
+        ldv<V>(p.known + e, kw);
+        ldv<V>(p.mask + (p.full ? e : b * p.HW + i % p.HW), m);
+        if (p.noise) ldv<V>(p.noise + e, nz);
+        if (p.knoise) ldv<V>(p.knoise + e, kz);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
+            if (u >= mul) break;
+            const float* ob = p.out + (b * mul + u) * Co * N + i;
+            float o[V], oe[V];
+            ldv<V>(ob, o);
+            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                mean[u][j] = inp_mean(a0, b0x, b0e, c1, c2, c3, p.type == OUT_BOTH, p.clip, p.last, z[j], o[j],
+                                      p.type == OUT_BOTH ? oe[j] : 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            float v = p.cfg ? dyn_guide(w, mean[0][j], mean[1][j]) : mean[0][j];
+            if (p.noise) v = inp_axpby(1.f, v, nscale, nz[j]);
+            const float kn = p.knoise ? inp_axpby(ak, kw[j], bk, kz[j]) : ak * kw[j];
+            xn[j] = inp_merge(m[j], kn, v);
+        }
+        stv<V>(p.xn + e, xn);
+        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+    }
+}
+
+// the forward transition q(x_t | x_s) of any length, xn = a*x + b*noise; xdup (optional) rows 2b, 2b+1 <- xn.  A thread reads its V
+// elements before it writes them, so xn may alias x.
+template <int V>
+__global__ void forward_jump_kernel(const float* x, const float* noise, const float* k, float a, float b, float* xn, float* xdup, int n,
+                                    long long N) {
+    const long long total = (long long)n * N / V;
+    if (k) { a = k[0]; b = k[1]; }                 // device-resident coefficients keep the launch HIP-graph replayable
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, s = e / N, i = e % N;
+        float z[V], nz[V], r[V];
+        ldv<V>(x + e, z);
+        ldv<V>(noise + e, nz);
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = inp_axpby(a, z[j], b, nz[j]);
+        stv<V>(xn + e, r);
+        if (xdup) { stv<V>(xdup + 2 * s * N + i, r); stv<V>(xdup + (2 * s + 1) * N + i, r); }
+    }
+}
+
 }  // namespace
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
@@ -771,5 +866,47 @@ extern "C" int vd_solver_step_dyn(const float* xt, const float* out, float* hist
     else
         hipLaunchKernelGGL(solver_step_dyn_kernel<1>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, p);
     VD_LAUNCH_CHECK("solver_step_dyn_kernel");
+    return 0;
+}
+
+extern "C" int vd_inpaint_step(const float* xt, const float* out, const float* noise, const float* known, const float* mask,
+                               const float* knoise, const float* k, const float* k_dev, int32_t type, int32_t cfg, int32_t last_step,
+                               int32_t clip, int32_t mask_c, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_inpaint_step: pass the coefficients either as host k or as device k_dev");
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_inpaint_step: bad model_out_type %d", type);
+    VD_REQUIRE(xt && out && known && mask && xn, "vd_inpaint_step: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_inpaint_step: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_REQUIRE(mask_c == 1 || mask_c == C, "vd_inpaint_step: mask_c must be 1 or C (mask_c=%d, C=%d)", mask_c, C);
+    VD_REQUIRE(!xdup || cfg, "vd_inpaint_step: the duplicated state is the guided network's input (cfg = 1)");
+    VD_REQUIRE(noise != nullptr || k_dev != nullptr || k[5] == 0.f, "vd_inpaint_step: noise required when the noise scale is non-zero");
+    VD_REQUIRE(knoise != nullptr || k_dev != nullptr || k[9] == 0.f, "vd_inpaint_step: knoise required when bk is non-zero");
+    const long long N = (long long)C * HW;
+    InpaintArgs p = {};
+    p.xt = xt; p.out = out; p.noise = noise; p.known = known; p.mask = mask; p.knoise = knoise; p.kdev = k_dev;
+    for (int i = 0; i < 10; ++i) p.k[i] = k ? k[i] : 0.f;
+    p.type = type; p.cfg = cfg ? 1 : 0; p.last = last_step ? 1 : 0; p.clip = clip ? 1 : 0; p.full = mask_c == C ? 1 : 0;
+    p.xn = xn; p.xdup = xdup; p.n = n; p.N = N; p.HW = HW;
+    // a one-channel mask is indexed per channel: a vector must not straddle two channels
+    if (N % 4 == 0 && (p.full || HW % 4 == 0) && all_aligned16(xt, out, noise, known, mask, knoise, xn, xdup))
+        hipLaunchKernelGGL(inpaint_step_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(inpaint_step_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("inpaint_step_kernel");
+    return 0;
+}
+
+extern "C" int vd_forward_jump(const float* x, const float* noise, const float* k, const float* k_dev, float* xn, float* xdup, int32_t n,
+                               int64_t N, void* stream) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_forward_jump: pass the coefficients either as host k or as device k_dev");
+    VD_REQUIRE(x && noise && xn, "vd_forward_jump: null pointer");
+    VD_REQUIRE(n > 0 && N > 0, "vd_forward_jump: empty batch or image (n=%d, N=%lld)", n, (long long)N);
+    const float a = k ? k[0] : 0.f, b = k ? k[1] : 0.f;
+    if (N % 4 == 0 && all_aligned16(x, noise, xn, xdup))
+        hipLaunchKernelGGL(forward_jump_kernel<4>, dim3(grid_for(n * (long long)N / 4)), dim3(256), 0, (hipStream_t)stream, x, noise, k_dev,
+                           a, b, xn, xdup, n, (long long)N);
+    else
+        hipLaunchKernelGGL(forward_jump_kernel<1>, dim3(grid_for(n * (long long)N)), dim3(256), 0, (hipStream_t)stream, x, noise, k_dev, a,
+                           b, xn, xdup, n, (long long)N);
+    VD_LAUNCH_CHECK("forward_jump_kernel");
     return 0;
 }

@@ -128,6 +128,9 @@ _SIGNATURES = {
     "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_abs_kth_rows": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
     "vd_solver_step_dyn": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_inpaint_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
+                                  _vp]),
+    "vd_forward_jump": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -834,6 +837,20 @@ def solver_step_dyn(xt, out, hist, k8, mot, cfg, r, s_max, s_out, xn, xdup, n, C
     arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
     _check(lib().vd_solver_step_dyn(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(r), float(s_max), ptr(s_out),
                                     ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_solver_step_dyn")
+
+
+def inpaint_step(xt, out, noise, known, mask, knoise, k10, mot, cfg, last, clip, mask_c, xn, xdup, n, Cc, HW, k_dev=None):
+    """sample_step merged with ak*known + bk*knoise by the mask (n x mask_c x HW floats, mask_c 1 or C; 1 keeps the known image).
+    k10: sample_step's 8 host floats + (ak, bk), or None with k_dev = device tensor of 10 floats (graph-replayable form)"""
+    arr = None if k10 is None else (_f32 * 10)(*[float(v) for v in k10])
+    _check(lib().vd_inpaint_step(ptr(xt), ptr(out), ptr(noise), ptr(known), ptr(mask), ptr(knoise), arr, ptr(k_dev), mot, int(cfg),
+                                 int(last), int(clip), int(mask_c), ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_inpaint_step")
+
+
+def forward_jump(x, noise, k2, xn, xdup, n, N, k_dev=None):
+    """xn = a*x + b*noise over n rows of N floats (xdup optional: 2n interleaved rows); k2 = (a, b) host floats, or None with k_dev"""
+    arr = None if k2 is None else (_f32 * 2)(*[float(v) for v in k2])
+    _check(lib().vd_forward_jump(ptr(x), ptr(noise), arr, ptr(k_dev), ptr(xn), ptr(xdup), n, int(N), stream()), "vd_forward_jump")
 
 
 def sumsq(g, out1):

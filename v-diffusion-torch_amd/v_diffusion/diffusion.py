@@ -812,6 +812,24 @@ class GaussianDiffusion:
                                dynamic_quantile, dynamic_max).cpu()
 
     @torch.inference_mode()
+    def p_sample_inpaint(self, denoise_fn, known, mask, label=None, device=None, seed=None, use_ddim=False, jump_length=1, resamplings=1,
+                         start=None, clip_denoised=True):
+        """Reverse chain conditioned on a given image (extension, v_diffusion/inpaint.py): RePaint inpainting (Lugmayr et al. 2022) and,
+        with ``start``, SDEdit-style image-to-image.  ``known`` is (B, C, H, W) on the GPU; ``mask`` is (B or 1, 1 or C, H, W), float in
+        [0, 1] or bool, 1 = keep ``known``.  Every reverse step is one network call and one fused launch: the ordinary posterior step
+        (DDPM, or DDIM with ``use_ddim``) for the unknown region, alpha_s known + sigma_s eps for the known one, merged by the mask.  With
+        ``resamplings`` > 1 the chain jumps forward by ``jump_length`` grid steps at every resampling point and denoises again
+        (``resampling_schedule``); a jump is one draw and one launch.  The chain ends on the x0 prediction of the step to index 0, where
+        the known region (mask == 1) equals ``known`` exactly.  ``start=k`` (1 <= k <= sample_timesteps) begins at
+        x_k = alpha_k known + sigma_k eps everywhere instead of pure noise and runs ``resampling_schedule(k, ...)``; an all-zero mask then
+        gives pure image-to-image.  Draws, from one generator seeded with ``seed``, always made and in this order: the initial state;
+        then per transition a reverse step draws the posterior noise and then the known region's noise, a jump draws one tensor.
+        Returns a CPU tensor."""
+        from .inpaint import p_sample_inpaint
+        return p_sample_inpaint(self, denoise_fn, known, mask, label, device, seed, use_ddim, jump_length, resamplings, start,
+                                clip_denoised).cpu()
+
+    @torch.inference_mode()
     def p_sample_uint8_async(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, use_ddim=False,
                              use_graph=None):
         """The sampler plumbing of reference generate.py:143-150 without its host round trips: the chain
