@@ -520,6 +520,39 @@ int vd_inpaint_step(const float* xt, const float* out, const float* noise, const
  * alias x.  Access forms as above: dwordx4 when N is a multiple of 4 and all bases are 16-byte aligned, scalar otherwise. */
 int vd_forward_jump(const float* x, const float* noise, const float* k, const float* k_dev, float* xn, float* xdup, int32_t n, int64_t N,
                     void* stream);
+/* one step of DDPM noise-space inversion (Huberman-Spiegelglas et al. 2024, "An Edit Friendly DDPM Noise Space") in log-SNR terms, ONE
+ * launch after the step's network call: the next state is drawn from the image itself and the noise map that makes the ordinary
+ * reverse step land on it is extracted.  xt (the state x_{i+1} the network saw), x0, eps, xs, z: n images (NCHW); out: n*(1+cfg)
+ * images, cond/uncond interleaved when cfg, 2C channels for a "both" network; xdup (optional, cfg only): 2n images.
+ * k: vd_inpaint_step's 10 floats, host (k) or device (k_dev), exactly one of the two: k[0..7] = vd_sample_step's
+ * {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3} of the step that lands on index i, k[8], k[9] = {ak, bk} = the alpha and sigma of
+ * index i.  Evaluation order, all in fp32, per element:
+ *   x0h  = clip?(a0*xt + b0x*out (+ b0e*out_eps))           per branch
+ *   mean = last_step ? x0h : c1*xt + c2*x0h + c3*out
+ *   v    = cfg ? mean_c + w_guide*(mean_c - mean_u) : mean_c                 -- vd_inpaint_step's expressions, same fused operations
+ *   xs   = ak*x0 + bk*eps                                   (xs = ak*x0 when eps is null)   -- vd_inpaint_step's kn, bit for bit
+ *   z    = (xs - v) / noise_scale                           one fp32 subtraction, one IEEE fp32 division
+ *   xdup = xs on rows 2b and 2b+1                           (the next guided network input)
+ * vd_sample_step on (xt, out, noise = z) then returns xs to rounding.  The step to index 0 has no noise of its own: pass last_step = 1,
+ * k[5] = 1, (ak, bk) = (1, 0) and a null eps, and z is the residual x0 - x0h.  xs depends on neither xt nor out: a NaN of the network
+ * stays in that sample's z.  With the host form k[5] must be finite and non-zero and a null eps needs k[9] == 0.  xs may alias xt (each
+ * thread reads all it needs before it writes); z is a buffer of its own.  No workspace, no LDS, no waiting on another workgroup;
+ * HIP-graph capturable with k_dev.  Any C*HW; 64-bit element offsets; dwordx4 accesses when C*HW is a multiple of 4 and all bases are
+ * 16-byte aligned, scalar otherwise; the two forms give the same bits. */
+int vd_noise_extract(const float* xt, const float* out, const float* x0, const float* eps, const float* k, const float* k_dev,
+                     int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip, float* xs, float* z, float* xdup, int32_t n,
+                     int32_t C, int32_t HW, void* stream);
+/* spherical interpolation of n pairs of rows of N floats, ONE launch: out[r] = wa*a[r] + wb*b[r].  The fraction f is one host float
+ * (frac) for all rows or n device floats (frac_dev), exactly one of the two.  One workgroup (1024 threads) owns one row and waits on no
+ * other.  Pass 1: <a,b>, |a|^2, |b|^2 in fp64, thread t adding the products of its accesses t, t + 1024, ... in order, the lanes of a
+ * wave by a fixed butterfly, the 16 wave sums in wave order -- no atomics, the same bits on every call.  Then, in fp64 on one thread:
+ *   c = <a,b> / (|a| |b|) clamped to [-1, 1],  w = acos(c),  (wa, wb) = (sin((1-f) w), sin(f w)) / sin(w), each rounded to fp32 once;
+ *   (wa, wb) = (1 - f, f) when sin(w) < 1e-6 (parallel or antiparallel rows) or a norm is 0.
+ * Pass 2 re-reads the rows: out = fma(wb, b, wa*a) in fp32.  A NaN makes its own row NaN and no other.  w_out (optional, n x 2 floats)
+ * receives (wa, wb).  out may alias neither input.  Access forms as above: dwordx4 when N is a multiple of 4 and a, b, out are 16-byte
+ * aligned, scalar otherwise (the two forms add in different orders and may differ in the last bit of a weight). */
+int vd_slerp_rows(const float* a, const float* b, const float* frac, const float* frac_dev, float* out, float* w_out, int32_t n, int64_t N,
+                  void* stream);
 
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */

@@ -4,7 +4,7 @@
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
 //   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
-//   jump: no counterpart in the reference
+//   jump, the noise-map extraction of DDPM inversion and spherical interpolation: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 #include "common.h"
 
@@ -691,6 +691,113 @@ __global__ void forward_jump_kernel(const float* x, const float* noise, const fl
     }
 }
 
+// ---- DDPM noise-space inversion (Huberman-Spiegelglas et al. 2024) in log-SNR terms: given the state xt = x_{i+1} and the network's
+// output there, draw the next state from the image itself, xs = ak*x0 + bk*eps, and extract the noise map the ordinary reverse step
+// would have needed to land on it, z = (xs - v)/noise_scale with v sample_step_kernel's guided mean.  k[10] = inpaint_step_kernel's ten.
+// Evaluation order, every operation in fp32, mean and v inpaint_step_kernel's expressions (inp_mean, dyn_guide):
+//   xs = ak*x0 + bk*eps  (ak*x0 when eps is null): inpaint_step_kernel's known-region value, same expression, same bits
+//   z  = (xs - v) / k[5]   one subtraction, one IEEE division;   xdup rows 2b, 2b+1 <- xs
+// xs does not depend on xt or out: a NaN of the network stays in z.  Each thread reads all it needs of its V elements before it writes
+// any of them, so xs may alias xt.  Written once with contraction off, so the wide and the scalar form give the same bits.
+__device__ __forceinline__ float inv_extract(float xs, float v, float nscale) {
+#pragma clang fp contract(off)
+    return (xs - v) / nscale;
+}
+
+struct ExtractArgs {
+    const float* xt; const float* out; const float* x0; const float* eps; float k[10]; const float* kdev;
+    int type, cfg, last, clip; float* xs; float* z; float* xdup; int n; long long N;
+};
+
+template <int V>
+__global__ void noise_extract_kernel(const ExtractArgs p) {
+    const long long N = p.N, total = (long long)p.n * N / V;
+    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
+    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
+    const float ak = kp[8], bk = kp[9];
+    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float zt[V], im[V], ez[V], mean[2][V], xs[V], zz[V];
+        ldv<V>(p.xt + e, zt);
+        ldv<V>(p.x0 + e, im);
+        if (p.eps) ldv<V>(p.eps + e, ez);
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
+            if (u >= mul) break;
+            const float* ob = p.out + (b * mul + u) * Co * N + i;
+            float o[V], oe[V];
+            ldv<V>(ob, o);
+            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                mean[u][j] = inp_mean(a0, b0x, b0e, c1, c2, c3, p.type == OUT_BOTH, p.clip, p.last, zt[j], o[j],
+                                      p.type == OUT_BOTH ? oe[j] : 0.f);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float v = p.cfg ? dyn_guide(w, mean[0][j], mean[1][j]) : mean[0][j];
+            xs[j] = p.eps ? inp_axpby(ak, im[j], bk, ez[j]) : ak * im[j];
+            zz[j] = inv_extract(xs[j], v, nscale);
+        }
+        stv<V>(p.xs + e, xs);
+        stv<V>(p.z + e, zz);
+        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xs); stv<V>(p.xdup + (2 * b + 1) * N + i, xs); }
+    }
+}
+
+// ---- spherical interpolation of two latents per sample: out = wa*a + wb*b with (wa, wb) = (sin((1-f) w), sin(f w)) / sin w, w the
+// angle between the rows.  ONE WORKGROUP OWNS ONE ROW, as in abs_kth_rows_kernel, and waits on no other.  Pass 1: thread t adds the
+// products of its accesses t, t + 1024, ... (element order inside an access) to three fp64 sums <a,b>, |a|^2, |b|^2; the 64 lanes of a
+// wave are added by a fixed butterfly and the 16 wave sums in wave order: no atomics, the same bits on every call.  Thread 0 forms the
+// weights in fp64 and rounds each to fp32 once.  Pass 2 re-reads the rows (they stay in L2): out = fma(wb, b, wa*a), spelled out.
+enum { SLERP_THREADS = 1024 };
+
+template <int V>
+__global__ __launch_bounds__(SLERP_THREADS) void slerp_rows_kernel(const float* a, const float* b, const float* frac, float frac_all,
+                                                                   float* out, float* w_out, long long N) {
+    __shared__ double sh[SLERP_THREADS / 64];
+    __shared__ float wsh[2];
+    const long long row = (long long)blockIdx.x * N;
+    const float* ar = a + row;
+    const float* br = b + row;
+    double dab = 0.0, daa = 0.0, dbb = 0.0;
+    for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)SLERP_THREADS * V) {
+        float x[V], y[V];
+        ldv<V>(ar + i, x);
+        ldv<V>(br + i, y);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const double xd = x[j], yd = y[j];
+            dab = fma(xd, yd, dab); daa = fma(xd, xd, daa); dbb = fma(yd, yd, dbb);
+        }
+    }
+    dab = block_sum(dab, sh); daa = block_sum(daa, sh); dbb = block_sum(dbb, sh);
+    if (threadIdx.x == 0) {
+        const double f = frac ? (double)frac[blockIdx.x] : (double)frac_all;
+        double wa = 1.0 - f, wb = f;                         // the lerp weights: a zero row, or rows (anti)parallel to within sin w < 1e-6
+        if (!(daa == 0.0) && !(dbb == 0.0)) {
+            double c = dab / (sqrt(daa) * sqrt(dbb));
+            c = c < -1.0 ? -1.0 : (c > 1.0 ? 1.0 : c);       // a NaN passes through, into this row's weights only
+            const double om = acos(c), s = sin(om);
+            if (!(s < 1e-6)) { wa = sin((1.0 - f) * om) / s; wb = sin(f * om) / s; }
+        }
+        wsh[0] = (float)wa; wsh[1] = (float)wb;
+        if (w_out) { w_out[2 * blockIdx.x] = wsh[0]; w_out[2 * blockIdx.x + 1] = wsh[1]; }
+    }
+    __syncthreads();
+    const float wa = wsh[0], wb = wsh[1];
+    float* orow = out + row;
+    for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)SLERP_THREADS * V) {
+        float x[V], y[V], r[V];
+        ldv<V>(ar + i, x);
+        ldv<V>(br + i, y);
+#pragma unroll
+        for (int j = 0; j < V; ++j) r[j] = inp_axpby(wa, x[j], wb, y[j]);
+        stv<V>(orow + i, r);
+    }
+}
+
 }  // namespace
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
@@ -908,5 +1015,48 @@ extern "C" int vd_forward_jump(const float* x, const float* noise, const float* 
         hipLaunchKernelGGL(forward_jump_kernel<1>, dim3(grid_for(n * (long long)N)), dim3(256), 0, (hipStream_t)stream, x, noise, k_dev, a,
                            b, xn, xdup, n, (long long)N);
     VD_LAUNCH_CHECK("forward_jump_kernel");
+    return 0;
+}
+
+extern "C" int vd_noise_extract(const float* xt, const float* out, const float* x0, const float* eps, const float* k, const float* k_dev,
+                                int32_t type, int32_t cfg, int32_t last_step, int32_t clip, float* xs, float* z, float* xdup, int32_t n,
+                                int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_noise_extract: pass the coefficients either as host k or as device k_dev");
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_noise_extract: bad model_out_type %d", type);
+    VD_REQUIRE(xt && out && x0 && xs && z, "vd_noise_extract: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_noise_extract: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_REQUIRE(!xdup || cfg, "vd_noise_extract: the duplicated state is the guided network's input (cfg = 1)");
+    VD_REQUIRE(z != xs && z != xt && z != x0 && z != eps && xs != x0 && xs != eps, "vd_noise_extract: z is a buffer of its own, and xs may alias xt only");
+    VD_REQUIRE(k_dev != nullptr || (std::isfinite(k[5]) && k[5] != 0.f), "vd_noise_extract: the noise scale k[5] must be finite and non-zero, got %g",
+               (double)k[5]);
+    VD_REQUIRE(eps != nullptr || k_dev != nullptr || k[9] == 0.f, "vd_noise_extract: eps required when bk is non-zero");
+    const long long N = (long long)C * HW;
+    ExtractArgs p = {};
+    p.xt = xt; p.out = out; p.x0 = x0; p.eps = eps; p.kdev = k_dev;
+    for (int i = 0; i < 10; ++i) p.k[i] = k ? k[i] : 0.f;
+    p.type = type; p.cfg = cfg ? 1 : 0; p.last = last_step ? 1 : 0; p.clip = clip ? 1 : 0;
+    p.xs = xs; p.z = z; p.xdup = xdup; p.n = n; p.N = N;
+    if (N % 4 == 0 && all_aligned16(xt, out, x0, eps, xs, z, xdup))
+        hipLaunchKernelGGL(noise_extract_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
+    else
+        hipLaunchKernelGGL(noise_extract_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("noise_extract_kernel");
+    return 0;
+}
+
+extern "C" int vd_slerp_rows(const float* a, const float* b, const float* frac, const float* frac_dev, float* out, float* w_out, int32_t n,
+                             int64_t N, void* stream) {
+    VD_REQUIRE((frac != nullptr) != (frac_dev != nullptr), "vd_slerp_rows: pass the fraction either as one host float or as n device floats");
+    VD_REQUIRE(a && b && out, "vd_slerp_rows: null pointer");
+    VD_REQUIRE(n > 0 && N > 0, "vd_slerp_rows: empty batch or row (n=%d, N=%lld)", n, (long long)N);
+    VD_REQUIRE(out != a && out != b, "vd_slerp_rows: out may alias neither input (the rows are read twice)");
+    const float f = frac ? frac[0] : 0.f;
+    if (N % 4 == 0 && all_aligned16(a, b, out))
+        hipLaunchKernelGGL(slerp_rows_kernel<4>, dim3(n), dim3(SLERP_THREADS), 0, (hipStream_t)stream, a, b, frac_dev, f, out, w_out,
+                           (long long)N);
+    else
+        hipLaunchKernelGGL(slerp_rows_kernel<1>, dim3(n), dim3(SLERP_THREADS), 0, (hipStream_t)stream, a, b, frac_dev, f, out, w_out,
+                           (long long)N);
+    VD_LAUNCH_CHECK("slerp_rows_kernel");
     return 0;
 }

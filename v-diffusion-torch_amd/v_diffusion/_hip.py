@@ -131,6 +131,8 @@ _SIGNATURES = {
     "vd_inpaint_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
                                   _vp]),
     "vd_forward_jump": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
+    "vd_noise_extract": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_slerp_rows": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -851,6 +853,21 @@ def forward_jump(x, noise, k2, xn, xdup, n, N, k_dev=None):
     """xn = a*x + b*noise over n rows of N floats (xdup optional: 2n interleaved rows); k2 = (a, b) host floats, or None with k_dev"""
     arr = None if k2 is None else (_f32 * 2)(*[float(v) for v in k2])
     _check(lib().vd_forward_jump(ptr(x), ptr(noise), arr, ptr(k_dev), ptr(xn), ptr(xdup), n, int(N), stream()), "vd_forward_jump")
+
+
+def noise_extract(xt, out, x0, eps, k10, mot, cfg, last, clip, xs, z, xdup, n, Cc, HW, k_dev=None):
+    """xs = ak*x0 + bk*eps and the noise map z = (xs - guided mean of sample_step)/k[5] (vd_noise_extract).  k10: inpaint_step's ten host
+    floats, or None with k_dev = device tensor of 10 floats; eps may be None when bk = 0; xs may alias xt"""
+    arr = None if k10 is None else (_f32 * 10)(*[float(v) for v in k10])
+    _check(lib().vd_noise_extract(ptr(xt), ptr(out), ptr(x0), ptr(eps), arr, ptr(k_dev), mot, int(cfg), int(last), int(clip), ptr(xs),
+                                  ptr(z), ptr(xdup), n, Cc, HW, stream()), "vd_noise_extract")
+
+
+def slerp_rows(a, b, frac, out, w_out, n, N, frac_dev=None):
+    """out = spherical interpolation of n pairs of rows of N floats (vd_slerp_rows); frac = one host float, or None with frac_dev =
+    device tensor of n floats; w_out optional, n x 2 floats"""
+    arr = None if frac is None else (_f32 * 1)(float(frac))
+    _check(lib().vd_slerp_rows(ptr(a), ptr(b), arr, ptr(frac_dev), ptr(out), ptr(w_out), n, int(N), stream()), "vd_slerp_rows")
 
 
 def sumsq(g, out1):

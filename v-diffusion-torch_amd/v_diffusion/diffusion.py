@@ -830,6 +830,48 @@ class GaussianDiffusion:
                                 clip_denoised).cpu()
 
     @torch.inference_mode()
+    def p_invert_noise(self, denoise_fn, x_0, label=None, device=None, seed=None, start=None, clip_denoised=True):
+        """DDPM noise-space inversion of a given image batch (extension, v_diffusion/invert.py; Huberman-Spiegelglas et al. 2024):
+        ``(x_start, maps)`` such that ``p_sample_replay(denoise_fn, x_start, maps, label)`` returns ``x_0``, for any network.  With
+        Tc = ``start`` or ``sample_timesteps``: x_i = alpha_i x_0 + sigma_i eps_i for i = Tc ... 1 with independent eps_i
+        ((alpha_i, sigma_i) = ``known_coefs``), ``x_start`` = x_Tc, and ``maps[i]`` = (x_i - mu_i(x_{i+1})) / noise_scale_i, the noise the
+        DDPM step landing on i needs to arrive at x_i from x_{i+1} (mu_i = the guided posterior mean of the ordinary step).  The step to
+        index 0 has no noise: ``maps[0]`` = x_0 - x0_hat(x_1), the residual, with scale 1.  Each step is one network call and one fused
+        launch (vd_noise_extract).  ``x_0`` is (B, C, H, W) on the GPU.  Both results stay on the GPU, fp32; ``maps`` has shape
+        (Tc, B, C, H, W), is allocated once and takes Tc*B*C*H*W*4 bytes -- 1.5 GB at T = 1000 for 128 x 3 x 32 x 32.
+        Draws, from one ``torch.Generator(device).manual_seed(seed)``, each of the image shape, in this order: eps_Tc, eps_{Tc-1}, ...,
+        eps_1.  Refused: ``model_var_type="learned"``, ``x0eps_coef=True``, a step >= 1 whose noise scale is 0, CPU tensors, ``start``
+        outside [1, sample_timesteps].  There is no ``use_ddim``: eta = 0 has no noise to extract (``p_encode`` is the way back there)."""
+        from .invert import p_invert_noise
+        return p_invert_noise(self, denoise_fn, x_0, label, device, seed, start, clip_denoised)
+
+    @torch.inference_mode()
+    def p_sample_replay(self, denoise_fn, x_start, maps, label=None, device=None, clip_denoised=True):
+        """The DDPM chain from index ``maps.shape[0]`` down to 0 over GIVEN noise (extension, v_diffusion/invert.py): each step is one
+        network call and vd_sample_step with ``noise = maps[i]``; on the last step the noise-scale slot is 1.0 instead of 0.0, so
+        ``maps[0]`` is added to the final prediction.  With the maps, network and label of ``p_invert_noise`` it returns that x_0; with
+        another label, or on another ``GaussianDiffusion`` over the same schedule with another ``w_guide``, it is the edit;
+        ``maps[0] = 0`` drops the residual; with the draws of ``p_sample(seed=..., use_ddim=False)`` as maps (and ``maps[0] = 0``) it is that
+        ``p_sample`` bit for bit.  ``maps`` must have shape (Tc,) + ``x_start.shape`` with 1 <= Tc <= sample_timesteps.  Nothing is drawn.
+        Returns a CPU tensor."""
+        from .invert import p_sample_replay
+        return p_sample_replay(self, denoise_fn, x_start, maps, label, device, clip_denoised).cpu()
+
+    @torch.inference_mode()
+    def p_encode(self, denoise_fn, x_0, label=None, device=None, steps=None, order=1, spacing="time", clip_denoised=False, stop=None):
+        """DDIM (``order=1``) / DPM-Solver++(2M) (``order=2``) encoding (extension, v_diffusion/invert.py): the probability-flow ODE run
+        upwards from the image, tau_0 -> ... -> tau_stop on the grid of ``p_sample_solver`` (``steps=None`` = ``sample_timesteps``,
+        ``spacing`` as there, ``stop=None`` = ``steps``: the full latent).  Each step is one network call at the CURRENT state and
+        vd_solver_step on the ascending row of ``encode_coefs``.  ``p_sample_solver(noise=latent, steps=..., order=...)`` decodes; the
+        round trip is exact only in the limit of small steps (measured on a solvable problem: FINDINGS.md).  Deterministic, nothing is
+        drawn.  Returns the latent ON THE GPU (it feeds ``slerp`` and ``p_sample_solver``).
+        Rounding: the first row leaves logsnr_max, where sigma is tiny, with c1 = sigma_1/sigma_0 in the hundreds (cosine +-20 schedule, time spacing:
+        4.3e3 at 8 steps, 6.9e2 at 50, 1.4e2 at 250, 36 at 1000); the fp32 rounding of the image there, 2^-24 |x| per element, enters the
+        next state as c1 * 2^-24 * |x| absolute -- 4e-5 |x| at 50 steps -- next to a signal of order sigma_1."""
+        from .invert import p_encode
+        return p_encode(self, denoise_fn, x_0, label, device, steps, order, spacing, clip_denoised, stop)
+
+    @torch.inference_mode()
     def p_sample_uint8_async(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, use_ddim=False,
                              use_graph=None):
         """The sampler plumbing of reference generate.py:143-150 without its host round trips: the chain
