@@ -210,41 +210,147 @@ __global__ void bpd_bwd_kernel(const BpdArgs p, const float* use_kl, const float
     }
 }
 
-struct StepArgs {
-    const float* xt; const float* out; const float* noise; float k[8]; const float* kdev;
-    int type, cfg, last, clip; float* xn; float* xdup; int n, C; long long HW;
-};
-
-// one reverse step for a batch sharing the step index; x0_hat = a0*xt + b0x*o (+ b0e*o_eps), mean = c1*xt + c2*x0_hat + c3*o
-// (c3 = k[7]: the weight of the raw network output, for the posterior over (eps, x0) of an eps-network without clipping, where the
-// reference takes the output itself as eps, diffusion.py:338-347 -- rebuilding it as (xt - alpha*x0_hat)/sigma cancels)
-__global__ void sample_step_kernel(const StepArgs p) {
-    const long long N = (long long)p.C * p.HW, total = (long long)p.n * N;
-    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
-    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
-    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 * p.C : p.C;
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const long long b = idx / N, i = idx % N;
-        const float xt = p.xt[idx];
-        float mean[2];
-        for (int u = 0; u < mul; ++u) {                      // rows interleaved cond, uncond (diffusion.py:369-372)
-            const float* ob = p.out + (b * mul + u) * Co * p.HW;
-            float x0h = a0 * xt + b0x * ob[i] + (p.type == OUT_BOTH ? b0e * ob[N + i] : 0.f);
-            if (p.clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
-            mean[u] = p.last ? x0h : c1 * xt + c2 * x0h + c3 * ob[i];
-        }
-        float v = p.cfg ? mean[0] + w * (mean[0] - mean[1]) : mean[0];
-        if (p.noise) v += nscale * p.noise[idx];
-        p.xn[idx] = v;
-        if (p.xdup) { p.xdup[(2 * b) * N + i] = v; p.xdup[(2 * b + 1) * N + i] = v; }
-    }
-}
-
 inline int grid_for(long long total) {
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
     return (int)(g < 1 ? 1 : g);
+}
+
+// V = floats per lane and access: 4 (dwordx4) when C*HW is a multiple of 4 and every base is 16-byte aligned -- a vector then never
+// straddles two samples or the two halves of a "both" output -- else 1.
+template <int V> __device__ __forceinline__ void ldv(const float* p, float (&r)[V]) {
+    if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
+    else r[0] = *p;
+}
+
+template <int V> __device__ __forceinline__ void stv(float* p, const float (&r)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else *p = r[0];
+}
+
+// elements [i, i + V) of row b of xn <- r, and of rows 2b, 2b+1 of xdup (optional: the next guided network input)
+template <int V> __device__ __forceinline__ void st_dup(float* xn, float* xdup, long long b, long long N, long long i, const float (&r)[V]) {
+    stv<V>(xn + b * N + i, r);
+    if (xdup) { stv<V>(xdup + 2 * b * N + i, r); stv<V>(xdup + (2 * b + 1) * N + i, r); }
+}
+
+// ---- what the reverse-step kernels share: the product sampler's step, the DPM-Solver++ step and its thresholded form, the RePaint step
+// and the noise extraction of DDPM inversion.  Each takes the state xt (n rows of N = C*HW floats) and a network output of n*(1+cfg)
+// rows, cond and uncond interleaved (diffusion.py:369-372), of N floats or, for "both", 2N; each forms a value per branch, guides it,
+// and writes xn and (optional) xdup.  The coefficients come as host floats copied into the kernel argument or, to keep the launch
+// HIP-graph replayable, as a device pointer.
+struct Coefs { float k[10]; const float* kdev; };
+
+__device__ __forceinline__ const float* coefs(const Coefs& c) { return c.kdev ? c.kdev : c.k; }
+
+struct StepCommon {
+    const float* xt; const float* out; Coefs c; int type, cfg, last, clip; float* xn; float* xdup; int n; long long N;
+};
+
+// Every expression of these kernels is written once, with contraction off and the fused operations spelled out: the bits of a step are
+// a property of this text, not of the compiler.  The wide and the scalar form of a kernel (a caller's buffers decide between them)
+// agree bit for bit, the thresholded solver step with s_max = 1 and no guidance is the solver step with clip = 1, the selection passes
+// of the thresholded step see the bits its final pass sees, and noise extraction forms the mean the RePaint step forms.
+__device__ __forceinline__ float x0_hat(float a0, float b0x, float b0e, bool both, float z, float o, float oe) {
+#pragma clang fp contract(off)
+    const float e = both ? b0e * oe : 0.f;
+    return __builtin_fmaf(b0x, o, a0 * z) + e;
+}
+
+__device__ __forceinline__ float guide(float w, float xc, float xu) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(w, xc - xu, xc);
+}
+
+__device__ __forceinline__ float solver_update(float c1, float c2, float c2r, float z, float g, float h) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(c2r, g - h, __builtin_fmaf(c1, z, c2 * g));
+}
+
+// The posterior mean c1*z + c2*x0h + c3*o has two groupings, and they differ in the last bit: mean_plain is the product sampler's
+// (three products, two sums, nothing fused), mean_fused the RePaint step's and the noise extraction's.  Both stay: merging them
+// changes the bits of one side's seeded chains.
+__device__ __forceinline__ float mean_plain(float c1, float c2, float c3, float z, float x0h, float o) {
+#pragma clang fp contract(off)
+    return c3 * o + (c1 * z + c2 * x0h);
+}
+
+__device__ __forceinline__ float mean_fused(float c1, float c2, float c3, float z, float x0h, float o) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(c3, o, __builtin_fmaf(c2, x0h, c1 * z));
+}
+
+__device__ __forceinline__ float axpby(float a, float x, float b, float y) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(b, y, a * x);
+}
+
+// per branch: the x0 prediction a0*z + b0x*o (+ b0e*o_eps), clipped to [-1, 1] when asked
+struct PredX0 {
+    float a0, b0x, b0e; bool both, clip;
+    __device__ __forceinline__ float operator()(float z, float o, float oe) const {
+        const float x0h = x0_hat(a0, b0x, b0e, both, z, o, oe);
+        return clip ? fminf(fmaxf(x0h, -1.f), 1.f) : x0h;
+    }
+};
+
+// per branch: the step mean c1*z + c2*x0_hat + c3*o in one of its two groupings, or x0_hat itself on the last step
+// (c3 = k[7]: the weight of the raw network output, for the posterior over (eps, x0) of an eps-network without clipping, where the
+// reference takes the output itself as eps, diffusion.py:338-347 -- rebuilding it as (xt - alpha*x0_hat)/sigma cancels)
+template <bool FUSED> struct StepMean {
+    PredX0 x0; float c1, c2, c3; bool last;
+    __device__ __forceinline__ float operator()(float z, float o, float oe) const {
+        const float x0h = x0(z, o, oe);
+        if (last) return x0h;
+        return FUSED ? mean_fused(c1, c2, c3, z, x0h, o) : mean_plain(c1, c2, c3, z, x0h, o);
+    }
+};
+
+// k = {a0, b0x, b0e, c1, c2, noise scale | c2*rho, w_guide, c3 [, ak, bk]}
+__device__ __forceinline__ PredX0 pred_x0(const StepCommon& s, const float* k) { return {k[0], k[1], k[2], s.type == OUT_BOTH, s.clip != 0}; }
+
+template <bool FUSED> __device__ __forceinline__ StepMean<FUSED> step_mean(const StepCommon& s, const float* k) {
+    return {pred_x0(s, k), k[3], k[4], k[7], s.last != 0};
+}
+
+// g[j] = f(z[j], o, o_eps) of sample b's cond row, guided by the same of its uncond row when cfg, for the elements [i, i + V)
+template <int V, class F>
+__device__ __forceinline__ void guided(const StepCommon& s, long long b, long long i, float w, const float (&z)[V], const F& f,
+                                       float (&g)[V]) {
+    const bool both = s.type == OUT_BOTH;
+    const long long N = s.N, row = both ? 2 * N : N;
+    const float* oc = s.out + b * (1 + s.cfg) * row + i;
+    float o[V], oe[V] = {};
+    ldv<V>(oc, o);
+    if (both) ldv<V>(oc + N, oe);
+#pragma unroll
+    for (int j = 0; j < V; ++j) g[j] = f(z[j], o[j], oe[j]);
+    if (s.cfg) {
+        ldv<V>(oc + row, o);
+        if (both) ldv<V>(oc + row + N, oe);
+#pragma unroll
+        for (int j = 0; j < V; ++j) g[j] = guide(w, g[j], f(z[j], o[j], oe[j]));
+    }
+}
+
+struct StepArgs { StepCommon s; const float* noise; };
+
+// one reverse step for a batch sharing the step index: xn = guided mean_plain + k[5]*noise (when noise is given).  Scalar.
+__global__ void sample_step_kernel(const StepArgs p) {
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N;
+    const float* k = coefs(s.c);
+    const StepMean<false> f = step_mean<false>(s, k);
+    const float nscale = k[5], w = k[6];
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const long long b = idx / N, i = idx % N;
+        float z[1], v[1];
+        ldv<1>(s.xt + idx, z);
+        guided<1>(s, b, i, w, z, f, v);
+        if (p.noise) v[0] = axpby(1.f, v[0], nscale, p.noise[idx]);
+        st_dup<1>(s.xn, s.xdup, b, N, i, v);
+    }
 }
 
 // ---- progressive distillation (Salimans & Ho 2022): two DDIM steps of a teacher on the 2N grid become the regression target of one
@@ -257,19 +363,7 @@ inline int grid_for(long long total) {
 // was predicted from, (a0 - 1)*z + b0x*o (+ b0e*o_eps).  The residual x_student - x_tilde is assembled from the differences alone:
 // at high log-SNR all predictions sit within 1e-3 ... 1e-5 of z_t, and through the direct forms one fp32 ulp of a weight near 1 is
 // up to 1e-3 of the residual (the a0 - 1 slot of the bound-term kernels, for the same reason).
-// V = floats per lane and access: 4 (dwordx4) when C*HW is a multiple of 4 and every base is 16-byte aligned -- a vector then never
-// straddles two samples or the two halves of a "both" output -- else 1.
 enum { DK = 20 };
-
-template <int V> __device__ __forceinline__ void ldv(const float* p, float (&r)[V]) {
-    if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
-    else r[0] = *p;
-}
-
-template <int V> __device__ __forceinline__ void stv(float* p, const float (&r)[V]) {
-    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
-    else *p = r[0];
-}
 
 // guided x0 prediction x of elements [i, i + V) of sample b, and d = x - z in difference form, from a network output of n*(1+cfg)
 // rows (cond, uncond interleaved): the arithmetic of sample_step_kernel's last step -- clip each prediction, then x_c + w (x_c - x_u)
@@ -392,53 +486,32 @@ __global__ void distill_loss_bwd_kernel(const float* resid, const float* coef, c
     }
 }
 
-template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
-
 // ---- DPM-Solver++(2M) (Lu et al. 2022, data-prediction form): one reverse step of the probability-flow ODE in log-SNR time from the
 // guided x0 prediction g of this step and the one of the step before (hist).  k[8] = {a0, b0x, b0e, c1, c2, c2*rho, w_guide, 0} with
 // c1, c2 the DDIM weights of the step and rho = h / (2 h_prev); c2*rho = 0 gives the DDIM step, (c1, c2, c2*rho) = (0, 1, 0) the
 // guided x0 prediction itself (the last row of a chain).  Evaluation order, every operation in fp32:
-//   x_u = a0*xt + b0x*o (+ b0e*o_eps), clipped when asked, per branch;   g = x_c + w*(x_c - x_u)  (g = x_c without cfg)
+//   g = the guided PredX0 of the two branches (each clipped when asked)
 //   xn  = c1*xt + c2*g + c2rho*(g - hist);   hist <- g;   xdup rows 2b, 2b+1 <- xn
 // Each thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
-struct SolverArgs {
-    const float* xt; const float* out; float* hist; float k[8]; const float* kdev;
-    int type, cfg, clip; float* xn; float* xdup; int n; long long N;
-};
+struct SolverArgs { StepCommon s; float* hist; };
 
 template <int V>
 __global__ void solver_step_kernel(const SolverArgs p) {
-    const long long N = p.N, total = (long long)p.n * N / V;
-    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
-    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], c2r = kp[5], w = kp[6];
-    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = coefs(s.c);
+    const PredX0 f = pred_x0(s, k);
+    const float c1 = k[3], c2 = k[4], c2r = k[5], w = k[6];
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long e = idx * V, b = e / N, i = e % N;
-        float z[V], h[V], pr[2][V], g[V], xn[V];
-        ldv<V>(p.xt + e, z);
+        float z[V], h[V], g[V], xn[V];
+        ldv<V>(s.xt + e, z);
         ldv<V>(p.hist + e, h);
+        guided<V>(s, b, i, w, z, f, g);
 #pragma unroll
-        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
-            if (u >= mul) break;
-            const float* ob = p.out + (b * mul + u) * Co * N + i;
-            float o[V], oe[V];
-            ldv<V>(ob, o);
-            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
-#pragma unroll
-            for (int j = 0; j < V; ++j) {
-                float x0h = a0 * z[j] + b0x * o[j] + (p.type == OUT_BOTH ? b0e * oe[j] : 0.f);
-                if (p.clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
-                pr[u][j] = x0h;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < V; ++j) {
-            g[j] = p.cfg ? pr[0][j] + w * (pr[0][j] - pr[1][j]) : pr[0][j];
-            xn[j] = c1 * z[j] + c2 * g[j] + c2r * (g[j] - h[j]);
-        }
+        for (int j = 0; j < V; ++j) xn[j] = solver_update(c1, c2, c2r, z[j], g[j], h[j]);
         stv<V>(p.hist + e, g);
-        stv<V>(p.xn + e, xn);
-        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+        st_dup<V>(s.xn, s.xdup, b, N, i, xn);
     }
 }
 
@@ -521,154 +594,80 @@ __global__ __launch_bounds__(KTH_THREADS) void abs_kth_rows_kernel(const float* 
     if (threadIdx.x == 0) kth[blockIdx.x] = __uint_as_float(key);
 }
 
-// The selection passes and the final pass must see the same bits of g, and with s_max = 1 and no guidance the step must reproduce
-// solver_step_kernel(clip = 1) bit for bit: the three expressions below are written once, with contraction off and the fused
-// operations spelled out -- the grouping the compiler gives solver_step_kernel's expressions.
-__device__ __forceinline__ float dyn_x0(float a0, float b0x, float b0e, bool both, float z, float o, float oe) {
-#pragma clang fp contract(off)
-    const float e = both ? b0e * oe : 0.f;
-    return __builtin_fmaf(b0x, o, a0 * z) + e;
-}
-
-__device__ __forceinline__ float dyn_guide(float w, float xc, float xu) {
-#pragma clang fp contract(off)
-    return __builtin_fmaf(w, xc - xu, xc);
-}
-
-__device__ __forceinline__ float dyn_update(float c1, float c2, float c2r, float z, float g, float h) {
-#pragma clang fp contract(off)
-    return __builtin_fmaf(c2r, g - h, __builtin_fmaf(c1, z, c2 * g));
-}
-
-// unclipped guided x0 prediction g of elements [i, i + V) of one sample, and the state z it was predicted from
-template <int V> struct GuidedProd {
-    const float* xt; const float* oc; const float* ou;       // the sample's row of xt, its cond and uncond output rows (ou unused without cfg)
-    long long N; bool both, cfg; float a0, b0x, b0e, w;
-    __device__ __forceinline__ void eval(long long i, float (&z)[V], float (&g)[V]) const {
-        float o[V], oe[V] = {};
-        ldv<V>(xt + i, z);
-        ldv<V>(oc + i, o);
-        if (both) ldv<V>(oc + N + i, oe);
-#pragma unroll
-        for (int j = 0; j < V; ++j) g[j] = dyn_x0(a0, b0x, b0e, both, z[j], o[j], oe[j]);
-        if (cfg) {
-            ldv<V>(ou + i, o);
-            if (both) ldv<V>(ou + N + i, oe);
-#pragma unroll
-            for (int j = 0; j < V; ++j) g[j] = dyn_guide(w, g[j], dyn_x0(a0, b0x, b0e, both, z[j], o[j], oe[j]));
-        }
-    }
-    __device__ __forceinline__ void operator()(long long i, float (&g)[V]) const { float z[V]; eval(i, z, g); }
-};
-
-struct SolverDynArgs {
-    const float* xt; const float* out; float* hist; float k[8]; const float* kdev;
-    int type, cfg; uint32_t r; float s_max; float* s_out; float* xn; float* xdup; int n; long long N;
-};
+struct SolverDynArgs { StepCommon s; float* hist; uint32_t r; float s_max; float* s_out; };
 
 // one workgroup per sample.  No thread writes before every thread has left the last selection pass (its closing barrier), and a
 // thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
 template <int V>
 __global__ __launch_bounds__(KTH_THREADS) void solver_step_dyn_kernel(const SolverDynArgs p) {
     __shared__ KthShared sh;
-    const long long b = blockIdx.x, N = p.N;
-    const float* kp = p.kdev ? p.kdev : p.k;
-    const float c1 = kp[3], c2 = kp[4], c2r = kp[5];
-    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
-    const GuidedProd<V> prod = {p.xt + b * N, p.out + (b * mul) * Co * N, p.out + (b * mul + p.cfg) * Co * N, N,
-                                p.type == OUT_BOTH, p.cfg != 0, kp[0], kp[1], kp[2], kp[6]};
+    const StepCommon& s = p.s;
+    const long long b = blockIdx.x, N = s.N;
+    const float* k = coefs(s.c);
+    const PredX0 f = {k[0], k[1], k[2], s.type == OUT_BOTH, false};       // unclipped: the threshold takes the clip's place
+    const float c1 = k[3], c2 = k[4], c2r = k[5], w = k[6];
+    // the state z and the unclipped guided x0 prediction g of elements [i, i + V): the same bits each time it is asked
+    const auto eval = [&](long long i, float (&z)[V], float (&g)[V]) { ldv<V>(s.xt + b * N + i, z); guided<V>(s, b, i, w, z, f, g); };
+    const auto prod = [&](long long i, float (&g)[V]) { float z[V]; eval(i, z, g); };
     const float s_raw = __uint_as_float(abs_kth_select<V>(prod, N, p.r, sh));
-    const float s = s_raw != s_raw ? s_raw : fminf(fmaxf(s_raw, 1.f), p.s_max);       // a NaN of rank r stays one
-    if (threadIdx.x == 0 && p.s_out) p.s_out[b] = s;
+    const float t = s_raw != s_raw ? s_raw : fminf(fmaxf(s_raw, 1.f), p.s_max);       // a NaN of rank r stays one
+    if (threadIdx.x == 0 && p.s_out) p.s_out[b] = t;
     for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)blockDim.x * V) {
         float z[V], g[V], h[V], xn[V];
-        prod.eval(i, z, g);
+        eval(i, z, g);
         ldv<V>(p.hist + b * N + i, h);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            float c = g[j] < -s ? -s : (g[j] > s ? s : g[j]);                         // a NaN passes through
-            if (s != 1.f) c = c / s;                                                  // IEEE division; c / 1 = c
+            float c = g[j] < -t ? -t : (g[j] > t ? t : g[j]);                         // a NaN passes through
+            if (t != 1.f) c = c / t;                                                  // IEEE division; c / 1 = c
             g[j] = c;
-            xn[j] = dyn_update(c1, c2, c2r, z[j], c, h[j]);
+            xn[j] = solver_update(c1, c2, c2r, z[j], c, h[j]);
         }
         stv<V>(p.hist + b * N + i, g);
-        stv<V>(p.xn + b * N + i, xn);
-        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+        st_dup<V>(s.xn, s.xdup, b, N, i, xn);
     }
 }
 
 // ---- RePaint inpainting (Lugmayr et al. 2022) in log-SNR terms: sample_step_kernel's reverse step for the unknown region, a draw from
 // q(x_s | x_known) for the known one, and their merge by the mask, in one launch.  k[10] = sample_step_kernel's eight
 // {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3} and {ak, bk}, the alpha and sigma of the state the step lands on.  Evaluation order,
-// every operation in fp32, u sample_step_kernel's expressions term by term:
-//   x0h = a0*xt + b0x*o (+ b0e*o_eps), clipped when asked, per branch;   mean = last ? x0h : c1*xt + c2*x0h + c3*o
-//   v = cfg ? mean_c + w*(mean_c - mean_u) : mean_c;   u = v + noise_scale*noise  (when noise is given)
+// every operation in fp32:
+//   v = the guided StepMean<fused> of the two branches;   u = v + noise_scale*noise  (when noise is given)
 //   kn = ak*known + bk*knoise  (ak*known when knoise is null)
 //   xn = m == 1 ? kn : m == 0 ? u : m*kn + (1 - m)*u;   xdup rows 2b, 2b+1 <- xn
 // The two ends of the mask SELECT: a NaN or Inf of the branch not chosen does not reach xn.  full = the mask has C channels (else one,
 // shared by the sample's channels: a vector of V elements must then lie inside one channel, HW % V == 0).
 // Each thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
-// The wide and the scalar form must give the same bits (a caller's buffers decide between them), so the expressions are written once,
-// with contraction off and the fused operations spelled out.
-__device__ __forceinline__ float inp_mean(float a0, float b0x, float b0e, float c1, float c2, float c3, bool both, bool clip, bool last,
-                                          float z, float o, float oe) {
-#pragma clang fp contract(off)
-    float x0h = __builtin_fmaf(b0x, o, a0 * z) + (both ? b0e * oe : 0.f);
-    if (clip) x0h = fminf(fmaxf(x0h, -1.f), 1.f);
-    return last ? x0h : __builtin_fmaf(c3, o, __builtin_fmaf(c2, x0h, c1 * z));
-}
-
 __device__ __forceinline__ float inp_merge(float m, float kn, float u) {
 #pragma clang fp contract(off)
     return m == 1.f ? kn : (m == 0.f ? u : __builtin_fmaf(1.f - m, u, m * kn));
 }
 
-__device__ __forceinline__ float inp_axpby(float a, float x, float b, float y) {
-#pragma clang fp contract(off)
-    return __builtin_fmaf(b, y, a * x);
-}
-
-struct InpaintArgs {
-    const float* xt; const float* out; const float* noise; const float* known; const float* mask; const float* knoise;
-    float k[10]; const float* kdev; int type, cfg, last, clip, full; float* xn; float* xdup; int n; long long N, HW;
-};
+struct InpaintArgs { StepCommon s; const float* noise; const float* known; const float* mask; const float* knoise; int full; long long HW; };
 
 template <int V>
 __global__ void inpaint_step_kernel(const InpaintArgs p) {
-    const long long N = p.N, total = (long long)p.n * N / V;
-    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
-    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
-    const float ak = kp[8], bk = kp[9];
-    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = coefs(s.c);
+    const StepMean<true> f = step_mean<true>(s, k);
+    const float nscale = k[5], w = k[6], ak = k[8], bk = k[9];
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long e = idx * V, b = e / N, i = e % N;
-        float z[V], kw[V], m[V], nz[V], kz[V], mean[2][V], xn[V];
-        ldv<V>(p.xt + e, z);
+        float z[V], kw[V], m[V], nz[V], kz[V], v[V], xn[V];
+        ldv<V>(s.xt + e, z);
         ldv<V>(p.known + e, kw);
         ldv<V>(p.mask + (p.full ? e : b * p.HW + i % p.HW), m);
         if (p.noise) ldv<V>(p.noise + e, nz);
         if (p.knoise) ldv<V>(p.knoise + e, kz);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
-            if (u >= mul) break;
-            const float* ob = p.out + (b * mul + u) * Co * N + i;
-            float o[V], oe[V];
-            ldv<V>(ob, o);
-            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-                mean[u][j] = inp_mean(a0, b0x, b0e, c1, c2, c3, p.type == OUT_BOTH, p.clip, p.last, z[j], o[j],
-                                      p.type == OUT_BOTH ? oe[j] : 0.f);
-        }
+        guided<V>(s, b, i, w, z, f, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            float v = p.cfg ? dyn_guide(w, mean[0][j], mean[1][j]) : mean[0][j];
-            if (p.noise) v = inp_axpby(1.f, v, nscale, nz[j]);
-            const float kn = p.knoise ? inp_axpby(ak, kw[j], bk, kz[j]) : ak * kw[j];
-            xn[j] = inp_merge(m[j], kn, v);
+            if (p.noise) v[j] = axpby(1.f, v[j], nscale, nz[j]);
+            const float kn = p.knoise ? axpby(ak, kw[j], bk, kz[j]) : ak * kw[j];
+            xn[j] = inp_merge(m[j], kn, v[j]);
         }
-        stv<V>(p.xn + e, xn);
-        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xn); stv<V>(p.xdup + (2 * b + 1) * N + i, xn); }
+        st_dup<V>(s.xn, s.xdup, b, N, i, xn);
     }
 }
 
@@ -685,7 +684,7 @@ __global__ void forward_jump_kernel(const float* x, const float* noise, const fl
         ldv<V>(x + e, z);
         ldv<V>(noise + e, nz);
 #pragma unroll
-        for (int j = 0; j < V; ++j) r[j] = inp_axpby(a, z[j], b, nz[j]);
+        for (int j = 0; j < V; ++j) r[j] = axpby(a, z[j], b, nz[j]);
         stv<V>(xn + e, r);
         if (xdup) { stv<V>(xdup + 2 * s * N + i, r); stv<V>(xdup + (2 * s + 1) * N + i, r); }
     }
@@ -694,55 +693,39 @@ __global__ void forward_jump_kernel(const float* x, const float* noise, const fl
 // ---- DDPM noise-space inversion (Huberman-Spiegelglas et al. 2024) in log-SNR terms: given the state xt = x_{i+1} and the network's
 // output there, draw the next state from the image itself, xs = ak*x0 + bk*eps, and extract the noise map the ordinary reverse step
 // would have needed to land on it, z = (xs - v)/noise_scale with v sample_step_kernel's guided mean.  k[10] = inpaint_step_kernel's ten.
-// Evaluation order, every operation in fp32, mean and v inpaint_step_kernel's expressions (inp_mean, dyn_guide):
+// Evaluation order, every operation in fp32, v inpaint_step_kernel's guided StepMean<fused>:
 //   xs = ak*x0 + bk*eps  (ak*x0 when eps is null): inpaint_step_kernel's known-region value, same expression, same bits
 //   z  = (xs - v) / k[5]   one subtraction, one IEEE division;   xdup rows 2b, 2b+1 <- xs
 // xs does not depend on xt or out: a NaN of the network stays in z.  Each thread reads all it needs of its V elements before it writes
-// any of them, so xs may alias xt.  Written once with contraction off, so the wide and the scalar form give the same bits.
+// any of them, so xs may alias xt.
 __device__ __forceinline__ float inv_extract(float xs, float v, float nscale) {
 #pragma clang fp contract(off)
     return (xs - v) / nscale;
 }
 
-struct ExtractArgs {
-    const float* xt; const float* out; const float* x0; const float* eps; float k[10]; const float* kdev;
-    int type, cfg, last, clip; float* xs; float* z; float* xdup; int n; long long N;
-};
+struct ExtractArgs { StepCommon s; const float* x0; const float* eps; float* z; };       // s.xn = xs
 
 template <int V>
 __global__ void noise_extract_kernel(const ExtractArgs p) {
-    const long long N = p.N, total = (long long)p.n * N / V;
-    const float* kp = p.kdev ? p.kdev : p.k;       // device-resident coefficients keep the launch HIP-graph replayable
-    const float a0 = kp[0], b0x = kp[1], b0e = kp[2], c1 = kp[3], c2 = kp[4], nscale = kp[5], w = kp[6], c3 = kp[7];
-    const float ak = kp[8], bk = kp[9];
-    const int mul = 1 + p.cfg, Co = p.type == OUT_BOTH ? 2 : 1;
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = coefs(s.c);
+    const StepMean<true> f = step_mean<true>(s, k);
+    const float nscale = k[5], w = k[6], ak = k[8], bk = k[9];
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long e = idx * V, b = e / N, i = e % N;
-        float zt[V], im[V], ez[V], mean[2][V], xs[V], zz[V];
-        ldv<V>(p.xt + e, zt);
+        float zt[V], im[V], ez[V], v[V], xs[V], zz[V];
+        ldv<V>(s.xt + e, zt);
         ldv<V>(p.x0 + e, im);
         if (p.eps) ldv<V>(p.eps + e, ez);
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {                        // rows interleaved cond, uncond
-            if (u >= mul) break;
-            const float* ob = p.out + (b * mul + u) * Co * N + i;
-            float o[V], oe[V];
-            ldv<V>(ob, o);
-            if (p.type == OUT_BOTH) ldv<V>(ob + N, oe);
-#pragma unroll
-            for (int j = 0; j < V; ++j)
-                mean[u][j] = inp_mean(a0, b0x, b0e, c1, c2, c3, p.type == OUT_BOTH, p.clip, p.last, zt[j], o[j],
-                                      p.type == OUT_BOTH ? oe[j] : 0.f);
-        }
+        guided<V>(s, b, i, w, zt, f, v);
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            const float v = p.cfg ? dyn_guide(w, mean[0][j], mean[1][j]) : mean[0][j];
-            xs[j] = p.eps ? inp_axpby(ak, im[j], bk, ez[j]) : ak * im[j];
-            zz[j] = inv_extract(xs[j], v, nscale);
+            xs[j] = p.eps ? axpby(ak, im[j], bk, ez[j]) : ak * im[j];
+            zz[j] = inv_extract(xs[j], v[j], nscale);
         }
-        stv<V>(p.xs + e, xs);
         stv<V>(p.z + e, zz);
-        if (p.xdup) { stv<V>(p.xdup + 2 * b * N + i, xs); stv<V>(p.xdup + (2 * b + 1) * N + i, xs); }
+        st_dup<V>(s.xn, s.xdup, b, N, i, xs);
     }
 }
 
@@ -793,9 +776,55 @@ __global__ __launch_bounds__(SLERP_THREADS) void slerp_rows_kernel(const float* 
         ldv<V>(ar + i, x);
         ldv<V>(br + i, y);
 #pragma unroll
-        for (int j = 0; j < V; ++j) r[j] = inp_axpby(wa, x[j], wb, y[j]);
+        for (int j = 0; j < V; ++j) r[j] = axpby(wa, x[j], wb, y[j]);
         stv<V>(orow + i, r);
     }
+}
+
+// ---- host side of the entries below
+template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
+
+#define VD_TRY(call) do { if (const int rc_ = (call)) return rc_; } while (0)
+
+// the dwordx4 instantiation when wide (the element count is a multiple of 4 and every base 16-byte aligned), else the scalar one:
+// grid-stride kernels over total elements, and kernels whose workgroup of `threads` owns one of n rows
+template <class K, class... A> inline void launch_elems(K k4, K k1, bool wide, long long total, void* stream, const A&... a) {
+    hipLaunchKernelGGL(wide ? k4 : k1, dim3(grid_for(wide ? total / 4 : total)), dim3(256), 0, (hipStream_t)stream, a...);
+}
+
+template <class K, class... A> inline void launch_rows(K k4, K k1, bool wide, int n, int threads, void* stream, const A&... a) {
+    hipLaunchKernelGGL(wide ? k4 : k1, dim3(n), dim3(threads), 0, (hipStream_t)stream, a...);
+}
+
+// count coefficients as host floats k (copied into the kernel argument) or as a device pointer k_dev, never both
+inline int set_coefs(const char* who, Coefs& c, const float* k, const float* k_dev, int count) {
+    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "%s: pass the coefficients either as host k or as device k_dev", who);
+    c = {};
+    for (int i = 0; i < count; ++i) c.k[i] = k ? k[i] : 0.f;
+    c.kdev = k_dev;
+    return 0;
+}
+
+inline StepCommon step_common(const float* xt, const float* out, int type, int cfg, int last, int clip, float* xn, float* xdup, int n,
+                              int C, int HW) {
+    StepCommon s = {};
+    s.xt = xt; s.out = out; s.type = type; s.cfg = cfg ? 1 : 0; s.last = last ? 1 : 0; s.clip = clip ? 1 : 0;
+    s.xn = xn; s.xdup = xdup; s.n = n; s.N = (long long)C * HW;
+    return s;
+}
+
+// the refusals the step entries share (the first that applies is the one reported); ptrs = the entry's own buffers are all given
+inline int step_checks(const char* who, StepCommon& s, const float* k, const float* k_dev, int count, bool ptrs, int C, int HW) {
+    VD_TRY(set_coefs(who, s.c, k, k_dev, count));
+    VD_REQUIRE(s.type >= 0 && s.type <= 3, "%s: bad model_out_type %d", who, s.type);
+    VD_REQUIRE(ptrs, "%s: null pointer", who);
+    VD_REQUIRE(s.n > 0 && C > 0 && HW > 0, "%s: empty batch or image (n=%d, C=%d, HW=%d)", who, s.n, C, HW);
+    return 0;
+}
+
+inline int dup_is_guided(const char* who, const StepCommon& s) {
+    VD_REQUIRE(!s.xdup || s.cfg, "%s: the duplicated state is the guided network's input (cfg = 1)", who);
+    return 0;
 }
 
 }  // namespace
@@ -833,12 +862,9 @@ extern "C" int vd_loss_bwd(const float* x0, const float* eps, const float* xt, c
 extern "C" int vd_sample_step(const float* xt, const float* out, const float* noise, const float* k, const float* k_dev,
                               int32_t type, int32_t cfg, int32_t last_step, int32_t clip, float* xn, float* xdup, int32_t n,
                               int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_sample_step: pass the coefficients either as host k or as device k_dev");
+    StepArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, HW), noise};
+    VD_TRY(set_coefs("vd_sample_step", p.s.c, k, k_dev, 8));
     VD_REQUIRE(noise != nullptr || k_dev != nullptr || k[5] == 0.f, "vd_sample_step: noise required when the noise scale is non-zero");
-    StepArgs p = {};
-    p.xt = xt; p.out = out; p.noise = noise; p.kdev = k_dev;
-    for (int i = 0; i < 8; ++i) p.k[i] = k ? k[i] : 0.f;
-    p.type = type; p.cfg = cfg; p.last = last_step; p.clip = clip; p.xn = xn; p.xdup = xdup; p.n = n; p.C = C; p.HW = HW;
     hipLaunchKernelGGL(sample_step_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
     VD_LAUNCH_CHECK("sample_step_kernel");
     return 0;
@@ -874,10 +900,7 @@ extern "C" int vd_distill_mid(const float* zt, const float* out, const float* co
     VD_REQUIRE(!zdup || cfg, "vd_distill_mid: the duplicated state is the guided teacher's input (cfg = 1)");
     const long long N = (long long)C * HW;
     DistillMidArgs p = {zt, out, coef, teacher_type, cfg ? 1 : 0, clip ? 1 : 0, xhat, dhat, zmid, zdup, n, N};
-    if (N % 4 == 0 && all_aligned16(zt, out, xhat, dhat, zmid, zdup))
-        hipLaunchKernelGGL(distill_mid_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(distill_mid_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_elems(distill_mid_kernel<4>, distill_mid_kernel<1>, N % 4 == 0 && all_aligned16(zt, out, xhat, dhat, zmid, zdup), n * N, stream, p);
     VD_LAUNCH_CHECK("distill_mid_kernel");
     return 0;
 }
@@ -893,10 +916,8 @@ extern "C" int vd_distill_loss_fwd(const float* xhat, const float* dhat, const f
     VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_fwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
     const long long N = (long long)C * HW;
     DistillLossArgs p = {xhat, dhat, zmid, teacher_out, zt, student_out, coef, teacher_type, student_type, cfg ? 1 : 0, clip ? 1 : 0, n, N};
-    if (N % 4 == 0 && all_aligned16(xhat, dhat, zmid, teacher_out, zt, student_out, resid, xtilde))
-        hipLaunchKernelGGL(distill_loss_fwd_kernel<4>, dim3(n), dim3(256), 0, (hipStream_t)stream, p, loss, resid, xtilde);
-    else
-        hipLaunchKernelGGL(distill_loss_fwd_kernel<1>, dim3(n), dim3(256), 0, (hipStream_t)stream, p, loss, resid, xtilde);
+    launch_rows(distill_loss_fwd_kernel<4>, distill_loss_fwd_kernel<1>,
+                N % 4 == 0 && all_aligned16(xhat, dhat, zmid, teacher_out, zt, student_out, resid, xtilde), n, 256, stream, p, loss, resid, xtilde);
     VD_LAUNCH_CHECK("distill_loss_fwd_kernel");
     return 0;
 }
@@ -907,33 +928,19 @@ extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const 
     VD_REQUIRE(resid && coef && gloss && dout, "vd_distill_loss_bwd: null pointer");
     VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_bwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
     const long long N = (long long)C * HW;
-    if (N % 4 == 0 && all_aligned16(resid, dout))
-        hipLaunchKernelGGL(distill_loss_bwd_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, resid, coef, gloss,
-                           student_type, dout, n, N);
-    else
-        hipLaunchKernelGGL(distill_loss_bwd_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, resid, coef, gloss,
-                           student_type, dout, n, N);
+    launch_elems(distill_loss_bwd_kernel<4>, distill_loss_bwd_kernel<1>, N % 4 == 0 && all_aligned16(resid, dout), n * N, stream, resid, coef,
+                 gloss, (int)student_type, dout, (int)n, N);
     VD_LAUNCH_CHECK("distill_loss_bwd_kernel");
     return 0;
 }
 
 extern "C" int vd_solver_step(const float* xt, const float* out, float* hist, const float* k, const float* k_dev, int32_t type,
                               int32_t cfg, int32_t clip, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_solver_step: pass the coefficients either as host k or as device k_dev");
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_solver_step: bad model_out_type %d", type);
-    VD_REQUIRE(xt && out && hist && xn, "vd_solver_step: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_solver_step: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
-    VD_REQUIRE(!xdup || cfg, "vd_solver_step: the duplicated state is the guided network's input (cfg = 1)");
+    SolverArgs p = {step_common(xt, out, type, cfg, 0, clip, xn, xdup, n, C, HW), hist};
+    VD_TRY(step_checks("vd_solver_step", p.s, k, k_dev, 8, xt && out && hist && xn, C, HW));
+    VD_TRY(dup_is_guided("vd_solver_step", p.s));
     VD_REQUIRE(hist != xt && hist != xn, "vd_solver_step: hist is a buffer of its own");
-    const long long N = (long long)C * HW;
-    SolverArgs p = {};
-    p.xt = xt; p.out = out; p.hist = hist; p.kdev = k_dev;
-    for (int i = 0; i < 8; ++i) p.k[i] = k ? k[i] : 0.f;
-    p.type = type; p.cfg = cfg ? 1 : 0; p.clip = clip ? 1 : 0; p.xn = xn; p.xdup = xdup; p.n = n; p.N = N;
-    if (N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup))
-        hipLaunchKernelGGL(solver_step_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(solver_step_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_elems(solver_step_kernel<4>, solver_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup), n * p.s.N, stream, p);
     VD_LAUNCH_CHECK("solver_step_kernel");
     return 0;
 }
@@ -943,10 +950,8 @@ extern "C" int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, 
     VD_REQUIRE(n > 0 && N > 0, "vd_abs_kth_rows: empty batch or row (n=%d, N=%lld)", n, (long long)N);
     VD_REQUIRE(N <= VD_KTH_MAX_ROW, "vd_abs_kth_rows: rows of at most %lld elements (N=%lld)", (long long)VD_KTH_MAX_ROW, (long long)N);
     VD_REQUIRE(r >= 0 && r < N, "vd_abs_kth_rows: rank %lld outside [0, %lld)", (long long)r, (long long)N);
-    if (N % 4 == 0 && vd_aligned16(x))
-        hipLaunchKernelGGL(abs_kth_rows_kernel<4>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, x, (long long)N, (uint32_t)r, kth);
-    else
-        hipLaunchKernelGGL(abs_kth_rows_kernel<1>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, x, (long long)N, (uint32_t)r, kth);
+    launch_rows(abs_kth_rows_kernel<4>, abs_kth_rows_kernel<1>, N % 4 == 0 && vd_aligned16(x), n, KTH_THREADS, stream, x, (long long)N,
+                (uint32_t)r, kth);
     VD_LAUNCH_CHECK("abs_kth_rows_kernel");
     return 0;
 }
@@ -954,24 +959,16 @@ extern "C" int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, 
 extern "C" int vd_solver_step_dyn(const float* xt, const float* out, float* hist, const float* k, const float* k_dev, int32_t type,
                                   int32_t cfg, int64_t r, float s_max, float* s_out, float* xn, float* xdup, int32_t n, int32_t C,
                                   int32_t HW, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_solver_step_dyn: pass the coefficients either as host k or as device k_dev");
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_solver_step_dyn: bad model_out_type %d", type);
-    VD_REQUIRE(xt && out && hist && xn, "vd_solver_step_dyn: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_solver_step_dyn: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
-    VD_REQUIRE(!xdup || cfg, "vd_solver_step_dyn: the duplicated state is the guided network's input (cfg = 1)");
+    SolverDynArgs p = {step_common(xt, out, type, cfg, 0, 0, xn, xdup, n, C, HW), hist, (uint32_t)r, s_max, s_out};
+    VD_TRY(step_checks("vd_solver_step_dyn", p.s, k, k_dev, 8, xt && out && hist && xn, C, HW));
+    VD_TRY(dup_is_guided("vd_solver_step_dyn", p.s));
     VD_REQUIRE(hist != xt && hist != xn, "vd_solver_step_dyn: hist is a buffer of its own");
     VD_REQUIRE(s_max >= 1.f, "vd_solver_step_dyn: s_max must be >= 1 (+Inf for no cap), got %g", (double)s_max);
-    const long long N = (long long)C * HW;
+    const long long N = p.s.N;
     VD_REQUIRE(N <= VD_KTH_MAX_ROW, "vd_solver_step_dyn: images of at most %lld elements (C*HW=%lld)", (long long)VD_KTH_MAX_ROW, N);
     VD_REQUIRE(r >= 0 && r < N, "vd_solver_step_dyn: rank %lld outside [0, %lld)", (long long)r, N);
-    SolverDynArgs p = {};
-    p.xt = xt; p.out = out; p.hist = hist; p.kdev = k_dev;
-    for (int i = 0; i < 8; ++i) p.k[i] = k ? k[i] : 0.f;
-    p.type = type; p.cfg = cfg ? 1 : 0; p.r = (uint32_t)r; p.s_max = s_max; p.s_out = s_out; p.xn = xn; p.xdup = xdup; p.n = n; p.N = N;
-    if (N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup))
-        hipLaunchKernelGGL(solver_step_dyn_kernel<4>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(solver_step_dyn_kernel<1>, dim3(n), dim3(KTH_THREADS), 0, (hipStream_t)stream, p);
+    launch_rows(solver_step_dyn_kernel<4>, solver_step_dyn_kernel<1>, N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup), n, KTH_THREADS,
+                stream, p);
     VD_LAUNCH_CHECK("solver_step_dyn_kernel");
     return 0;
 }
@@ -979,41 +976,27 @@ extern "C" int vd_solver_step_dyn(const float* xt, const float* out, float* hist
 extern "C" int vd_inpaint_step(const float* xt, const float* out, const float* noise, const float* known, const float* mask,
                                const float* knoise, const float* k, const float* k_dev, int32_t type, int32_t cfg, int32_t last_step,
                                int32_t clip, int32_t mask_c, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_inpaint_step: pass the coefficients either as host k or as device k_dev");
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_inpaint_step: bad model_out_type %d", type);
-    VD_REQUIRE(xt && out && known && mask && xn, "vd_inpaint_step: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_inpaint_step: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    InpaintArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, HW), noise, known, mask, knoise, mask_c == C ? 1 : 0, HW};
+    VD_TRY(step_checks("vd_inpaint_step", p.s, k, k_dev, 10, xt && out && known && mask && xn, C, HW));
     VD_REQUIRE(mask_c == 1 || mask_c == C, "vd_inpaint_step: mask_c must be 1 or C (mask_c=%d, C=%d)", mask_c, C);
-    VD_REQUIRE(!xdup || cfg, "vd_inpaint_step: the duplicated state is the guided network's input (cfg = 1)");
+    VD_TRY(dup_is_guided("vd_inpaint_step", p.s));
     VD_REQUIRE(noise != nullptr || k_dev != nullptr || k[5] == 0.f, "vd_inpaint_step: noise required when the noise scale is non-zero");
     VD_REQUIRE(knoise != nullptr || k_dev != nullptr || k[9] == 0.f, "vd_inpaint_step: knoise required when bk is non-zero");
-    const long long N = (long long)C * HW;
-    InpaintArgs p = {};
-    p.xt = xt; p.out = out; p.noise = noise; p.known = known; p.mask = mask; p.knoise = knoise; p.kdev = k_dev;
-    for (int i = 0; i < 10; ++i) p.k[i] = k ? k[i] : 0.f;
-    p.type = type; p.cfg = cfg ? 1 : 0; p.last = last_step ? 1 : 0; p.clip = clip ? 1 : 0; p.full = mask_c == C ? 1 : 0;
-    p.xn = xn; p.xdup = xdup; p.n = n; p.N = N; p.HW = HW;
     // a one-channel mask is indexed per channel: a vector must not straddle two channels
-    if (N % 4 == 0 && (p.full || HW % 4 == 0) && all_aligned16(xt, out, noise, known, mask, knoise, xn, xdup))
-        hipLaunchKernelGGL(inpaint_step_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(inpaint_step_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_elems(inpaint_step_kernel<4>, inpaint_step_kernel<1>,
+                 p.s.N % 4 == 0 && (p.full || HW % 4 == 0) && all_aligned16(xt, out, noise, known, mask, knoise, xn, xdup), n * p.s.N, stream, p);
     VD_LAUNCH_CHECK("inpaint_step_kernel");
     return 0;
 }
 
 extern "C" int vd_forward_jump(const float* x, const float* noise, const float* k, const float* k_dev, float* xn, float* xdup, int32_t n,
                                int64_t N, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_forward_jump: pass the coefficients either as host k or as device k_dev");
+    Coefs c;
+    VD_TRY(set_coefs("vd_forward_jump", c, k, k_dev, 2));
     VD_REQUIRE(x && noise && xn, "vd_forward_jump: null pointer");
     VD_REQUIRE(n > 0 && N > 0, "vd_forward_jump: empty batch or image (n=%d, N=%lld)", n, (long long)N);
-    const float a = k ? k[0] : 0.f, b = k ? k[1] : 0.f;
-    if (N % 4 == 0 && all_aligned16(x, noise, xn, xdup))
-        hipLaunchKernelGGL(forward_jump_kernel<4>, dim3(grid_for(n * (long long)N / 4)), dim3(256), 0, (hipStream_t)stream, x, noise, k_dev,
-                           a, b, xn, xdup, n, (long long)N);
-    else
-        hipLaunchKernelGGL(forward_jump_kernel<1>, dim3(grid_for(n * (long long)N)), dim3(256), 0, (hipStream_t)stream, x, noise, k_dev, a,
-                           b, xn, xdup, n, (long long)N);
+    launch_elems(forward_jump_kernel<4>, forward_jump_kernel<1>, N % 4 == 0 && all_aligned16(x, noise, xn, xdup), n * (long long)N, stream, x,
+                 noise, k_dev, c.k[0], c.k[1], xn, xdup, (int)n, (long long)N);
     VD_LAUNCH_CHECK("forward_jump_kernel");
     return 0;
 }
@@ -1021,25 +1004,15 @@ extern "C" int vd_forward_jump(const float* x, const float* noise, const float* 
 extern "C" int vd_noise_extract(const float* xt, const float* out, const float* x0, const float* eps, const float* k, const float* k_dev,
                                 int32_t type, int32_t cfg, int32_t last_step, int32_t clip, float* xs, float* z, float* xdup, int32_t n,
                                 int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE((k != nullptr) != (k_dev != nullptr), "vd_noise_extract: pass the coefficients either as host k or as device k_dev");
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_noise_extract: bad model_out_type %d", type);
-    VD_REQUIRE(xt && out && x0 && xs && z, "vd_noise_extract: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_noise_extract: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
-    VD_REQUIRE(!xdup || cfg, "vd_noise_extract: the duplicated state is the guided network's input (cfg = 1)");
+    ExtractArgs p = {step_common(xt, out, type, cfg, last_step, clip, xs, xdup, n, C, HW), x0, eps, z};
+    VD_TRY(step_checks("vd_noise_extract", p.s, k, k_dev, 10, xt && out && x0 && xs && z, C, HW));
+    VD_TRY(dup_is_guided("vd_noise_extract", p.s));
     VD_REQUIRE(z != xs && z != xt && z != x0 && z != eps && xs != x0 && xs != eps, "vd_noise_extract: z is a buffer of its own, and xs may alias xt only");
     VD_REQUIRE(k_dev != nullptr || (std::isfinite(k[5]) && k[5] != 0.f), "vd_noise_extract: the noise scale k[5] must be finite and non-zero, got %g",
                (double)k[5]);
     VD_REQUIRE(eps != nullptr || k_dev != nullptr || k[9] == 0.f, "vd_noise_extract: eps required when bk is non-zero");
-    const long long N = (long long)C * HW;
-    ExtractArgs p = {};
-    p.xt = xt; p.out = out; p.x0 = x0; p.eps = eps; p.kdev = k_dev;
-    for (int i = 0; i < 10; ++i) p.k[i] = k ? k[i] : 0.f;
-    p.type = type; p.cfg = cfg ? 1 : 0; p.last = last_step ? 1 : 0; p.clip = clip ? 1 : 0;
-    p.xs = xs; p.z = z; p.xdup = xdup; p.n = n; p.N = N;
-    if (N % 4 == 0 && all_aligned16(xt, out, x0, eps, xs, z, xdup))
-        hipLaunchKernelGGL(noise_extract_kernel<4>, dim3(grid_for(n * N / 4)), dim3(256), 0, (hipStream_t)stream, p);
-    else
-        hipLaunchKernelGGL(noise_extract_kernel<1>, dim3(grid_for(n * N)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_elems(noise_extract_kernel<4>, noise_extract_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, x0, eps, xs, z, xdup), n * p.s.N,
+                 stream, p);
     VD_LAUNCH_CHECK("noise_extract_kernel");
     return 0;
 }
@@ -1051,12 +1024,8 @@ extern "C" int vd_slerp_rows(const float* a, const float* b, const float* frac, 
     VD_REQUIRE(n > 0 && N > 0, "vd_slerp_rows: empty batch or row (n=%d, N=%lld)", n, (long long)N);
     VD_REQUIRE(out != a && out != b, "vd_slerp_rows: out may alias neither input (the rows are read twice)");
     const float f = frac ? frac[0] : 0.f;
-    if (N % 4 == 0 && all_aligned16(a, b, out))
-        hipLaunchKernelGGL(slerp_rows_kernel<4>, dim3(n), dim3(SLERP_THREADS), 0, (hipStream_t)stream, a, b, frac_dev, f, out, w_out,
-                           (long long)N);
-    else
-        hipLaunchKernelGGL(slerp_rows_kernel<1>, dim3(n), dim3(SLERP_THREADS), 0, (hipStream_t)stream, a, b, frac_dev, f, out, w_out,
-                           (long long)N);
+    launch_rows(slerp_rows_kernel<4>, slerp_rows_kernel<1>, N % 4 == 0 && all_aligned16(a, b, out), n, SLERP_THREADS, stream, a, b, frac_dev, f,
+                out, w_out, (long long)N);
     VD_LAUNCH_CHECK("slerp_rows_kernel");
     return 0;
 }

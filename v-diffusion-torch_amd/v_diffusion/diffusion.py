@@ -13,13 +13,13 @@ What runs where
 MI355X only: CPU tensors raise (the CPU restatement is oracle/diffusion_ref.py, test infrastructure).
 ``loss_type="kl"`` (variational-bound terms, reference :446-464) is one fused kernel pair as well (vd_bpd_terms / vd_bpd_bwd).
 """
-import contextlib
 import math
 
 import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .chain import Chain, captured_step
 from .functions import flat_mean
 
 F64 = torch.float64
@@ -667,52 +667,13 @@ class GaussianDiffusion:
         net = getattr(denoise_fn, "module", denoise_fn)
         return hasattr(net, "engine") and not net.training and rows <= self.GRAPH_MAX_ROWS and pred_freq is None
 
-    def _sample_loop_graph(self, denoise_fn, shape, x_t, y_in, cfg, device, generator, use_ddim):
-        B, C = shape[0], shape[1]
-        HW = int(shape[2]) * int(shape[3])
+    def _sample_loop_graph(self, denoise_fn, shape, x_t, label, device, generator, use_ddim):
+        def launch(ch, st, out):
+            _hip.sample_step(ch.x, out, st["noise"], None, ch.mot, ch.cfg, False, True, *ch.dst, ch.B, ch.C, ch.HW, k_dev=st["k"])
+        graph, st, _ = captured_step(self.__dict__.setdefault("_graphs", {}), self.GRAPH_CACHE_MAX, self, denoise_fn, shape, label, device,
+                                     launch, bufs=("noise",))
+        st["chain"].load(x_t, label)
         T = self.sample_timesteps
-        net = getattr(denoise_fn, "module", denoise_fn)
-        mot = _hip.OUT_TYPES[self.model_out_type]
-        key = (id(denoise_fn), tuple(shape), bool(cfg), self.model_out_type, None if y_in is None else tuple(y_in.shape),
-               hash(tuple(p.data_ptr() for p in net.parameters())))
-        cache = self.__dict__.setdefault("_graphs", {})
-        entry = cache.get(key)
-        if entry is None:
-            rows = B * (1 + cfg)
-            st = dict(x=torch.zeros(shape, dtype=torch.float32, device=device),
-                      t=torch.zeros((rows,), dtype=F64, device=device),
-                      noise=torch.zeros(shape, dtype=torch.float32, device=device),
-                      k=torch.zeros((8,), dtype=torch.float32, device=device),
-                      y=None if y_in is None else torch.zeros_like(y_in))
-            st["xin"] = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=device) if cfg else st["x"]
-
-            def body():
-                out = denoise_fn(st["xin"], st["t"], st["y"]).to(torch.float32).contiguous()
-                _hip.sample_step(st["x"], out, st["noise"], None, mot, cfg, False, True, st["x"], st["xin"] if cfg else None,
-                                 B, C, HW, k_dev=st["k"])
-            side = torch.cuda.Stream(device)
-            side.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(side):              # warm-up outside capture (lazy initialisation, workspace growth)
-                body()
-            torch.cuda.current_stream(device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                body()
-            # the graph's pack / convolution nodes hold raw pointers into the forward's ConvPacks (device tables, U images):
-            # keep that object referenced by the cache entry, so an engine-side eviction can never free memory a cached graph
-            # replays through; the graph cache itself is a small LRU (a graph pins its activations)
-            eng = net.engine() if hasattr(net, "engine") else None
-            while len(cache) >= self.GRAPH_CACHE_MAX:
-                cache.pop(next(iter(cache)))
-            entry = cache[key] = (graph, st, None if eng is None else eng.packs)
-        else:
-            cache[key] = cache.pop(key)                # most recently used last
-        graph, st = entry[0], entry[1]
-        st["x"].copy_(x_t)
-        if cfg:
-            st["xin"].copy_(x_t.repeat_interleave(2, dim=0))
-        if y_in is not None:
-            st["y"].copy_(y_in)
         rowsk, tnets = [], []
         for ti in range(T):
             k8, t_net = self._step_coefs(ti, use_ddim)
@@ -726,52 +687,32 @@ class GaussianDiffusion:
             st["noise"].normal_(generator=generator)
             st["k"].copy_(ktab[ti])
             graph.replay()
-        return st["x"].clone()
+        return st["chain"].x.clone()
 
     def _sample_loop(self, denoise_fn, shape, noise, label, device, seed, use_ddim, pred_freq=None, use_graph=None):
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("GaussianDiffusion.p_sample: device must be an MI355X ('cuda'); there is no CPU path")
-        B, T = shape[0], self.sample_timesteps
         generator = None if seed is None else torch.Generator(device).manual_seed(seed)
         if noise is None:
             x_t = torch.randn(shape, device=device, generator=generator)
         else:
             x_t = noise.to(device=device, dtype=torch.float32).contiguous().clone()
-        if label is not None:
-            label = label.to(device)
-        cfg = self._use_cfg(label)
-        if cfg:
-            y_in = label.repeat_interleave(2, dim=0).clone()
-            y_in[1::2] = 0                                     # unconditional rows (reference :372)
-            x_in = x_t.repeat_interleave(2, dim=0)
-            x_in_next = torch.empty_like(x_in)
-        else:
-            y_in, x_in, x_in_next = label, x_t, None
         if use_graph is None:
-            use_graph = self._graph_eligible(denoise_fn, B * (1 + cfg), pred_freq)
+            use_graph = self._graph_eligible(denoise_fn, shape[0] * (1 + self._use_cfg(label)), pred_freq)
         if use_graph:
-            return self._sample_loop_graph(denoise_fn, tuple(shape), x_t, y_in, cfg, device, generator, use_ddim), []
-        x_next = torch.empty_like(x_t)
+            return self._sample_loop_graph(denoise_fn, tuple(shape), x_t, label, device, generator, use_ddim), []
+        ch = Chain(self, denoise_fn, x_t, label, device)
         preds = []
-        net = getattr(denoise_fn, "module", denoise_fn)
-        eng = net.engine() if hasattr(net, "engine") else None
-        with (eng.fixed_weights() if eng is not None else contextlib.nullcontext()):       # the weights do not change inside one reverse chain
-            return self._eager_chain(denoise_fn, x_t, x_in, x_in_next, x_next, y_in, cfg, B, T, device, generator, use_ddim,
-                                     pred_freq, preds)
-
-    def _eager_chain(self, denoise_fn, x_t, x_in, x_in_next, x_next, y_in, cfg, B, T, device, generator, use_ddim, pred_freq, preds):
-        for ti in reversed(range(T)):
-            step_noise = torch.empty_like(x_t).normal_(generator=generator)      # drawn every step, also for DDIM (:389)
-            want = pred_freq is not None and (ti + 1) % pred_freq == 0
-            pred = self._reverse_step(denoise_fn, x_t, x_in if cfg else x_t, y_in, ti, cfg, step_noise, use_ddim, True,
-                                      want, x_next, x_in_next)
-            if want:
-                preds.append(pred.cpu())
-            x_t, x_next = x_next, x_t
-            if cfg:
-                x_in, x_in_next = x_in_next, x_in
-        return x_t, preds
+        with ch.fixed_weights():
+            for ti in reversed(range(self.sample_timesteps)):
+                step_noise = torch.empty_like(ch.x).normal_(generator=generator)      # drawn every step, also for DDIM (:389)
+                want = pred_freq is not None and (ti + 1) % pred_freq == 0
+                pred = self._reverse_step(denoise_fn, ch.x, ch.net_in, ch.y_in, ti, ch.cfg, step_noise, use_ddim, True, want, *ch.dst)
+                if want:
+                    preds.append(pred.cpu())
+                ch.advance()
+        return ch.x, preds
 
     @staticmethod
     def _default_device(denoise_fn):

@@ -18,13 +18,13 @@ Random draws, from one ``torch.Generator(device).manual_seed(seed)``, each of th
 as ``p_sample`` does), in this fixed order: first the initial state (x_T, or the eps of x_start = alpha known + sigma eps); then per
 transition of the schedule, a reverse step draws ``noise`` (the posterior's) and then ``knoise`` (the known region's), a jump draws one.
 """
-import contextlib
 import numbers
 
 import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .chain import Chain, chain_length, image_batch
 from .diffusion import F64, _device_ctx, _need_cuda
 
 
@@ -96,8 +96,7 @@ def _check_inputs(gd, known, mask, jump_length, resamplings, start):
     """everything that can be refused before a launch; returns (T of the chain, the mask's channel count)"""
     if gd.model_var_type == "learned":
         raise NotImplementedError("model_var_type='learned'")
-    if not torch.is_tensor(known) or known.dim() != 4 or known.numel() == 0:
-        raise ValueError(f"known must be a non-empty (B, C, H, W) tensor, got shape {tuple(getattr(known, 'shape', ()))}")
+    image_batch("known", known)
     B, C, H, W = known.shape
     if not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) \
             or tuple(mask.shape[2:]) != (H, W):
@@ -109,12 +108,9 @@ def _check_inputs(gd, known, mask, jump_length, resamplings, start):
         lo, hi = float(mask.min()), float(mask.max())
         if not (lo >= 0.0 and hi <= 1.0):                          # (a NaN fails both)
             raise ValueError(f"mask values must lie in [0, 1], got [{lo}, {hi}]")
-    T = gd.sample_timesteps
-    if start is not None:
-        if isinstance(start, bool) or not isinstance(start, numbers.Integral) or not 1 <= start <= T:
-            raise ValueError(f"start must be an integer in [1, {T}], got {start!r}")
-    resampling_schedule(T if start is None else start, jump_length, resamplings)      # validates the two counts
-    return (T if start is None else int(start)), int(mask.shape[1])
+    Tc = chain_length(gd, start)
+    resampling_schedule(Tc, jump_length, resamplings)              # validates the two counts
+    return Tc, int(mask.shape[1])
 
 
 def p_sample_inpaint(gd, denoise_fn, known, mask, label=None, device=None, seed=None, use_ddim=False, jump_length=1, resamplings=1,
@@ -131,42 +127,22 @@ def p_sample_inpaint(gd, denoise_fn, known, mask, label=None, device=None, seed=
         known = known.to(device=device, dtype=torch.float32).contiguous()
         shape = tuple(known.shape)
         draw = lambda: torch.randn(shape, device=device, generator=generator)
-        B, C = shape[:2]
-        HW = shape[2] * shape[3]
-        m = mask.to(device=device, dtype=torch.float32).expand(B, mask_c, shape[2], shape[3]).contiguous()
-        if label is not None:
-            label = label.to(device)
-        cfg = gd._use_cfg(label)
-        if cfg:
-            y_in = label.repeat_interleave(2, dim=0).clone()
-            y_in[1::2] = 0                                                     # unconditional rows, as _sample_loop builds them
-        else:
-            y_in = label
-        rows = B * (1 + cfg)
-        x_t = draw()                                                           # x_T, or the eps of the noised start
-        x_next = torch.empty_like(x_t)
-        x_in = torch.empty((rows,) + shape[1:], dtype=torch.float32, device=device) if cfg else None
-        x_in_next = torch.empty_like(x_in) if cfg else None
+        m = mask.to(device=device, dtype=torch.float32).expand(shape[0], mask_c, shape[2], shape[3]).contiguous()
+        ch = Chain(gd, denoise_fn, draw(), label, device, dup=False)           # x_T, or the eps of the noised start
+        B, C, HW = ch.B, ch.C, ch.HW
         if start is not None:                                                  # SDEdit: x_start = alpha known + sigma eps, everywhere
-            _hip.forward_jump(known, x_t, known_coefs(fn, T, Tc), x_next, x_in, B, C * HW)
-            x_t, x_next = x_next, x_t
-        elif cfg:
-            x_in.copy_(x_t.repeat_interleave(2, dim=0))
-        mot = _hip.OUT_TYPES[gd.model_out_type]
-        net = getattr(denoise_fn, "module", denoise_fn)
-        eng = net.engine() if hasattr(net, "engine") else None
-        with (eng.fixed_weights() if eng is not None else contextlib.nullcontext()):   # the weights do not change inside one chain
+            _hip.forward_jump(known, ch.x, known_coefs(fn, T, Tc), *ch.dst, B, C * HW)
+            ch.advance()
+        elif ch.cfg:
+            ch.x_in.copy_(ch.x.repeat_interleave(2, dim=0))
+        with ch.fixed_weights():
             for cur, nxt in zip(sched, sched[1:]):
                 if nxt < cur:                                                  # reverse step cur -> nxt = cur - 1
                     k8, t_net = gd._step_coefs(nxt, use_ddim, clip)
                     noise, knoise = draw(), draw()
-                    t_in = torch.full((rows,), t_net, dtype=F64, device=device)
-                    out = denoise_fn(x_in if cfg else x_t, t_in, y_in).to(torch.float32).contiguous()
-                    _hip.inpaint_step(x_t, out, noise, known, m, knoise, list(k8) + list(known_coefs(fn, T, nxt)), mot, cfg, nxt == 0,
-                                      clip, mask_c, x_next, x_in_next, B, C, HW)
+                    _hip.inpaint_step(ch.x, ch.net(t_net), noise, known, m, knoise, list(k8) + list(known_coefs(fn, T, nxt)), ch.mot, ch.cfg,
+                                      nxt == 0, clip, mask_c, *ch.dst, B, C, HW)
                 else:                                                          # jump cur -> nxt = cur + jump_length: one draw
-                    _hip.forward_jump(x_t, draw(), jump_coefs(fn, T, cur, nxt - cur), x_next, x_in_next, B, C * HW)
-                x_t, x_next = x_next, x_t
-                if cfg:
-                    x_in, x_in_next = x_in_next, x_in
-        return x_t
+                    _hip.forward_jump(ch.x, draw(), jump_coefs(fn, T, cur, nxt - cur), *ch.dst, B, C * HW)
+                ch.advance()
+        return ch.x

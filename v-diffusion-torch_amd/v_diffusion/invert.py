@@ -22,13 +22,13 @@ h = (l_n - l_t)/2 < 0, rho = h/(2 h_prev).  vd_solver_step runs them as it is.  
 What runs where: tables and coefficients are fp64 host arithmetic on the fp32-rounded log-SNRs, each value rounded once; everything per
 element is the kernels.  MI355X only: CPU tensors raise.  A captured-graph path is not built for any of the three chains.
 """
-import contextlib
 import numbers
 
 import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .chain import Chain, chain_length, image_batch, refuse_variants
 from .diffusion import F64, _device_ctx, _need_cuda, _pred_coefs
 from .inpaint import known_coefs
 from .solver import C2RHO, _check, _grid
@@ -67,82 +67,29 @@ def encode_coefs(logsnr_fn, steps, order=1, spacing="time", model_out_type="v", 
     return torch.stack(rows).contiguous(), torch.tensor(times, dtype=F64)
 
 
-def _refuse_variants(gd, what):
-    if gd.model_var_type == "learned":
-        raise NotImplementedError("model_var_type='learned'")
-    if gd.x0eps_coef:
-        raise NotImplementedError(f"x0eps_coef=True with {what}")
-
-
-def _image_batch(name, x):
-    if not torch.is_tensor(x) or x.dim() != 4 or x.numel() == 0:
-        raise ValueError(f"{name} must be a non-empty (B, C, H, W) tensor, got shape {tuple(getattr(x, 'shape', ()))}")
-
-
-def _guided_rows(gd, label, device):
-    """(cfg, the label rows the network sees on the device: cond, uncond interleaved as ``_sample_loop`` builds them)"""
-    if label is not None:
-        label = label.to(device)
-    cfg = gd._use_cfg(label)
-    if cfg:
-        y_in = label.repeat_interleave(2, dim=0).clone()
-        y_in[1::2] = 0
-    else:
-        y_in = label
-    return cfg, y_in
-
-
-def _fixed_weights(denoise_fn):
-    net = getattr(denoise_fn, "module", denoise_fn)
-    eng = net.engine() if hasattr(net, "engine") else None
-    return eng.fixed_weights() if eng is not None else contextlib.nullcontext()     # the weights do not change inside one chain
-
-
 def p_encode(gd, denoise_fn, x_0, label=None, device=None, steps=None, order=1, spacing="time", clip_denoised=False, stop=None):
     """the chain of ``GaussianDiffusion.p_encode`` (see there); returns the latent on the device"""
     steps = gd.sample_timesteps if steps is None else int(steps)
     _check(steps, order)
-    _refuse_variants(gd, "the ascending solver")
-    _image_batch("x_0", x_0)
+    refuse_variants(gd, "the ascending solver")
+    image_batch("x_0", x_0)
     if stop is not None and (isinstance(stop, bool) or not isinstance(stop, numbers.Integral) or not 1 <= stop <= steps):
         raise ValueError(f"stop must be an integer in [1, {steps}], got {stop!r}")
     table, t_net = encode_coefs(gd.logsnr_fn, steps, order, spacing, gd.model_out_type, gd.w_guide)      # host only; checks the spacing
     _need_cuda(x_0, "p_encode")
     device = torch.device(gd._default_device(denoise_fn) if device is None else device)
     with _device_ctx(device):
-        x_t = x_0.to(device=device, dtype=torch.float32).contiguous().clone()
-        B, C = x_t.shape[:2]
-        HW = x_t.shape[2] * x_t.shape[3]
-        cfg, y_in = _guided_rows(gd, label, device)
-        rows = B * (1 + cfg)
-        mot, clip = _hip.OUT_TYPES[gd.model_out_type], bool(clip_denoised)
-        hist = torch.zeros_like(x_t)
-        x_next = torch.empty_like(x_t)
-        x_in = x_t.repeat_interleave(2, dim=0) if cfg else x_t
-        x_in_next = torch.empty_like(x_in) if cfg else None
-        with _fixed_weights(denoise_fn):
+        ch = Chain(gd, denoise_fn, x_0.to(device=device, dtype=torch.float32).contiguous().clone(), label, device)
+        clip = bool(clip_denoised)
+        hist = torch.zeros_like(ch.x)
+        with ch.fixed_weights():
             for i in range(steps if stop is None else int(stop)):
-                t_in = torch.full((rows,), float(t_net[i]), dtype=F64, device=device)
-                out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
-                _hip.solver_step(x_t, out, hist, table[i].tolist(), mot, cfg, clip, x_next, x_in_next, B, C, HW)
-                x_t, x_next = x_next, x_t
-                if cfg:
-                    x_in, x_in_next = x_in_next, x_in
-                else:
-                    x_in = x_t
-        return x_t
+                _hip.solver_step(ch.x, ch.net(float(t_net[i])), hist, table[i].tolist(), ch.mot, ch.cfg, clip, *ch.dst, ch.B, ch.C, ch.HW)
+                ch.advance()
+        return ch.x
 
 
 # ------------------------------------------------------------------------------------------------ DDPM noise-space inversion
-def _chain_length(gd, start):
-    T = gd.sample_timesteps
-    if start is None:
-        return T
-    if isinstance(start, bool) or not isinstance(start, numbers.Integral) or not 1 <= start <= T:
-        raise ValueError(f"start must be an integer in [1, {T}], got {start!r}")
-    return int(start)
-
-
 def _ddpm_rows(gd, Tc, clip):
     """[(the 8 floats of vd_sample_step, the network time)] of the DDPM steps landing on i = 0 ... Tc - 1, each noisy step's scale checked"""
     rows = [gd._step_coefs(i, False, clip) for i in range(Tc)]
@@ -155,9 +102,9 @@ def _ddpm_rows(gd, Tc, clip):
 
 def p_invert_noise(gd, denoise_fn, x_0, label=None, device=None, seed=None, start=None, clip_denoised=True):
     """the chain of ``GaussianDiffusion.p_invert_noise`` (see there); returns (x_start, maps) on the device"""
-    _refuse_variants(gd, "noise-space inversion (that chain expands perturbations ~300x: a replay would not reconstruct)")
-    _image_batch("x_0", x_0)
-    Tc = _chain_length(gd, start)
+    refuse_variants(gd, "noise-space inversion (that chain expands perturbations ~300x: a replay would not reconstruct)")
+    image_batch("x_0", x_0)
+    Tc = chain_length(gd, start)
     clip = bool(clip_denoised)
     rows = _ddpm_rows(gd, Tc, clip)
     _need_cuda(x_0, "p_invert_noise")
@@ -168,33 +115,29 @@ def p_invert_noise(gd, denoise_fn, x_0, label=None, device=None, seed=None, star
         x_0 = x_0.to(device=device, dtype=torch.float32).contiguous()
         shape = tuple(x_0.shape)
         draw = lambda: torch.randn(shape, device=device, generator=generator)
-        B, C = shape[:2]
-        HW = shape[2] * shape[3]
-        cfg, y_in = _guided_rows(gd, label, device)
-        nrows = B * (1 + cfg)
-        mot = _hip.OUT_TYPES[gd.model_out_type]
         maps = torch.empty((Tc,) + shape, dtype=torch.float32, device=device)
         x_start = torch.empty_like(x_0)
-        x_in = torch.empty((nrows,) + shape[1:], dtype=torch.float32, device=device) if cfg else None
-        _hip.forward_jump(x_0, draw(), known_coefs(fn, T, Tc), x_start, x_in, B, C * HW)        # x_Tc = alpha x_0 + sigma eps_Tc
-        x_t = x_start.clone()                                      # the working state is rewritten in place; x_start is returned
-        with _fixed_weights(denoise_fn):
+        ch = Chain(gd, denoise_fn, x_start, label, device, in_place=True, dup=False)
+        B, C, HW = ch.B, ch.C, ch.HW
+        _hip.forward_jump(x_0, draw(), known_coefs(fn, T, Tc), *ch.dst, B, C * HW)             # x_Tc = alpha x_0 + sigma eps_Tc
+        ch.x = x_start.clone()                                     # the working state is rewritten in place; x_start is returned
+        with ch.fixed_weights():
             for i in reversed(range(Tc)):                          # the step landing on i, from the state at i + 1
                 k8, t_net = rows[i]
                 eps = draw() if i > 0 else None
-                t_in = torch.full((nrows,), t_net, dtype=F64, device=device)
-                out = denoise_fn(x_in if cfg else x_t, t_in, y_in).to(torch.float32).contiguous()
+                out = ch.net(t_net)
                 k10 = list(k8) + list(known_coefs(fn, T, i))
                 if i == 0:
                     k10[5] = 1.0                                   # the residual x_0 - x0_hat: scale 1, (ak, bk) = (1, 0), no draw
-                _hip.noise_extract(x_t, out, x_0, eps, k10, mot, cfg, i == 0, clip, x_t, maps[i], x_in if i > 0 else None, B, C, HW)
+                _hip.noise_extract(ch.x, out, x_0, eps, k10, ch.mot, ch.cfg, i == 0, clip, ch.x, maps[i], ch.x_in if i > 0 else None,
+                                   B, C, HW)
         return x_start, maps
 
 
 def p_sample_replay(gd, denoise_fn, x_start, maps, label=None, device=None, clip_denoised=True):
     """the chain of ``GaussianDiffusion.p_sample_replay`` (see there); returns the final image batch on the device"""
-    _refuse_variants(gd, "the replay of noise maps")
-    _image_batch("x_start", x_start)
+    refuse_variants(gd, "the replay of noise maps")
+    image_batch("x_start", x_start)
     T = gd.sample_timesteps
     if not torch.is_tensor(maps) or maps.dim() != 5 or tuple(maps.shape[1:]) != tuple(x_start.shape) or not 1 <= maps.shape[0] <= T:
         raise ValueError(f"maps must have shape (Tc, {', '.join(str(v) for v in x_start.shape)}) with 1 <= Tc <= {T}, got "
@@ -206,29 +149,17 @@ def p_sample_replay(gd, denoise_fn, x_start, maps, label=None, device=None, clip
     _need_cuda(maps, "p_sample_replay")
     device = torch.device(gd._default_device(denoise_fn) if device is None else device)
     with _device_ctx(device):
-        x_t = x_start.to(device=device, dtype=torch.float32).contiguous().clone()
+        ch = Chain(gd, denoise_fn, x_start.to(device=device, dtype=torch.float32).contiguous().clone(), label, device)
         maps = maps.to(device=device, dtype=torch.float32).contiguous()
-        B, C = x_t.shape[:2]
-        HW = x_t.shape[2] * x_t.shape[3]
-        cfg, y_in = _guided_rows(gd, label, device)
-        nrows = B * (1 + cfg)
-        mot = _hip.OUT_TYPES[gd.model_out_type]
-        x_next = torch.empty_like(x_t)
-        x_in = x_t.repeat_interleave(2, dim=0) if cfg else None
-        x_in_next = torch.empty_like(x_in) if cfg else None
-        with _fixed_weights(denoise_fn):
+        with ch.fixed_weights():
             for i in reversed(range(Tc)):
                 k8, t_net = rows[i]
                 k8 = list(k8)
                 if i == 0:
                     k8[5] = 1.0                                    # vd_sample_step adds k[5]*noise also on the last step: the residual
-                t_in = torch.full((nrows,), t_net, dtype=F64, device=device)
-                out = denoise_fn(x_in if cfg else x_t, t_in, y_in).to(torch.float32).contiguous()
-                _hip.sample_step(x_t, out, maps[i], k8, mot, cfg, i == 0, clip, x_next, x_in_next, B, C, HW)
-                x_t, x_next = x_next, x_t
-                if cfg:
-                    x_in, x_in_next = x_in_next, x_in
-        return x_t
+                _hip.sample_step(ch.x, ch.net(t_net), maps[i], k8, ch.mot, ch.cfg, i == 0, clip, *ch.dst, ch.B, ch.C, ch.HW)
+                ch.advance()
+        return ch.x
 
 
 # ------------------------------------------------------------------------------------------------ spherical interpolation

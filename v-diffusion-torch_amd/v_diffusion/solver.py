@@ -23,14 +23,13 @@ g = x_c + w (x_c - x_u) still reaches 1 + 2w.  ``clip_denoised="dynamic"`` is Im
 the "higher" order statistic -- a value of the sample, found exactly by a radix select inside the step's one launch
 (vd_solver_step_dyn) -- where Imagen interpolates a percentile; the two differ by at most the gap between neighbouring order statistics.
 """
-import contextlib
 import math
-from collections import OrderedDict
 
 import torch
 import torch.nn.functional as F
 
 from . import _hip
+from .chain import Chain, captured_step, refuse_variants
 from .diffusion import F64, _device_ctx, _pred_coefs, logsnr_to_posterior_ddim, stable_log1mexp
 
 # columns of the coefficient table (include/vdiff_hip.h, vd_solver_step)
@@ -176,47 +175,6 @@ def dynamic_threshold(x, quantile=0.995, max_value=None):
         return torch.maximum(torch.minimum(xc, sb), -sb) / sb, s
 
 
-def _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device):
-    """(graph, state, pinned packs) of one reverse step -- network forward + the step's launch on device-resident coefficients -- from
-    this object's own small LRU cache.  ``clip`` is ``_clip_mode``'s: the rank and the cap of the dynamic threshold are launch
-    arguments, not table data, so they are part of the key."""
-    B, C = shape[0], shape[1]
-    HW = int(shape[2]) * int(shape[3])
-    mot = _hip.OUT_TYPES[gd.model_out_type]
-    key = ("solver", id(denoise_fn), tuple(shape), bool(cfg), clip, gd.model_out_type, None if y_in is None else tuple(y_in.shape),
-           hash(tuple(p.data_ptr() for p in net.parameters())) if isinstance(net, torch.nn.Module) else None)
-    cache = gd.__dict__.setdefault("_solver_graphs", OrderedDict())
-    entry = cache.get(key)
-    if entry is not None:
-        cache.move_to_end(key)
-        return entry
-    rows = B * (1 + cfg)
-    st = dict(x=torch.zeros(shape, dtype=torch.float32, device=device),
-              hist=torch.zeros(shape, dtype=torch.float32, device=device),
-              t=torch.zeros((rows,), dtype=F64, device=device),
-              k=torch.zeros((K,), dtype=torch.float32, device=device),
-              y=None if y_in is None else torch.zeros_like(y_in))
-    st["xin"] = torch.zeros((rows,) + tuple(shape[1:]), dtype=torch.float32, device=device) if cfg else st["x"]
-
-    def body():
-        out = denoise_fn(st["xin"], st["t"], st["y"]).to(torch.float32).contiguous()
-        _step(clip, st["x"], out, st["hist"], None, mot, cfg, st["x"], st["xin"] if cfg else None, B, C, HW, k_dev=st["k"])
-    side = torch.cuda.Stream(device)
-    side.wait_stream(torch.cuda.current_stream(device))
-    with torch.cuda.stream(side):                  # warm-up outside capture (lazy initialisation, workspace growth)
-        body()
-    torch.cuda.current_stream(device).wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        body()
-    # the graph's pack / convolution nodes hold raw pointers into the forward's ConvPacks: the entry keeps that object alive
-    eng = net.engine() if hasattr(net, "engine") else None
-    while len(cache) >= GRAPH_CACHE_MAX:
-        cache.popitem(last=False)
-    entry = cache[key] = (graph, st, None if eng is None else eng.packs)
-    return entry
-
-
 def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=2, spacing="time",
                     clip_denoised=True, use_graph=False, dynamic_quantile=0.995, dynamic_max=None):
     """the reverse chain of ``GaussianDiffusion.p_sample_solver`` (see there); returns the final image batch on the device"""
@@ -224,10 +182,7 @@ def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, 
     _check(steps, order)
     shape = tuple(shape)
     clip = _clip_mode(clip_denoised, int(shape[1]) * int(shape[2]) * int(shape[3]), dynamic_quantile, dynamic_max)
-    if gd.model_var_type == "learned":
-        raise NotImplementedError("model_var_type='learned'")
-    if gd.x0eps_coef:
-        raise NotImplementedError("x0eps_coef=True with the multistep solver")
+    refuse_variants(gd, "the multistep solver")
     device = torch.device(gd._default_device(denoise_fn) if device is None else device)
     with _device_ctx(device):
         generator = None if seed is None else torch.Generator(device).manual_seed(seed)
@@ -235,48 +190,27 @@ def p_sample_solver(gd, denoise_fn, shape, noise=None, label=None, device=None, 
             x_t = torch.randn(shape, device=device, generator=generator)      # the only draw: p_sample's x_T for this seed
         else:
             x_t = noise.to(device=device, dtype=torch.float32).contiguous().clone()
-        if label is not None:
-            label = label.to(device)
-        cfg = gd._use_cfg(label)
-        if cfg:
-            y_in = label.repeat_interleave(2, dim=0).clone()
-            y_in[1::2] = 0                                                     # unconditional rows, as _sample_loop builds them
-        else:
-            y_in = label
-        B, C = shape[0], shape[1]
-        HW = int(shape[2]) * int(shape[3])
-        rows = B * (1 + cfg)
-        net = getattr(denoise_fn, "module", denoise_fn)
         if use_graph:
-            graph, st, _ = _graph_entry(gd, denoise_fn, net, shape, y_in, cfg, clip, device)
-            st["x"].copy_(x_t)
+            # one reverse step -- network forward + the step's launch on device-resident coefficients -- from this object's own small
+            # LRU cache.  The rank and the cap of the dynamic threshold are launch arguments, not table data: ``clip`` is part of the key
+            def launch(ch, st, out):
+                _step(clip, ch.x, out, st["hist"], None, ch.mot, ch.cfg, *ch.dst, ch.B, ch.C, ch.HW, k_dev=st["k"])
+            graph, st, _ = captured_step(gd.__dict__.setdefault("_solver_graphs", {}), GRAPH_CACHE_MAX, gd, denoise_fn, shape, label, device,
+                                         launch, key=(clip,), bufs=("hist",))
+            st["chain"].load(x_t, label)
             st["hist"].zero_()
-            if cfg:
-                st["xin"].copy_(x_t.repeat_interleave(2, dim=0))
-            if y_in is not None:
-                st["y"].copy_(y_in)
             table, t_net = solver_coefs(gd.logsnr_fn, steps, order, spacing, gd.model_out_type, gd.w_guide)
             ktab, t_net = table.to(device), t_net.tolist()
             for i in reversed(range(steps)):
                 st["t"].fill_(t_net[i])
                 st["k"].copy_(ktab[i])
                 graph.replay()
-            return st["x"].clone()
-        mot = _hip.OUT_TYPES[gd.model_out_type]
+            return st["chain"].x.clone()
+        ch = Chain(gd, denoise_fn, x_t, label, device)
         hist = torch.zeros_like(x_t)
-        x_next = torch.empty_like(x_t)
-        x_in = x_t.repeat_interleave(2, dim=0) if cfg else x_t
-        x_in_next = torch.empty_like(x_in) if cfg else None
         tau = _grid(gd.logsnr_fn, steps, spacing)
-        eng = net.engine() if hasattr(net, "engine") else None
-        with (eng.fixed_weights() if eng is not None else contextlib.nullcontext()):   # the weights do not change inside one chain
+        with ch.fixed_weights():
             for k8, t_net in _rows(gd.logsnr_fn, tau, order, gd.model_out_type, gd.w_guide):      # solver_coefs' rows, last one first
-                t_in = torch.full((rows,), t_net, dtype=F64, device=device)
-                out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
-                _step(clip, x_t, out, hist, k8.tolist(), mot, cfg, x_next, x_in_next, B, C, HW)
-                x_t, x_next = x_next, x_t
-                if cfg:
-                    x_in, x_in_next = x_in_next, x_in
-                else:
-                    x_in = x_t
-        return x_t
+                _step(clip, ch.x, ch.net(t_net), hist, k8.tolist(), ch.mot, ch.cfg, *ch.dst, ch.B, ch.C, ch.HW)
+                ch.advance()
+        return ch.x
