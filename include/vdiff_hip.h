@@ -413,6 +413,36 @@ int vd_bpd_bwd(const float* x0, const float* xt, const float* out, const float* 
 int vd_sample_step(const float* xt, const float* out, const float* noise, const float* k, const float* k_dev,
                    int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip,
                    float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* ---- learned variances (model_var_type "learned"; Nichol & Dhariwal 2021, the intent of diffusion.py:320-324 with the tensor intp_frac
+ * of logsnr_to_posterior :155).  The network output has Cp + C channels: Cp = C (2C for "both") prediction channels, then C channels nu.
+ * Per element frac = sigmoid(nu), logvar = lvmin + frac*delta, with lvmin the fixed_small (= true posterior) log-variance of the step and
+ * delta = lvmax - lvmin = logsigmoid(-logsnr_t) - logsigmoid(-logsnr_s) >= 0, both formed on the host in fp64 and rounded once.
+ * No atomics in any of the five: the same call gives the same bits. */
+/* vd_bpd_terms for such an output: coef[n][8] = {a0, b0x, b0e, c1, c2, lvmin, delta, a0 - 1}; kl, nll, pred, mse as there, with
+ * kl_e = 0.5(-1 - d + e^d + (c2 (x0_hat - x0))^2 e^-logvar), d = lvmin - logvar, and exp(-logvar/2) scaling the decoder's CDF arguments */
+int vd_bpd_terms_lv(const float* x0, const float* xt, const float* out, const float* coef, int32_t model_out_type, int32_t clip,
+                    float* kl, float* nll, float* pred, float* mse, int32_t n, int32_t C, int32_t HW, void* stream);
+/* dout [n][Cp + C][HW] = gloss[b] * d (use_kl[b] != 0 ? kl[b] : nll[b]) / d out.  mean_grad = 0 writes exact zeros to the prediction
+ * channels (the stop-gradient of the hybrid loss); the nu channels do not depend on mean_grad.  Under clip a clamped pixel passes no
+ * gradient to the prediction channels and still passes one to nu. */
+int vd_bpd_bwd_lv(const float* x0, const float* xt, const float* out, const float* coef, const float* use_kl, const float* gloss,
+                  int32_t model_out_type, int32_t clip, int32_t mean_grad, float* dout, int32_t n, int32_t C, int32_t HW, void* stream);
+/* hybrid loss, one launch each way: loss[b] = mse_b + vlb_weight * (use_kl[b] != 0 ? kl_b : nll_b), mse_b = vd_loss_fwd's value on the
+ * prediction channels (every reweight), the bound term vd_bpd_terms_lv's without clipping.  aux[n][4] = {the two snr_trunc means, kl_b,
+ * nll_b}.  The backward writes all Cp + C channels: the prediction channels take gloss[b] * d mse_b / d out alone (the bound term's mean
+ * is a constant), the nu channels vlb_weight * gloss[b] * d term_b / d nu. */
+int vd_hybrid_loss_fwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr, const float* coef,
+                       const float* use_kl, int32_t model_out_type, int32_t reweight, float vlb_weight, float* loss, float* aux,
+                       int32_t n, int32_t C, int32_t HW, void* stream);
+int vd_hybrid_loss_bwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr, const float* coef,
+                       const float* use_kl, const float* aux, const float* gloss, int32_t model_out_type, int32_t reweight,
+                       float vlb_weight, float* dout, int32_t n, int32_t C, int32_t HW, void* stream);
+/* vd_sample_step for such an output (n*(1+cfg) rows of Cp + C channels).  k: 10 HOST floats {a0, b0x, b0e, c1, c2, lvmin, w_guide, c3,
+ * delta, 0}; the guided mean is vd_sample_step's, and xn = mean + exp(0.5 (lvmin + delta*sigmoid(nu))) * noise with nu of the
+ * CONDITIONAL row (diffusion.py:386-387) when noise is given and last_step = 0; noise = null gives vd_sample_step's bits on the
+ * prediction channels.  Wide (dwordx4) when C*HW % 4 == 0 and every base is 16-byte aligned, else scalar; the two agree bit for bit. */
+int vd_sample_step_lv(const float* xt, const float* out, const float* noise, const float* k, int32_t model_out_type, int32_t cfg,
+                      int32_t last_step, int32_t clip, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
 /* progressive distillation (Salimans & Ho 2022): a student with N sampling steps regresses, in x-space, on the result of two
  * deterministic DDIM steps of a teacher on the 2N grid, t -> t' = t - 1/(2N) -> t'' = t - 1/N.  Three launches around the two teacher
  * forwards and the student forward.  coef[n][20] (device), per sample, computed on the host in fp64 from the fp32-rounded

@@ -3,6 +3,7 @@
 //   train_loss (mse) forward/backward  diffusion.py:466-490,520-541 ; flat_mean functions.py:102-104
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
+//   learned variances (bound terms, hybrid loss, reverse step for outputs with variance channels)  the intent of diffusion.py:320-324
 //   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
 //   jump, the noise-map extraction of DDPM inversion and spherical interpolation: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
@@ -210,6 +211,219 @@ __global__ void bpd_bwd_kernel(const BpdArgs p, const float* use_kl, const float
     }
 }
 
+// ---- learned variances (Nichol & Dhariwal 2021; the reference's intent at diffusion.py:320-324 with logsnr_to_posterior :155): the
+// network output has C more channels nu after its Cp = C (2C for "both") prediction channels, and per element
+//   frac = sigmoid(nu),  logvar = lvmin + frac*delta,  d = lvmin - logvar = -frac*delta
+// with lvmin the fixed_small (= true posterior) log-variance of the step and delta = lvmax - lvmin >= 0, both host fp64, rounded once.
+// frac and 1 - frac are each formed without cancellation, so d logvar / d nu = delta*frac*(1 - frac) keeps its digits where the
+// sigmoid saturates.
+struct LvFrac { float frac, omf; };
+
+__device__ __forceinline__ LvFrac lv_frac(float nu) {
+    const float e = expf(-fabsf(nu)), big = 1.f / (1.f + e), small = e * big;
+    return nu >= 0.f ? LvFrac{big, small} : LvFrac{small, big};
+}
+
+// written once, contraction off: the reverse step's wide and scalar forms and the bound-term kernels see the same bits
+__device__ __forceinline__ float lv_logvar(float lvmin, float delta, float frac) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(frac, delta, lvmin);
+}
+
+// coef[b][8] = {a0, b0x, b0e, c1, c2, lvmin, delta, a0 - 1}
+struct LvCoef { float a0, b0x, b0e, c1, c2, lvmin, delta, a0m1; };
+
+__device__ __forceinline__ LvCoef lv_coef(const float* k) { return {k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7]}; }
+
+// what forward and backward share of one element: x0_hat (clipped when asked), dx = x0_hat - x0 in the well-conditioned form of
+// bpd_terms_kernel, the variance, and the two CDFs of the decoder with their arguments
+struct LvElem {
+    float x0h, dx, frac, omf, d, em, inv, zu, zl, tu, tl, D; bool live;
+};
+
+__device__ __forceinline__ LvElem lv_elem(const LvCoef& q, int type, int clip, float x0, float xt, float o, float oe, float nu) {
+    LvElem r;
+    r.x0h = q.a0 * xt + q.b0x * o + (type == OUT_BOTH ? q.b0e * oe : 0.f);
+    r.dx = fmaf(q.b0e, type == OUT_BOTH ? oe : 0.f, fmaf(q.b0x, o, fmaf(q.a0m1, xt, xt - x0)));
+    r.live = true;                                            // the clamp passes no gradient to the mean outside [-1, 1]
+    if (clip && (r.x0h < -1.f || r.x0h > 1.f)) { r.x0h = fminf(fmaxf(r.x0h, -1.f), 1.f); r.dx = r.x0h - x0; r.live = false; }
+    const LvFrac f = lv_frac(nu);
+    const float lv = lv_logvar(q.lvmin, q.delta, f.frac);
+    r.frac = f.frac; r.omf = f.omf;
+    r.d = q.lvmin - lv;
+    r.em = expf(-lv);
+    r.inv = expf(-0.5f * lv);
+    r.zu = r.inv * (BPD_PREC - r.dx);                         // x0 - x0_hat = -dx
+    r.zl = r.inv * (-BPD_PREC - r.dx);
+    r.tu = tanhf(CDF_K * (r.zu + CDF_C * r.zu * r.zu * r.zu));
+    r.tl = tanhf(CDF_K * (r.zl + CDF_C * r.zl * r.zl * r.zl));
+    const float cu = x0 > BPD_CUT ? 1.f : 0.5f * (1.f + r.tu);
+    const float cl = x0 < -BPD_CUT ? 0.f : 0.5f * (1.f + r.tl);
+    r.D = cu - cl - BPD_TOL;
+    return r;
+}
+
+// KL element 0.5(-1 - d + e^d + (mean difference)^2 e^-logvar), the mean difference being c2*dx; -1 - d + e^d as expm1(d) - d
+__device__ __forceinline__ float lv_kl(const LvCoef& q, const LvElem& r) {
+    const float dm = q.c2 * r.dx;
+    return 0.5f * ((expm1f(r.d) - r.d) + dm * dm * r.em);
+}
+
+__device__ __forceinline__ float lv_nll(const LvElem& r) { return -logf(fmaxf(r.D, 0.f) + BPD_TOL); }
+
+// d term_e / d x0_hat (gx) and d term_e / d nu (gnu) of the KL (ukl) or the decoder NLL element
+__device__ __forceinline__ void lv_grads(const LvCoef& q, const LvElem& r, float x0, bool ukl, float& gx, float& gnu) {
+    float gl;                                                 // d term_e / d logvar
+    if (ukl) {
+        const float dm = q.c2 * r.dx;
+        gx = q.c2 * dm * r.em;
+        gl = 0.5f * (-expm1f(r.d) - dm * dm * r.em);
+    } else {
+        // cdf'(z) = 0.5 (1 - tanh^2) K (1 + 3 C z^2);  d z / d x0_hat = -inv,  d z / d logvar = -z/2
+        const float pu = x0 > BPD_CUT ? 0.f : 0.5f * (1.f - r.tu * r.tu) * CDF_K * (1.f + 3.f * CDF_C * r.zu * r.zu);
+        const float pl = x0 < -BPD_CUT ? 0.f : 0.5f * (1.f - r.tl * r.tl) * CDF_K * (1.f + 3.f * CDF_C * r.zl * r.zl);
+        const float rD = r.D >= 0.f ? 1.f / (r.D + BPD_TOL) : 0.f;
+        gx = (pu - pl) * r.inv * rD;
+        gl = 0.5f * (pu * r.zu - pl * r.zl) * rD;
+    }
+    gnu = gl * q.delta * r.frac * r.omf;
+}
+
+// vd_bpd_terms for an output of Cp + C channels.  One workgroup per sample
+__global__ __launch_bounds__(256) void bpd_terms_lv_kernel(const BpdArgs p, float* kl, float* nll, float* pred, float* mse) {
+    __shared__ float sh[8];
+    const int b = blockIdx.x;
+    const LvCoef q = lv_coef(p.coef + 8 * b);
+    const long long N = (long long)p.C * p.HW, Np = p.type == OUT_BOTH ? 2 * N : N;
+    const float* ob = p.out + (long long)b * (Np + N);
+    float s_kl = 0.f, s_nll = 0.f, s_mse = 0.f;
+    for (long long i = threadIdx.x; i < N; i += blockDim.x) {
+        const float x0 = p.x0[(long long)b * N + i], xt = p.xt[(long long)b * N + i];
+        const LvElem r = lv_elem(q, p.type, p.clip, x0, xt, ob[i], p.type == OUT_BOTH ? ob[N + i] : 0.f, ob[Np + i]);
+        s_kl += lv_kl(q, r);
+        s_nll += lv_nll(r);
+        s_mse += r.dx * r.dx;
+        if (pred) pred[(long long)b * N + i] = r.x0h;
+    }
+    s_kl = block_sum(s_kl, sh);
+    s_nll = block_sum(s_nll, sh);
+    s_mse = block_sum(s_mse, sh);
+    if (threadIdx.x == 0) {
+        const float sc = 1.f / ((float)N * 0.6931471805599453f);
+        kl[b] = s_kl * sc; nll[b] = s_nll * sc;
+        if (mse) mse[b] = s_mse / (float)N;
+    }
+}
+
+// dout (Cp + C channels) = gloss[b] * d (use_kl[b] ? kl_b : nll_b) / d out; without mean_grad the prediction channels are zeros
+__global__ void bpd_bwd_lv_kernel(const BpdArgs p, const float* use_kl, const float* gloss, int mean_grad, float* dout) {
+    const long long N = (long long)p.C * p.HW, total = (long long)p.n * N, Np = p.type == OUT_BOTH ? 2 * N : N;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const long long b = idx / N, i = idx % N;
+        const LvCoef q = lv_coef(p.coef + 8 * b);
+        const float* ob = p.out + b * (Np + N);
+        float* db = dout + b * (Np + N);
+        const float x0 = p.x0[idx];
+        const LvElem r = lv_elem(q, p.type, p.clip, x0, p.xt[idx], ob[i], p.type == OUT_BOTH ? ob[N + i] : 0.f, ob[Np + i]);
+        float gx, gnu;
+        lv_grads(q, r, x0, use_kl[b] != 0.f, gx, gnu);
+        const float sc = gloss[b] / ((float)N * 0.6931471805599453f);
+        const float g = mean_grad && r.live ? sc * gx : 0.f;
+        db[i] = g * q.b0x;
+        if (p.type == OUT_BOTH) db[N + i] = g * q.b0e;
+        db[Np + i] = sc * gnu;
+    }
+}
+
+// ---- hybrid loss (Nichol & Dhariwal 2021, eq. 16): loss_b = mse_b + vlb * (use_kl[b] ? kl_b : nll_b), mse_b loss_fwd_kernel's on the
+// prediction channels and the bound term bpd_terms_lv_kernel's without clipping, whose mean is a constant to the gradient.
+// aux[b][4] = {the two snr_trunc means, kl_b, nll_b}.
+// The mse part is loss_fwd_kernel's and loss_bwd_kernel's expression per element, restated as values (those two kernels keep their own
+// text: their bits are pinned by the training parity checks): the squared errors one element adds (e1: the eps error of snr_trunc,
+// else 0) and their gradient g * d e / d out (ge: for the second half of a "both" output).
+struct SqErr { float e0, e1; };
+struct OutGrad { float gx, ge; };
+
+__device__ __forceinline__ SqErr loss_sq(int rw, const PredCoef& k, float sa, float ss, float x0, float ep, float xt, float o, float oe) {
+    if (rw == RW_SNR_TRUNC) {
+        const float x0h = k.a0 * xt + k.b0x * o + k.b0e * oe;
+        const float eph = k.a1 * xt + k.b1x * o + k.b1e * oe;
+        return {(x0 - x0h) * (x0 - x0h), (ep - eph) * (ep - eph)};
+    }
+    const float tgt = rw == RW_CONSTANT ? x0 : (rw == RW_SNR ? ep : (-x0 * ss + ep * sa));
+    return {(tgt - o) * (tgt - o), 0.f};
+}
+
+__device__ __forceinline__ OutGrad loss_grad(int rw, const PredCoef& k, float sa, float ss, bool eps_branch, float g, float x0, float ep,
+                                             float xt, float o, float oe) {
+    if (rw == RW_SNR_TRUNC) {
+        float r, bx, be;
+        if (!eps_branch) { r = (k.a0 * xt + k.b0x * o + k.b0e * oe) - x0; bx = k.b0x; be = k.b0e; }
+        else             { r = (k.a1 * xt + k.b1x * o + k.b1e * oe) - ep; bx = k.b1x; be = k.b1e; }
+        return {g * r * bx, g * r * be};
+    }
+    const float tgt = rw == RW_CONSTANT ? x0 : (rw == RW_SNR ? ep : (-x0 * ss + ep * sa));
+    return {g * (o - tgt), 0.f};
+}
+
+// one workgroup per sample
+__global__ __launch_bounds__(256) void hybrid_fwd_kernel(const LossArgs p, const float* coef, const float* use_kl, float vlb, float* loss,
+                                                         float* aux) {
+    __shared__ float sh[8];
+    const int b = blockIdx.x;
+    const float l = p.logsnr[b];
+    const PredCoef k = pred_coef(p.type, l);
+    const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+    const LvCoef q = lv_coef(coef + 8 * b);
+    const long long N = (long long)p.C * p.HW, Np = p.type == OUT_BOTH ? 2 * N : N;
+    const float* ob = p.out + (long long)b * (Np + N);
+    float e0 = 0.f, e1 = 0.f, s_kl = 0.f, s_nll = 0.f;
+    for (long long i = threadIdx.x; i < N; i += blockDim.x) {
+        const long long idx = (long long)b * N + i;
+        const float x0 = p.x0[idx], xt = p.xt[idx], o = ob[i], oe = p.type == OUT_BOTH ? ob[N + i] : 0.f;
+        const SqErr m = loss_sq(p.rw, k, sa, ss, x0, p.eps[idx], xt, o, oe);
+        e0 += m.e0; e1 += m.e1;
+        const LvElem r = lv_elem(q, p.type, 0, x0, xt, o, oe, ob[Np + i]);
+        s_kl += lv_kl(q, r);
+        s_nll += lv_nll(r);
+    }
+    e0 = block_sum(e0, sh);
+    e1 = block_sum(e1, sh);
+    s_kl = block_sum(s_kl, sh);
+    s_nll = block_sum(s_nll, sh);
+    if (threadIdx.x == 0) {
+        const float m0 = e0 / (float)N, m1 = e1 / (float)N, sc = 1.f / ((float)N * 0.6931471805599453f);
+        const float kl = s_kl * sc, nll = s_nll * sc;
+        aux[4 * b] = m0; aux[4 * b + 1] = m1; aux[4 * b + 2] = kl; aux[4 * b + 3] = nll;
+        loss[b] = (p.rw == RW_SNR_TRUNC ? fmaxf(m0, m1) : m0) + vlb * (use_kl[b] != 0.f ? kl : nll);
+    }
+}
+
+// the whole gradient in one pass: the prediction channels take the mse gradient alone, the nu channels vlb * gloss[b] * d term_b / d nu
+__global__ void hybrid_bwd_kernel(const LossArgs p, const float* coef, const float* use_kl, float vlb, const float* aux, const float* gloss,
+                                  float* dout) {
+    const long long N = (long long)p.C * p.HW, total = (long long)p.n * N, Np = p.type == OUT_BOTH ? 2 * N : N;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
+         idx += (long long)gridDim.x * blockDim.x) {
+        const long long b = idx / N, i = idx % N;
+        const float l = p.logsnr[b];
+        const PredCoef k = pred_coef(p.type, l);
+        const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+        const LvCoef q = lv_coef(coef + 8 * b);
+        const float* ob = p.out + b * (Np + N);
+        float* db = dout + b * (Np + N);
+        const float x0 = p.x0[idx], xt = p.xt[idx], o = ob[i], oe = p.type == OUT_BOTH ? ob[N + i] : 0.f;
+        const LvElem r = lv_elem(q, p.type, 0, x0, xt, o, oe, ob[Np + i]);
+        float gx, gnu;
+        lv_grads(q, r, x0, use_kl[b] != 0.f, gx, gnu);
+        const OutGrad m = loss_grad(p.rw, k, sa, ss, !(aux[4 * b] >= aux[4 * b + 1]), gloss[b] * 2.f / (float)N, x0, p.eps[idx], xt, o, oe);
+        db[i] = m.gx;
+        if (p.type == OUT_BOTH) db[N + i] = m.ge;
+        db[Np + i] = vlb * gloss[b] / ((float)N * 0.6931471805599453f) * gnu;
+    }
+}
+
 inline int grid_for(long long total) {
     long long g = (total + 255) / 256;
     if (g > 4096) g = 4096;
@@ -236,7 +450,7 @@ template <int V> __device__ __forceinline__ void st_dup(float* xn, float* xdup, 
 
 // ---- what the reverse-step kernels share: the product sampler's step, the DPM-Solver++ step and its thresholded form, the RePaint step
 // and the noise extraction of DDPM inversion.  Each takes the state xt (n rows of N = C*HW floats) and a network output of n*(1+cfg)
-// rows, cond and uncond interleaved (diffusion.py:369-372), of N floats or, for "both", 2N; each forms a value per branch, guides it,
+// rows, cond and uncond interleaved (diffusion.py:369-372), of N floats or, for "both", 2N (the row stride may be larger); each forms a value per branch, guides it,
 // and writes xn and (optional) xdup.  The coefficients come as host floats copied into the kernel argument or, to keep the launch
 // HIP-graph replayable, as a device pointer.
 struct Coefs { float k[10]; const float* kdev; };
@@ -245,6 +459,7 @@ __device__ __forceinline__ const float* coefs(const Coefs& c) { return c.kdev ? 
 
 struct StepCommon {
     const float* xt; const float* out; Coefs c; int type, cfg, last, clip; float* xn; float* xdup; int n; long long N;
+    long long row;      // floats per row of out: N, for "both" 2N, and N more when the network also gives the variance channels
 };
 
 // Every expression of these kernels is written once, with contraction off and the fused operations spelled out: the bits of a step are
@@ -318,7 +533,7 @@ template <int V, class F>
 __device__ __forceinline__ void guided(const StepCommon& s, long long b, long long i, float w, const float (&z)[V], const F& f,
                                        float (&g)[V]) {
     const bool both = s.type == OUT_BOTH;
-    const long long N = s.N, row = both ? 2 * N : N;
+    const long long N = s.N, row = s.row;
     const float* oc = s.out + b * (1 + s.cfg) * row + i;
     float o[V], oe[V] = {};
     ldv<V>(oc, o);
@@ -350,6 +565,36 @@ __global__ void sample_step_kernel(const StepArgs p) {
         guided<1>(s, b, i, w, z, f, v);
         if (p.noise) v[0] = axpby(1.f, v[0], nscale, p.noise[idx]);
         st_dup<1>(s.xn, s.xdup, b, N, i, v);
+    }
+}
+
+// the same step for a network with learned variances (s.row = prediction channels + N): k = {a0, b0x, b0e, c1, c2, lvmin, w_guide, c3,
+// delta, 0}, host floats only;  xn = guided mean_plain + exp(0.5 (lvmin + delta*sigmoid(nu))) * noise, nu the variance channels of the
+// CONDITIONAL row (diffusion.py:386-387), when noise is given and the step is not the last.  Without noise this is sample_step_kernel
+// on the prediction channels, bit for bit.
+__device__ __forceinline__ float lv_sigma(float lvmin, float delta, float nu) { return expf(0.5f * lv_logvar(lvmin, delta, lv_frac(nu).frac)); }
+
+template <int V>
+__global__ void sample_step_lv_kernel(const StepArgs p) {
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = s.c.k;
+    const StepMean<false> f = step_mean<false>(s, k);
+    const float lvmin = k[5], w = k[6], delta = k[8];
+    const bool noisy = p.noise && !s.last;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float z[V], v[V];
+        ldv<V>(s.xt + e, z);
+        guided<V>(s, b, i, w, z, f, v);
+        if (noisy) {
+            float nu[V], nz[V];
+            ldv<V>(s.out + b * (1 + s.cfg) * s.row + (s.row - N) + i, nu);
+            ldv<V>(p.noise + e, nz);
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = axpby(1.f, v[j], lv_sigma(lvmin, delta, nu[j]), nz[j]);
+        }
+        st_dup<V>(s.xn, s.xdup, b, N, i, v);
     }
 }
 
@@ -810,6 +1055,7 @@ inline StepCommon step_common(const float* xt, const float* out, int type, int c
     StepCommon s = {};
     s.xt = xt; s.out = out; s.type = type; s.cfg = cfg ? 1 : 0; s.last = last ? 1 : 0; s.clip = clip ? 1 : 0;
     s.xn = xn; s.xdup = xdup; s.n = n; s.N = (long long)C * HW;
+    s.row = (type == OUT_BOTH ? 2 : 1) * s.N;
     return s;
 }
 
@@ -889,6 +1135,73 @@ extern "C" int vd_bpd_bwd(const float* x0, const float* xt, const float* out, co
     hipLaunchKernelGGL(bpd_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, use_kl, gloss,
                        dout);
     VD_LAUNCH_CHECK("bpd_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_bpd_terms_lv(const float* x0, const float* xt, const float* out, const float* coef, int32_t type, int32_t clip,
+                               float* kl, float* nll, float* pred, float* mse, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_terms_lv: bad model_out_type %d", type);
+    VD_REQUIRE(x0 && xt && out && coef && kl && nll, "vd_bpd_terms_lv: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_bpd_terms_lv: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    BpdArgs p = {x0, xt, out, coef, type, clip ? 1 : 0, n, C, (long long)HW};
+    hipLaunchKernelGGL(bpd_terms_lv_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, kl, nll, pred, mse);
+    VD_LAUNCH_CHECK("bpd_terms_lv_kernel");
+    return 0;
+}
+
+extern "C" int vd_bpd_bwd_lv(const float* x0, const float* xt, const float* out, const float* coef, const float* use_kl,
+                             const float* gloss, int32_t type, int32_t clip, int32_t mean_grad, float* dout, int32_t n, int32_t C,
+                             int32_t HW, void* stream) {
+    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_bwd_lv: bad model_out_type %d", type);
+    VD_REQUIRE(x0 && xt && out && coef && use_kl && gloss && dout, "vd_bpd_bwd_lv: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_bpd_bwd_lv: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    BpdArgs p = {x0, xt, out, coef, type, clip ? 1 : 0, n, C, (long long)HW};
+    hipLaunchKernelGGL(bpd_bwd_lv_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, use_kl, gloss,
+                       (int)(mean_grad ? 1 : 0), dout);
+    VD_LAUNCH_CHECK("bpd_bwd_lv_kernel");
+    return 0;
+}
+
+// the refusals the two hybrid entries share
+static int hybrid_checks(const char* who, int type, int rw, bool ptrs, int n, int C, int HW) {
+    VD_REQUIRE(type >= 0 && type <= 3 && rw >= 0 && rw <= 3, "%s: bad model_out_type/reweight (%d,%d)", who, type, rw);
+    VD_REQUIRE(!(type == OUT_BOTH && rw != RW_SNR_TRUNC), "%s: 'both' output needs snr_trunc (reference shape rule)", who);
+    VD_REQUIRE(ptrs, "%s: null pointer", who);
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "%s: empty batch or image (n=%d, C=%d, HW=%d)", who, n, C, HW);
+    return 0;
+}
+
+extern "C" int vd_hybrid_loss_fwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
+                                  const float* coef, const float* use_kl, int32_t type, int32_t rw, float vlb_weight, float* loss,
+                                  float* aux, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_TRY(hybrid_checks("vd_hybrid_loss_fwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && loss && aux, n, C, HW));
+    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
+    hipLaunchKernelGGL(hybrid_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, coef, use_kl, vlb_weight, loss, aux);
+    VD_LAUNCH_CHECK("hybrid_fwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_hybrid_loss_bwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
+                                  const float* coef, const float* use_kl, const float* aux, const float* gloss, int32_t type, int32_t rw,
+                                  float vlb_weight, float* dout, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_TRY(hybrid_checks("vd_hybrid_loss_bwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && aux && gloss && dout, n, C, HW));
+    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
+    hipLaunchKernelGGL(hybrid_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, coef, use_kl,
+                       vlb_weight, aux, gloss, dout);
+    VD_LAUNCH_CHECK("hybrid_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_sample_step_lv(const float* xt, const float* out, const float* noise, const float* k, int32_t type, int32_t cfg,
+                                 int32_t last_step, int32_t clip, float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream) {
+    StepArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, HW), noise};
+    VD_REQUIRE(k != nullptr, "vd_sample_step_lv: the ten coefficients are host floats (no device form)");
+    VD_TRY(step_checks("vd_sample_step_lv", p.s, k, nullptr, 10, xt && out && xn, C, HW));
+    VD_TRY(dup_is_guided("vd_sample_step_lv", p.s));
+    p.s.row += p.s.N;                                         // the variance channels follow the prediction channels
+    launch_elems(sample_step_lv_kernel<4>, sample_step_lv_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, xn, xdup), n * p.s.N,
+                 stream, p);
+    VD_LAUNCH_CHECK("sample_step_lv_kernel");
     return 0;
 }
 

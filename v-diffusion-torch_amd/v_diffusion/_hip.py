@@ -122,6 +122,11 @@ _SIGNATURES = {
     "vd_bpd_terms": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_bpd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vd_sample_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_bpd_terms_lv": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_bpd_bwd_lv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vd_hybrid_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_hybrid_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _i32, _i32, _vp]),
+    "vd_sample_step_lv": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
@@ -806,6 +811,36 @@ def sample_step(xt, out, noise, k8, mot, cfg, last, clip, xn, xdup, n, Cc, HW, k
     arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
     _check(lib().vd_sample_step(ptr(xt), ptr(out), ptr(noise), arr, ptr(k_dev), mot, int(cfg), int(last), int(clip), ptr(xn),
                                 ptr(xdup), n, Cc, HW, stream()), "vd_sample_step")
+
+
+def bpd_terms_lv(x0, xt, out, coef, mot, clip, kl, nll, pred, mse, n, Cc, HW):
+    """bpd_terms for a learned-variance output (Cp + C channels; coef slots 5, 6 = lvmin, delta)"""
+    _check(lib().vd_bpd_terms_lv(ptr(x0), ptr(xt), ptr(out), ptr(coef), mot, int(clip), ptr(kl), ptr(nll), ptr(pred), ptr(mse),
+                                 n, Cc, HW, stream()), "vd_bpd_terms_lv")
+
+
+def bpd_bwd_lv(x0, xt, out, coef, use_kl, gloss, mot, clip, mean_grad, dout, n, Cc, HW):
+    """dout has Cp + C channels; mean_grad = False writes zeros to the prediction channels"""
+    _check(lib().vd_bpd_bwd_lv(ptr(x0), ptr(xt), ptr(out), ptr(coef), ptr(use_kl), ptr(gloss), mot, int(clip), int(mean_grad), ptr(dout),
+                               n, Cc, HW, stream()), "vd_bpd_bwd_lv")
+
+
+def hybrid_loss_fwd(x0, eps, xt, out, logsnr, coef, use_kl, mot, rw, vlb_weight, loss, aux, n, Cc, HW):
+    """loss = mse on the prediction channels + vlb_weight * bound term; aux: n x 4 floats"""
+    _check(lib().vd_hybrid_loss_fwd(ptr(x0), ptr(eps), ptr(xt), ptr(out), ptr(logsnr), ptr(coef), ptr(use_kl), mot, rw, float(vlb_weight),
+                                    ptr(loss), ptr(aux), n, Cc, HW, stream()), "vd_hybrid_loss_fwd")
+
+
+def hybrid_loss_bwd(x0, eps, xt, out, logsnr, coef, use_kl, aux, gloss, mot, rw, vlb_weight, dout, n, Cc, HW):
+    _check(lib().vd_hybrid_loss_bwd(ptr(x0), ptr(eps), ptr(xt), ptr(out), ptr(logsnr), ptr(coef), ptr(use_kl), ptr(aux), ptr(gloss), mot, rw,
+                                    float(vlb_weight), ptr(dout), n, Cc, HW, stream()), "vd_hybrid_loss_bwd")
+
+
+def sample_step_lv(xt, out, noise, k10, mot, cfg, last, clip, xn, xdup, n, Cc, HW):
+    """sample_step for a learned-variance output; k10: 10 host floats (slot 5 = lvmin, slot 8 = delta); noise may be None"""
+    arr = (_f32 * 10)(*[float(v) for v in k10])
+    _check(lib().vd_sample_step_lv(ptr(xt), ptr(out), ptr(noise), arr, mot, int(cfg), int(last), int(clip), ptr(xn), ptr(xdup),
+                                   n, Cc, HW, stream()), "vd_sample_step_lv")
 
 
 def distill_mid(zt, tout, coef, tmot, cfg, clip, xhat, dhat, zmid, zdup, n, Cc, HW):

@@ -12,6 +12,9 @@ What runs where
 
 MI355X only: CPU tensors raise (the CPU restatement is oracle/diffusion_ref.py, test infrastructure).
 ``loss_type="kl"`` (variational-bound terms, reference :446-464) is one fused kernel pair as well (vd_bpd_terms / vd_bpd_bwd).
+``model_var_type="learned"`` (the reference's intent at :320-324, which cannot run as written): the network gives C more channels nu
+after its prediction channels, logvar = lvmin + sigmoid(nu) * (lvmax - lvmin) per element; the bound terms, the hybrid loss
+(``loss_type="hybrid"``, Nichol & Dhariwal 2021) and the reverse step each have a fused kernel for such outputs (vd_*_lv, vd_hybrid_loss_*).
 """
 import math
 
@@ -173,7 +176,7 @@ def logsnr_to_posterior(logsnr_s, logsnr_t, var_type: str, intp_frac: float = No
         lv = lv_small
     elif var_type == "fixed_medium":
         assert isinstance(intp_frac, (float, torch.Tensor))
-        lv = torch.lerp(lv_small, lv_large, intp_frac)
+        lv = torch.lerp(lv_small, lv_large, intp_frac.to(F64) if torch.is_tensor(intp_frac) else intp_frac)
     else:
         raise NotImplementedError(var_type)
     return c1.float(), c2.float(), lv.float()
@@ -246,6 +249,12 @@ def _pred_coefs64(model_out_type, l32):
     raise NotImplementedError(model_out_type)
 
 
+def _lv_delta(ls32, lt32):
+    """lvmax - lvmin of a step = logsigmoid(-logsnr_t) - logsigmoid(-logsnr_s) >= 0, fp64 from the fp32 log-SNRs: the closed form,
+    not the difference of the two log-variances (two numbers near -20 at the s = 0 end)"""
+    return F.logsigmoid(-lt32.to(F64)) - F.logsigmoid(-ls32.to(F64))
+
+
 def _device_ctx(device):
     """make ``device`` the current HIP device for the duration of a sampler call (kernels use its current stream)"""
     device = torch.device(device)
@@ -289,26 +298,58 @@ class _KLLoss(torch.autograd.Function):
     """where(s > 0, KL, decoder NLL) per sample in bits/dim (reference :510-515) with its analytic gradient wrt the output."""
 
     @staticmethod
-    def forward(ctx, out, x0, xt, coef, use_kl, mot):
+    def forward(ctx, out, x0, xt, coef, use_kl, mot, learned=False):
         B, C = x0.shape[:2]
         HW = x0[0, 0].numel()
         out = out.contiguous()
         kl = torch.empty((B,), dtype=torch.float32, device=x0.device)
         nll = torch.empty_like(kl)
         with torch.cuda.device(x0.device):
-            _hip.bpd_terms(x0, xt, out, coef, mot, False, kl, nll, None, None, B, C, HW)
+            (_hip.bpd_terms_lv if learned else _hip.bpd_terms)(x0, xt, out, coef, mot, False, kl, nll, None, None, B, C, HW)
         ctx.save_for_backward(out, x0, xt, coef, use_kl)
-        ctx.cfg = (mot, B, C, HW)
+        ctx.cfg = (mot, B, C, HW, learned)
         return torch.where(use_kl != 0, kl, nll)
 
     @staticmethod
     def backward(ctx, gloss):
         out, x0, xt, coef, use_kl = ctx.saved_tensors
-        mot, B, C, HW = ctx.cfg
+        mot, B, C, HW, learned = ctx.cfg
+        dout = torch.empty_like(out)
+        gloss = gloss.to(torch.float32).contiguous()
+        with torch.cuda.device(x0.device):
+            if learned:                                   # mean and variance both train through the bound
+                _hip.bpd_bwd_lv(x0, xt, out, coef, use_kl, gloss, mot, False, True, dout, B, C, HW)
+            else:
+                _hip.bpd_bwd(x0, xt, out, coef, use_kl, gloss, mot, False, dout, B, C, HW)
+        return dout, None, None, None, None, None, None
+
+
+class _HybridLoss(torch.autograd.Function):
+    """mse on the prediction channels + vlb_weight * where(s > 0, KL, decoder NLL) with the mean detached in the bound term (Nichol &
+    Dhariwal 2021, L_hybrid), one launch each way; the gradient covers all Cp + C channels of the output."""
+
+    @staticmethod
+    def forward(ctx, out, x0, eps, xt, logsnr32, coef, use_kl, mot, rw, vlb_weight):
+        B, C = x0.shape[:2]
+        HW = x0[0, 0].numel()
+        out = out.contiguous()
+        loss = torch.empty((B,), dtype=torch.float32, device=x0.device)
+        aux = torch.empty((B, 4), dtype=torch.float32, device=x0.device)
+        with torch.cuda.device(x0.device):
+            _hip.hybrid_loss_fwd(x0, eps, xt, out, logsnr32, coef, use_kl, mot, rw, vlb_weight, loss, aux, B, C, HW)
+        ctx.save_for_backward(out, x0, eps, xt, logsnr32, coef, use_kl, aux)
+        ctx.cfg = (mot, rw, vlb_weight, B, C, HW)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        out, x0, eps, xt, logsnr32, coef, use_kl, aux = ctx.saved_tensors
+        mot, rw, vlb_weight, B, C, HW = ctx.cfg
         dout = torch.empty_like(out)
         with torch.cuda.device(x0.device):
-            _hip.bpd_bwd(x0, xt, out, coef, use_kl, gloss.to(torch.float32).contiguous(), mot, False, dout, B, C, HW)
-        return dout, None, None, None, None, None
+            _hip.hybrid_loss_bwd(x0, eps, xt, out, logsnr32, coef, use_kl, aux, gloss.to(torch.float32).contiguous(), mot, rw, vlb_weight,
+                                 dout, B, C, HW)
+        return (dout,) + (None,) * 9
 
 
 class PendingImages:
@@ -341,7 +382,15 @@ class PendingImages:
 
 class GaussianDiffusion:
     def __init__(self, logsnr_fn, sample_timesteps, model_out_type, model_var_type, reweight_type, loss_type,
-                 intp_frac=None, w_guide=0.1, p_uncond=0.1, x0eps_coef=False):
+                 intp_frac=None, w_guide=0.1, p_uncond=0.1, x0eps_coef=False, vlb_weight=None):
+        """``model_var_type="learned"``: the network has C more output channels nu after its prediction channels and
+        logvar = lvmin + sigmoid(nu) * (lvmax - lvmin) per element.  ``loss_type="hybrid"`` (needs it) is the mse loss on the prediction
+        channels + ``vlb_weight`` * the bound term with its mean detached; ``vlb_weight=None`` = sample_timesteps / 1000, the paper's
+        lambda = 0.001 on the sum of the T terms, estimated from one term."""
+        if model_var_type == "learned" and x0eps_coef:
+            raise NotImplementedError("model_var_type='learned' with x0eps_coef=True")
+        if loss_type == "hybrid" and model_var_type != "learned":
+            raise ValueError("loss_type='hybrid' needs model_var_type='learned'")
         self.logsnr_fn = logsnr_fn
         self.sample_timesteps = sample_timesteps
         self.model_out_type = model_out_type
@@ -352,6 +401,19 @@ class GaussianDiffusion:
         self.w_guide = w_guide
         self.p_uncond = p_uncond
         self.x0eps_coef = x0eps_coef
+        self.vlb_weight = sample_timesteps / 1000 if vlb_weight is None else float(vlb_weight)
+
+    @property
+    def learned(self):
+        return self.model_var_type == "learned"
+
+    def _split_learned(self, model_out, C):
+        """(prediction channels, nu) of a learned-variance output for C-channel images; any other channel count raises"""
+        Cp = (2 if self.model_out_type == "both" else 1) * C
+        if model_out.ndim < 2 or model_out.shape[1] != Cp + C:
+            raise RuntimeError(f"model_var_type='learned' with model_out_type={self.model_out_type!r} needs a network output of "
+                               f"{Cp} + {C} channels (prediction, then variance), got shape {tuple(model_out.shape)}")
+        return model_out[:, :Cp], model_out[:, Cp:]
 
     def t2logsnr(self, *ts, x=None):
         """logsnr(t) reshaped to (B,1,1,..) in x's dtype (reference :293-295)"""
@@ -377,8 +439,10 @@ class GaussianDiffusion:
         return c1 * x_t + c2 * x_0, logvar
 
     def p_mean_var(self, model_out, x_t, logsnr_s, logsnr_t, clip_denoised, return_pred, use_ddim=False):
-        if self.model_var_type == "learned":
-            raise NotImplementedError("model_var_type='learned' is not supported (the reference asserts the same in train_loss)")
+        frac = None
+        if self.learned:                       # reference :320-324 as intended: the prediction from the first part, sigmoid of the rest
+            model_out, nu = self._split_learned(model_out, x_t.shape[1])
+            frac = torch.sigmoid(nu)
         l = logsnr_t
         s1, s0 = torch.sigmoid(l), torch.sigmoid(-l)
         if self.model_out_type == "x0":
@@ -402,7 +466,7 @@ class GaussianDiffusion:
         if use_ddim:
             mean, logvar = self.q_posterior_mean_var_ddim(pred, x_t, logsnr_s, logsnr_t)
         else:
-            mean, logvar = self.q_posterior_mean_var(pred, x_t, logsnr_s, logsnr_t)
+            mean, logvar = self.q_posterior_mean_var(pred, x_t, logsnr_s, logsnr_t, "fixed_medium" if self.learned else None, frac)
         return (mean, logvar, pred) if return_pred else (mean, logvar)
 
     # ------------------------------------------------------------------------------------------ training
@@ -433,7 +497,7 @@ class GaussianDiffusion:
         """Per-sample loss (B,) -- reference :492-545, mse branch.  ``y`` is mutated in place by the label drop
         (after the forward, reference quirk :527-529), which consumes one ``torch.rand(B)`` of the global CPU RNG."""
         _need_cuda(x_0, "train_loss")
-        if self.loss_type == "kl":
+        if self.loss_type in ("kl", "hybrid"):
             return self._train_loss_kl(denoise_fn, x_0, t, y, noise)
         if self.loss_type != "mse":
             raise NotImplementedError(self.loss_type)
@@ -463,18 +527,23 @@ class GaussianDiffusion:
     def _bpd_coefs(self, logsnr_s, logsnr_t):
         """coef[B][8] of vd_bpd_terms from per-sample (B,) log-SNRs: fp64 posterior arithmetic on the (tiny) vectors,
         fp32 prediction weights as reference :206-239 evaluates them."""
-        if self.model_var_type == "learned":
-            raise NotImplementedError("model_var_type='learned'")
         if self.x0eps_coef:
             raise NotImplementedError("x0eps_coef=True with the bits-per-dim terms")
         ls, lt = logsnr_s.reshape(-1).to(torch.float32), logsnr_t.reshape(-1).to(torch.float32)
         c1, c2, tlv = logsnr_to_posterior(ls, lt, "fixed_small")
-        _, _, mlv = logsnr_to_posterior(ls, lt, self.model_var_type, self.intp_frac)
+        if self.learned:                       # slot 6 = delta = lvmax - lvmin (the vd_*_lv kernels; slot 5 is lvmin already)
+            mlv = _lv_delta(ls, lt).float()
+        else:
+            _, _, mlv = logsnr_to_posterior(ls, lt, self.model_var_type, self.intp_frac)
         # prediction weights in fp64 from the fp32 log-SNR, rounded once; slot 7 carries a0 - 1, rounded on its own: the squared error
         # of x0_hat is taken from (a0 - 1)*x_t + (x_t - x_0) + ..., which stays well conditioned where x0_hat - x_0 is 1e-3 ... 1e-5
         # of x_0 (logsnr >= 12.9) -- through a0 itself one fp32 ulp of the weight is up to 1e-3 of that difference
         a0, b0x, b0e = _pred_coefs64(self.model_out_type, lt)
         return torch.stack([a0.float(), b0x.float(), b0e.float(), c1, c2, tlv, mlv, (a0 - 1.0).float()], dim=1).contiguous()
+
+    @property
+    def _bpd_terms(self):
+        return _hip.bpd_terms_lv if self.learned else _hip.bpd_terms
 
     def _loss_term_bpd(self, model_out, x_0, x_t, logsnr_s, logsnr_t, clip_denoised, return_pred=False):
         """(kl, decoder_nll[, pred_x_0]) per sample in bits per dimension -- reference :446-464, one fused kernel."""
@@ -483,17 +552,20 @@ class GaussianDiffusion:
         out = model_out.to(torch.float32).contiguous()
         B, C = x_0.shape[:2]
         HW = x_0[0, 0].numel()
+        if self.learned:
+            self._split_learned(out, C)
         coef = self._bpd_coefs(logsnr_s, logsnr_t)
         kl = torch.empty((B,), dtype=torch.float32, device=x_0.device)
         nll = torch.empty_like(kl)
         pred = torch.empty_like(x_0) if return_pred else None
         with torch.cuda.device(x_0.device):
-            _hip.bpd_terms(x_0, x_t, out, coef, _hip.OUT_TYPES[self.model_out_type], clip_denoised, kl, nll, pred, None, B, C, HW)
+            self._bpd_terms(x_0, x_t, out, coef, _hip.OUT_TYPES[self.model_out_type], clip_denoised, kl, nll, pred, None, B, C, HW)
         return (kl, nll, pred) if return_pred else (kl, nll)
 
     def _train_loss_kl(self, denoise_fn, x_0, t, y, noise):
         """un-weighted bound term per sample (reference :497-515): t snapped up to the sampling grid, s = t - 1/T,
-        KL(q || p) where s > 0 and the discretised decoder NLL for the last step."""
+        KL(q || p) where s > 0 and the discretised decoder NLL for the last step.  ``loss_type="hybrid"`` runs the same prologue, then
+        the label drop of the mse branch and the mse loss + vlb_weight * this term in one launch."""
         if noise is None:
             noise = torch.randn_like(x_0)
         x_0 = x_0.to(torch.float32).contiguous()
@@ -510,8 +582,18 @@ class GaussianDiffusion:
         with torch.cuda.device(x_0.device):
             _hip.q_sample(x_0, noise, lt32, x_t, B, C, HW)
         model_out = denoise_fn(x_t, t, y)
+        mot = _hip.OUT_TYPES[self.model_out_type]
+        if self.learned:
+            self._split_learned(model_out, C)
+        if self.loss_type == "hybrid":
+            assert self.reweight_type in _hip.REWEIGHTS
+            if self.p_uncond and y is not None:
+                keep = (torch.rand((y.shape[0],)) > self.p_uncond).to(device=y.device, dtype=y.dtype)
+                y *= keep.reshape((-1,) + (1,) * (y.ndim - 1))
+            return _HybridLoss.apply(model_out.to(torch.float32), x_0, noise, x_t, lt32, self._bpd_coefs(ls32, lt32), use_kl, mot,
+                                     _hip.REWEIGHTS[self.reweight_type], self.vlb_weight)
         coef = self._bpd_coefs(ls32, lt32)
-        return _KLLoss.apply(model_out.to(torch.float32), x_0, x_t, coef, use_kl, _hip.OUT_TYPES[self.model_out_type])
+        return _KLLoss.apply(model_out.to(torch.float32), x_0, x_t, coef, use_kl, mot, self.learned)
 
     def _prior_bpd(self, x_0):
         """KL(q(x_1 | x_0) || N(0, I)) per sample in bits/dim.  Reference :547-553 (its ``logsnr_t, = ...`` only unpacks for
@@ -546,7 +628,9 @@ class GaussianDiffusion:
                 noise = torch.empty_like(x_0).normal_(generator=generator)
                 _hip.q_sample(x_0, noise, lt32.contiguous(), x_t, B, C, HW)
                 out = denoise_fn(x_t, t, y).to(torch.float32).contiguous()
-                _hip.bpd_terms(x_0, x_t, out, self._bpd_coefs(ls32, lt32), mot, clip_denoised, kl, nll, None, ms, B, C, HW)
+                if self.learned:
+                    self._split_learned(out, C)
+                self._bpd_terms(x_0, x_t, out, self._bpd_coefs(ls32, lt32), mot, clip_denoised, kl, nll, None, ms, B, C, HW)
                 loss[:, i] = kl if i > 0 else nll
                 mse[:, i] = ms
         prior = self._prior_bpd(x_0)
@@ -556,12 +640,23 @@ class GaussianDiffusion:
     def _step_coefs(self, step, use_ddim, clip=True):
         """(the 8 floats of vd_sample_step for reverse step ``step`` (python int), the time the network is called with):
         [a0, b0x, b0e, c1, c2, noise scale, w_guide, c3] with x0_hat = a0*x_t + b0x*out (+ b0e*out_eps) and
-        mean = c1*x_t + c2*x0_hat + c3*out.  ``clip`` (the step's clip_denoised) only matters with ``x0eps_coef``."""
+        mean = c1*x_t + c2*x0_hat + c3*out.  ``clip`` (the step's clip_denoised) only matters with ``x0eps_coef``.
+        With learned variances: the 10 floats of vd_sample_step_lv, [a0, b0x, b0e, c1, c2, lvmin, w_guide, 0, delta, 0]."""
         T = self.sample_timesteps
         st = torch.tensor([step / T, (step + 1) / T], dtype=F64)
         l = self.logsnr_fn(st)                                 # a rescaling schedule rewrites st in place (:105-109)
         t_net = float(st[1])                                   # ... and the network is called with THAT t (:363-374)
         ls32, lt32 = l[0:1].float(), l[1:2].float()            # cast to the image dtype before the posterior (:365)
+        if self.learned:
+            # the 10 floats of vd_sample_step_lv: slot 5 = lvmin, slot 8 = delta -- the kernel forms the per-element noise scale
+            if use_ddim:
+                c1, c2, _ = logsnr_to_posterior_ddim(ls32, lt32, eta=0.)
+                lvmin = logsnr_to_posterior(ls32, lt32, "fixed_small")[2]
+            else:
+                c1, c2, lvmin = logsnr_to_posterior(ls32, lt32, "fixed_small")
+            a0, b0x, b0e = _pred_coefs(self.model_out_type, lt32[0])
+            return [a0, b0x, b0e, float(c1[0]), float(c2[0]), float(lvmin[0]), float(self.w_guide), 0.0,
+                    float(_lv_delta(ls32, lt32).float()[0]), 0.0], t_net
         if use_ddim:
             c1, c2, lv = logsnr_to_posterior_ddim(ls32, lt32, eta=0., x0eps_coef=self.x0eps_coef)
         else:
@@ -594,6 +689,14 @@ class GaussianDiffusion:
         out = denoise_fn(x_in, t_in, y_in).to(torch.float32).contiguous()
         mot = _hip.OUT_TYPES[self.model_out_type]
         pred = None
+        if self.learned:
+            self._split_learned(out, C)
+            if want_pred:
+                pred = torch.empty_like(x_t)
+                _hip.sample_step_lv(x_t, out, None, k8, mot, cfg, True, clip, pred, None, B, C, HW)
+            # DDIM adds no noise: the step's draw is made by the caller all the same and does not reach the kernel
+            _hip.sample_step_lv(x_t, out, None if use_ddim else noise, k8, mot, cfg, step == 0, clip, x_next, x_dup, B, C, HW)
+            return pred
         if want_pred:                                          # guided x0 prediction = the step-0 rule without noise
             pred = torch.empty_like(x_t)
             kp = list(k8)
@@ -698,8 +801,10 @@ class GaussianDiffusion:
             x_t = torch.randn(shape, device=device, generator=generator)
         else:
             x_t = noise.to(device=device, dtype=torch.float32).contiguous().clone()
+        if use_graph and self.learned:
+            raise NotImplementedError("use_graph=True with model_var_type='learned' (vd_sample_step_lv takes host coefficients only)")
         if use_graph is None:
-            use_graph = self._graph_eligible(denoise_fn, shape[0] * (1 + self._use_cfg(label)), pred_freq)
+            use_graph = not self.learned and self._graph_eligible(denoise_fn, shape[0] * (1 + self._use_cfg(label)), pred_freq)
         if use_graph:
             return self._sample_loop_graph(denoise_fn, tuple(shape), x_t, label, device, generator, use_ddim), []
         ch = Chain(self, denoise_fn, x_t, label, device)
