@@ -584,6 +584,34 @@ int vd_noise_extract(const float* xt, const float* out, const float* x0, const f
 int vd_slerp_rows(const float* a, const float* b, const float* frac, const float* frac_dev, float* out, float* w_out, int32_t n, int64_t N,
                   void* stream);
 
+/* ------------------------------------------------------------------ loss-aware timestep resampling (resample.hip)
+ * Nichol & Dhariwal 2021, section 3.3: timesteps drawn in proportion to sqrt(E[L_t^2]) and the loss reweighted by 1/(T p_t), with the
+ * history of the last K losses per timestep resident on the device (no counterpart in the reference; improved-diffusion's
+ * LossSecondMomentResampler keeps it in numpy and draws on the host).  State: hist [T][K] fp32, count [T] int32 (entries held, at most
+ * K), pos [T] int32 (next ring slot), cdf [T] fp64.  1 <= T <= 65536, K >= 1.
+ *
+ * the draw of B timesteps from B uniforms u in [0, 1) (fp64), ONE launch of one workgroup (1024 threads) that waits on no other; no
+ * atomics, no workspace, a fixed summation order: the same inputs give the same bits on every call; HIP-graph capturable.  All
+ * arithmetic in fp64.  The kernel decides on the device whether the history is warmed up (every count[t] == K):
+ *   warmed up: m_t = sqrt(sum_k hist[t][k]^2 / K) (k ascending), S = sum_t m_t, q_t = (1 - uniform_prob) m_t / S + uniform_prob / T
+ *              (q_t = 1/T when S is 0 or not finite), cdf[i] = sum_{j <= i} q_j; idx = min(T - 1, #{i : cdf[i] <= u}) by binary search,
+ *              w = fp32(1 / (T q_idx)) with q_idx re-evaluated from its history row by the same expression;
+ *   otherwise: idx = min(T - 1, floor(u T)), w = 1 exactly, cdf[i] = (i + 1) / T.
+ *   t = (idx + 1) / T either way, the value of a uniform draw on the discrete grid.
+ * S: thread j adds m_j, m_(j + 1024), ... in order, the 64 lanes of a wave by a fixed butterfly, the 16 wave sums in wave order.  The
+ * scan runs over chunks of 1024 timesteps: shuffles inside a wave, the totals of the waves in front added in wave order, the chunks in
+ * front carried in a register.  cdf differs from a sequential fp64 sum by rounding only (at most T ulps of 1 in the worst case, a few
+ * in practice).  The searches read cdf from LDS for T <= 4096 and from memory above that.  A NaN or negative u lands on index 0. */
+int vd_lsm_draw(const float* hist, const int32_t* count, const double* u, double* cdf, double* t_out, int32_t* idx_out, float* w_out,
+                int32_t T, int32_t K, int32_t B, double uniform_prob, void* stream);
+/* n rows (idx[r], loss[r]) enter the history in row order, ONE launch: a row with idx outside [0, T) or a loss that is not finite is
+ * skipped; otherwise hist[idx][pos[idx]] = loss, pos[idx] = (pos[idx] + 1) mod K, count[idx] = min(count[idx] + 1, K).  One thread
+ * owns one timestep and walks the rows, staged through LDS 1024 at a time, in order: the state afterwards is the sequential loop's bit
+ * for bit, also when a timestep occurs many times in one call (T n integer compares: nothing at T = 1000, n <= 8192).  No atomics, no
+ * waiting on another workgroup; n = 0 launches nothing. */
+int vd_lsm_update(float* hist, int32_t* count, int32_t* pos, const int32_t* idx, const float* loss, int32_t n, int32_t T, int32_t K,
+                  void* stream);
+
 /* ------------------------------------------------------------------ optimizer tail (train_utils.py:159-168, utils.py:144-149)
  * sum of squares of a flat buffer (global-norm clip), fused clip + AdamW + EMA over flat fp32 buffers */
 size_t vd_sumsq_ws_bytes(int64_t n);

@@ -138,6 +138,8 @@ _SIGNATURES = {
     "vd_forward_jump": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
     "vd_noise_extract": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_slerp_rows": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
+    "vd_lsm_draw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _vp]),
+    "vd_lsm_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_sumsq_ws_bytes": (_sz, [_i64]),
     "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
@@ -903,6 +905,18 @@ def slerp_rows(a, b, frac, out, w_out, n, N, frac_dev=None):
     device tensor of n floats; w_out optional, n x 2 floats"""
     arr = None if frac is None else (_f32 * 1)(float(frac))
     _check(lib().vd_slerp_rows(ptr(a), ptr(b), arr, ptr(frac_dev), ptr(out), ptr(w_out), n, int(N), stream()), "vd_slerp_rows")
+
+
+def lsm_draw(hist, count, u, cdf, t_out, idx_out, w_out, T, K, B, uniform_prob):
+    """B timesteps from B fp64 uniforms in proportion to the root mean square of each timestep's loss history (vd_lsm_draw): t_out fp64,
+    idx_out int32, w_out fp32 = 1 / (T q_idx); cdf (T fp64) receives the distribution drawn from"""
+    _check(lib().vd_lsm_draw(ptr(hist), ptr(count), ptr(u), ptr(cdf), ptr(t_out), ptr(idx_out), ptr(w_out), T, K, B, float(uniform_prob),
+                             stream()), "vd_lsm_draw")
+
+
+def lsm_update(hist, count, pos, idx, loss, n, T, K):
+    """n rows (idx int32, loss fp32) enter the per-timestep rings in row order (vd_lsm_update); n = 0 is a no-op"""
+    _check(lib().vd_lsm_update(ptr(hist), ptr(count), ptr(pos), ptr(idx), ptr(loss), n, T, K, stream()), "vd_lsm_update")
 
 
 def sumsq(g, out1):

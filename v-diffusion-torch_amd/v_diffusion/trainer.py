@@ -5,6 +5,7 @@
     loss = diffusion.train_loss(model, x, t, y, noise).mean() / num_accum ; backward   :147-154
     gradient mean over ranks (what DDP does for the reference, train.py:148)           RCCL all-reduce, bucketed
     clip_grad_norm_(max_norm) -> AdamW -> LR warm-up -> EMA                             :159-168, utils.py:144-149
+    optional, not in the reference: t drawn by loss-aware resampling, the loss reweighted by 1/(T p_t)      resample.py, schedule_sampler=
 
 MI355X-first choices
   * parameters, gradients, Adam moments and the EMA shadow are each ONE contiguous fp32 buffer (a 60.8 M-parameter CIFAR
@@ -27,6 +28,7 @@ import torch.distributed as dist
 
 from . import _hip
 from .flat import FlatParams
+from .resample import LossSecondMomentResampler
 
 BUCKET_BYTES = 32 << 20
 FLAG_SLOTS = 4            # floats behind the flat gradient buffer that travel with its last bucket (16 bytes: keeps buckets float4-sized)
@@ -198,7 +200,20 @@ class HotPathTrainer:
     """Equivalent of reference ``Trainer.step`` for one rank (see module docstring)."""
 
     def __init__(self, model, diffusion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup=5000,
-                 grad_norm=1.0, ema_decay=0.9999, use_ema=True, num_accum=1, timesteps=0, rank=0, world_size=1, group=None):
+                 grad_norm=1.0, ema_decay=0.9999, use_ema=True, num_accum=1, timesteps=0, rank=0, world_size=1, group=None,
+                 schedule_sampler="uniform"):
+        """``schedule_sampler``: "uniform" (the reference's draw), "loss-second-moment" or a ``LossSecondMomentResampler`` -- timesteps
+        drawn in proportion to the root mean square of their recent losses and the loss reweighted by 1/(T p_t) (v_diffusion/resample.py);
+        needs a discrete grid (``timesteps`` > 0)"""
+        if isinstance(schedule_sampler, str) and schedule_sampler not in ("uniform", "loss-second-moment"):
+            raise ValueError(f"schedule_sampler must be 'uniform', 'loss-second-moment' or a LossSecondMomentResampler, got {schedule_sampler!r}")
+        if not isinstance(schedule_sampler, (str, LossSecondMomentResampler)):
+            raise ValueError(f"schedule_sampler must be 'uniform', 'loss-second-moment' or a LossSecondMomentResampler, got {type(schedule_sampler).__name__}")
+        if schedule_sampler != "uniform":
+            if timesteps <= 0:
+                raise ValueError("schedule_sampler: loss-aware resampling needs a discrete grid (timesteps > 0); continuous t is drawn uniformly")
+            if not isinstance(schedule_sampler, str) and schedule_sampler.num_timesteps != timesteps:
+                raise ValueError(f"schedule_sampler holds {schedule_sampler.num_timesteps} timesteps, the trainer draws from {timesteps}")
         self.model, self.diffusion = model, diffusion
         self.lr, self.betas, self.eps, self.wd = lr, betas, eps, weight_decay
         self.warmup, self.grad_norm, self.ema_decay, self.num_accum, self.timesteps = warmup, grad_norm, ema_decay, num_accum, timesteps
@@ -209,6 +224,10 @@ class HotPathTrainer:
         model._grads_ready_hook = None
         self.generator = torch.Generator(self.device).manual_seed(8191 + rank)       # train_utils.py:124
         self.stats = DeviceRunningStatistics(device=self.device, loss=None)           # train_utils.py:135
+        # None = uniform: the code path, generator consumption and bits of a trainer without the argument
+        self.sampler = None if schedule_sampler == "uniform" else (
+            LossSecondMomentResampler(timesteps, device=self.device) if isinstance(schedule_sampler, str) else schedule_sampler)
+        self._drawn = None                                                            # (idx, w) of the last resampled draw, for its step
         # the leader = first member of the process group (global rank 0 need not belong to a sub-group)
         self.leader = dist.get_global_rank(group, 0) if (world_size > 1 and group is not None) else 0
         self.is_leader = world_size == 1 or (dist.get_rank() == self.leader if dist.is_initialized() else rank == 0)
@@ -223,7 +242,11 @@ class HotPathTrainer:
 
     def draw(self, x):
         B = x.shape[0]
-        if self.timesteps > 0:
+        if self.sampler is not None:
+            # stream: one fp64 rand(B) (the uniforms of the searches), then the noise as below; idx and w are kept for the step
+            t, idx, w = self.sampler.draw(B, generator=self.generator)
+            self._drawn = (idx, w)
+        elif self.timesteps > 0:
             t = torch.randint(self.timesteps, size=(B,), dtype=torch.float64, device=self.device,
                               generator=self.generator).add(1).div(self.timesteps)
         else:
@@ -231,25 +254,39 @@ class HotPathTrainer:
         noise = torch.empty_like(x).normal_(generator=self.generator)
         return t, noise
 
-    def step(self, x, y, update=True, t=None, noise=None):
+    def step(self, x, y, update=True, t=None, noise=None, weights=None):
         """One micro-batch: returns the detached mean loss (device tensor; no host sync here).  ``t`` / ``noise`` replace the draw from
-        the per-rank generator (tests: the same rows through one rank and through two must give the same update)."""
+        the per-rank generator (tests: the same rows through one rank and through two must give the same update).  With a resampler
+        the loss is the weighted mean ``dot(per-sample loss, w) / B`` and the per-sample losses enter its history after backward; for
+        an injected ``t`` the grid index is ``round(t T) - 1`` and ``w`` is ``weights`` ((B,) fp32; ones when None)."""
         flat = self.flat
+        idx = w = None
         if t is None or noise is None:
             t, noise = self.draw(x)
+            if self.sampler is not None:
+                idx, w = self._drawn
+        elif self.sampler is not None:
+            idx = torch.round(t.double() * self.timesteps).to(torch.int32) - 1
+            w = torch.ones(x.shape[0], dtype=torch.float32, device=self.device) if weights is None else weights.to(self.device, torch.float32)
         if flat.cls_range is not None:
             # did this micro-batch reach the class embedding?  One float behind the gradients: it is summed over ranks with the last
             # gradient bucket (and over micro-batches with the accumulation buffer), and vd_adamw_ema_flagged reads it on the device --
             # whether the class embedding is updated is ONE decision for all replicas (the gradients are averaged over ranks; a
             # rank-local decision would let replicas that saw y = None skip an update the others apply), and no host waits for another
             flat.flag.fill_(0.0 if y is None else 1.0)
-        loss = self.diffusion.train_loss(self.model, x_0=x, t=t, y=y, noise=noise).mean()
+        if self.sampler is None:
+            loss = self.diffusion.train_loss(self.model, x_0=x, t=t, y=y, noise=noise).mean()
+        else:
+            per = self.diffusion.train_loss(self.model, x_0=x, t=t, y=y, noise=noise)
+            loss = torch.dot(per, w) / x.shape[0]                  # sum_b L_b / (T q_b) / B: the paper's reweighting
         self.reducer.start()
         self.model._grads_ready_hook = self.reducer.ready if self.reducer.active else None     # (no listener: backward joins its side stream once, at the end)
         (loss / (self.num_accum * self.world)).backward()          # 1/world folds DDP's gradient averaging into the seed
         self.model._grads_ready_hook = None
         self.reducer.finish()
-        if self.num_accum > 1:                                     # the engine overwrites flat.g: keep the running sum (train_utils.py:154,
+        if self.sampler is not None:
+            self._update_history(idx, per.detach())
+        if self.num_accum > 1:                                    # the engine overwrites flat.g: keep the running sum (train_utils.py:154,
             if getattr(self, "_acc", None) is None:                # :257 -- loss / num_accum, .grad accumulated over the micro-batches)
                 self._acc = torch.zeros_like(flat.g_all)
             self._acc.add_(flat.g_all)
@@ -279,6 +316,18 @@ class HotPathTrainer:
             loss.div_(self.world)
         self.stats.update(x.shape[0], loss=loss * x.shape[0])      # train_utils.py:169, without its .item()
         return loss
+
+    def _update_history(self, idx, per):
+        """this micro-batch's (index, loss) rows into the resampler.  Data-parallel: ONE all_gather of the per-rank (B, 2) fp32 block
+        [idx, loss] (an index below 65536 is exact in fp32), the ranks concatenated in rank order -- every replica holds the same
+        history, as it holds the same parameters.  No host sync either way."""
+        if self.world > 1:
+            mine = torch.stack([idx.to(torch.float32), per.to(torch.float32)], dim=1)
+            parts = [torch.empty_like(mine) for _ in range(self.world)]
+            dist.all_gather(parts, mine, group=self.reducer.group)
+            rows = torch.cat(parts)
+            idx, per = rows[:, 0].to(torch.int32), rows[:, 1]
+        self.sampler.update(idx, per)
 
     def step_uint8(self, u8_hwc, y, flip=None, **kw):
         """``step`` on a batch as the dataset holds it BEFORE the reference's CPU transforms (datasets.py:111-126: PIL image ->
@@ -328,6 +377,8 @@ class HotPathTrainer:
                           "num_updates": flat.ema_updates}
         out["scheduler"] = {"base_lrs": [self.lr], "last_epoch": flat.step_count, "_step_count": flat.step_count + 1,
                             "_get_lr_called_within_step": False, "_last_lr": [self._lr_now()], "lr_lambdas": [None]}
+        if self.sampler is not None:                               # (absent for the uniform draw: reference-format checkpoints are unchanged)
+            out["schedule_sampler"] = self.sampler.state_dict()
         return out
 
     def gather_rng_states(self):
@@ -384,6 +435,8 @@ class HotPathTrainer:
             if sch is not None and opt is None:
                 flat.step_count = int(sch.get("last_epoch", flat.step_count))
                 flat.cls_steps = flat.step_count
+            if ckpt.get("schedule_sampler") is not None and self.sampler is not None:    # (either side without one: ignored)
+                self.sampler.load_state_dict(ckpt["schedule_sampler"])
         if ckpt.get("rng") is not None:
             if int(self.rank) in ckpt["rng"]:
                 self.generator.set_state(ckpt["rng"][int(self.rank)].cpu())
