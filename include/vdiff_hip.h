@@ -493,6 +493,32 @@ int vd_distill_loss_bwd(const float* resid, const float* coef, const float* glos
 int vd_solver_step(const float* xt, const float* out, float* hist, const float* k, const float* k_dev,
                    int32_t model_out_type, int32_t cfg, int32_t clip,
                    float* xn, float* xdup, int32_t n, int32_t C, int32_t HW, void* stream);
+/* one node of the UniPC multistep predictor-corrector (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast
+ * Sampling of Diffusion Models", data-prediction form, B(h) = h or e^h - 1), for a batch that shares the node, ONE launch.  The
+ * network was called at the PREDICTED state xt; its guided x0 prediction g corrects the step that arrived at this node at no further
+ * network call, the predictor of the step that leaves starts from the corrected state, and the history of the last three guided
+ * predictions shifts by one.  xt, h0, h1, h2, xn, xc_out: n images (NCHW), h0 the newest prediction; out: n*(1+cfg) images,
+ * cond/uncond interleaved when cfg, 2C channels for a "both" network; xdup (optional, cfg only): 2n images; xc_out (optional): the
+ * corrected state.
+ * k: 16 floats {a0, b0x, b0e, w_guide, c1, c2, p1, p2, eg, e1, e2, 0, 0, 0, 0, 0}, host (k) or device (k_dev), exactly one of the two
+ * as in vd_solver_step.  c1, c2 are the DDIM weights of the leaving step; with r_k the log-SNR distance of the k-th older prediction in
+ * units of the step and rho^p, rho^c the predictor's and the corrector's weights (v_diffusion.unipc_coefs: host fp64, each slot rounded
+ * once), p_k = -alpha_next B rho^p_k / r_k of the leaving step and eg = -alpha B rho^c_p, e_k = -alpha B (rho^c_k - rho^p_k) / r_k
+ * of the arriving one.  Evaluation order, all in fp32, per element:
+ *   x_c, x_u = clip?(a0*xt + b0x*out (+ b0e*out_eps))      per branch, as vd_solver_step (clip per branch, then guide)
+ *   g        = cfg ? x_c + w_guide*(x_c - x_u) : x_c
+ *   xc       = xt + eg*(g - h0) + e1*(h1 - h0) + e2*(h2 - h0)      the corrector of the step that arrived at this node
+ *   xn       = c1*xc + c2*g + p1*(h0 - g) + p2*(h1 - g)            the predictor of the step leaving it
+ *   h2 = h1;  h1 = h0;  h0 = g                              (read, then overwritten in place)
+ *   xdup     = xn on rows 2b and 2b+1;   xc_out = xc
+ * There is no first- or last-node flag: eg = e1 = e2 = 0 leaves xc = xt (the first node of a chain, whose history the host
+ * zero-fills, and every node without the corrector), p2 = 0 with p1 = -c2rho is the vd_solver_step update, and (c1, c2, p1, p2) =
+ * (0, 1, 0, 0) returns g, the guided x0 prediction every sampler here ends on.  xn may alias xt; h0, h1, h2 and xc_out are buffers of
+ * their own.  No workspace, no atomics: HIP-graph capturable.  Any C*HW; 64-bit element offsets; dwordx4 accesses when C*HW is a
+ * multiple of 4 and all bases are 16-byte aligned, scalar otherwise. */
+int vd_unipc_step(const float* xt, const float* out, float* h0, float* h1, float* h2, const float* k, const float* k_dev,
+                  int32_t model_out_type, int32_t cfg, int32_t clip,
+                  float* xn, float* xdup, float* xc_out, int32_t n, int32_t C, int32_t HW, void* stream);
 /* dynamic thresholding (Saharia et al. 2022, "Imagen", section 2.3; the companion Lu et al. 2022 recommend for the data-prediction
  * solver under guidance).  kth[b] = the element of rank r (0-based, ascending) of |x[b, 0..N)|, for n rows of N floats, 0 <= r < N.
  * Order: the bit pattern of |x| as an unsigned integer -- -0 = +0, denormals order as numbers, +Inf above every finite value, a NaN

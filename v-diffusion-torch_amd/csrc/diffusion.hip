@@ -453,7 +453,7 @@ template <int V> __device__ __forceinline__ void st_dup(float* xn, float* xdup, 
 // rows, cond and uncond interleaved (diffusion.py:369-372), of N floats or, for "both", 2N (the row stride may be larger); each forms a value per branch, guides it,
 // and writes xn and (optional) xdup.  The coefficients come as host floats copied into the kernel argument or, to keep the launch
 // HIP-graph replayable, as a device pointer.
-struct Coefs { float k[10]; const float* kdev; };
+struct Coefs { float k[16]; const float* kdev; };     // (16: the widest row, vd_unipc_step's)
 
 __device__ __forceinline__ const float* coefs(const Coefs& c) { return c.kdev ? c.kdev : c.k; }
 
@@ -480,6 +480,19 @@ __device__ __forceinline__ float guide(float w, float xc, float xu) {
 __device__ __forceinline__ float solver_update(float c1, float c2, float c2r, float z, float g, float h) {
 #pragma clang fp contract(off)
     return __builtin_fmaf(c2r, g - h, __builtin_fmaf(c1, z, c2 * g));
+}
+
+// UniPC: the corrector of the step that arrived, xt + eg*(g - h0) + e1*(h1 - h0) + e2*(h2 - h0), and the predictor of the step that
+// leaves, c1*xc + c2*g + p1*(h0 - g) + p2*(h1 - g): left to right, each product folded into the sum before it.  With e = 0 the first
+// returns xt itself; with p2 = 0 and p1 = -c2rho the second is solver_update with the sign moved from the weight into the difference.
+__device__ __forceinline__ float unipc_correct(float eg, float e1, float e2, float z, float g, float h0, float h1, float h2) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(e2, h2 - h0, __builtin_fmaf(e1, h1 - h0, __builtin_fmaf(eg, g - h0, z)));
+}
+
+__device__ __forceinline__ float unipc_predict(float c1, float c2, float p1, float p2, float xc, float g, float h0, float h1) {
+#pragma clang fp contract(off)
+    return __builtin_fmaf(p2, h1 - g, __builtin_fmaf(p1, h0 - g, __builtin_fmaf(c1, xc, c2 * g)));
 }
 
 // The posterior mean c1*z + c2*x0h + c3*o has two groupings, and they differ in the last bit: mean_plain is the product sampler's
@@ -756,6 +769,49 @@ __global__ void solver_step_kernel(const SolverArgs p) {
 #pragma unroll
         for (int j = 0; j < V; ++j) xn[j] = solver_update(c1, c2, c2r, z[j], g[j], h[j]);
         stv<V>(p.hist + e, g);
+        st_dup<V>(s.xn, s.xdup, b, N, i, xn);
+    }
+}
+
+// ---- UniPC (Zhao et al. 2023, multistep, data-prediction form, B(h) = h or e^h - 1): one node of the predictor-corrector chain in ONE
+// launch.  The network was called at the predicted state xt; its guided x0 prediction g first corrects the step that arrived at this
+// node (the corrector and the predictor of a step share x_bar, so the corrected state is the predicted one plus differences of
+// predictions: no further state image), then the predictor of the step that leaves starts from the corrected state, and the history
+// of the last three predictions (h0 newest) shifts by one.  k[16] = {a0, b0x, b0e, w_guide, c1, c2, p1, p2, eg, e1, e2, 0...}:
+// c1, c2 the DDIM weights of the leaving step, p_k = -alpha_next B rho^p_k / r_k, eg = -alpha B rho^c_p, e_k = -alpha B (rho^c_k -
+// rho^p_k) / r_k (v_diffusion/unipc.py builds them).  Evaluation order, every operation in fp32:
+//   g  = the guided PredX0 of the two branches (each clipped when asked)
+//   xc = xt + eg*(g - h0) + e1*(h1 - h0) + e2*(h2 - h0)
+//   xn = c1*xc + c2*g + p1*(h0 - g) + p2*(h1 - g)
+//   h2 <- h1;  h1 <- h0;  h0 <- g;   xdup rows 2b, 2b+1 <- xn;   xc_out <- xc (optional)
+// e = 0 (the first node, or no corrector) gives xc = xt; p2 = 0, p1 = -c2*rho the DPM-Solver++(2M) step; (c1, c2, p1, p2) = (0, 1, 0, 0)
+// returns g.  Each thread reads all it needs of its V elements before it writes any of them, so xn may alias xt.
+struct UnipcArgs { StepCommon s; float* h0; float* h1; float* h2; float* xc; };
+
+template <int V>
+__global__ void unipc_step_kernel(const UnipcArgs p) {
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = coefs(s.c);
+    const PredX0 f = pred_x0(s, k);
+    const float w = k[3], c1 = k[4], c2 = k[5], p1 = k[6], p2 = k[7], eg = k[8], e1 = k[9], e2 = k[10];
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float z[V], h0[V], h1[V], h2[V], g[V], xc[V], xn[V];
+        ldv<V>(s.xt + e, z);
+        ldv<V>(p.h0 + e, h0);
+        ldv<V>(p.h1 + e, h1);
+        ldv<V>(p.h2 + e, h2);
+        guided<V>(s, b, i, w, z, f, g);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            xc[j] = unipc_correct(eg, e1, e2, z[j], g[j], h0[j], h1[j], h2[j]);
+            xn[j] = unipc_predict(c1, c2, p1, p2, xc[j], g[j], h0[j], h1[j]);
+        }
+        stv<V>(p.h2 + e, h1);
+        stv<V>(p.h1 + e, h0);
+        stv<V>(p.h0 + e, g);
+        if (p.xc) stv<V>(p.xc + e, xc);
         st_dup<V>(s.xn, s.xdup, b, N, i, xn);
     }
 }
@@ -1255,6 +1311,23 @@ extern "C" int vd_solver_step(const float* xt, const float* out, float* hist, co
     VD_REQUIRE(hist != xt && hist != xn, "vd_solver_step: hist is a buffer of its own");
     launch_elems(solver_step_kernel<4>, solver_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, hist, xn, xdup), n * p.s.N, stream, p);
     VD_LAUNCH_CHECK("solver_step_kernel");
+    return 0;
+}
+
+extern "C" int vd_unipc_step(const float* xt, const float* out, float* h0, float* h1, float* h2, const float* k, const float* k_dev,
+                             int32_t type, int32_t cfg, int32_t clip, float* xn, float* xdup, float* xc_out, int32_t n, int32_t C, int32_t HW,
+                             void* stream) {
+    UnipcArgs p = {step_common(xt, out, type, cfg, 0, clip, xn, xdup, n, C, HW), h0, h1, h2, xc_out};
+    VD_TRY(step_checks("vd_unipc_step", p.s, k, k_dev, 16, xt && out && h0 && h1 && h2 && xn, C, HW));
+    VD_TRY(dup_is_guided("vd_unipc_step", p.s));
+    const float* const hs[3] = {h0, h1, h2};
+    for (const float* h : hs)
+        VD_REQUIRE(h != xt && h != xn && h != xc_out, "vd_unipc_step: each history image is a buffer of its own");
+    VD_REQUIRE(h0 != h1 && h0 != h2 && h1 != h2, "vd_unipc_step: each history image is a buffer of its own");
+    VD_REQUIRE(!xc_out || (xc_out != xt && xc_out != xn), "vd_unipc_step: xc_out is a buffer of its own");
+    launch_elems(unipc_step_kernel<4>, unipc_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, h0, h1, h2, xn, xdup, xc_out),
+                 n * p.s.N, stream, p);
+    VD_LAUNCH_CHECK("unipc_step_kernel");
     return 0;
 }
 

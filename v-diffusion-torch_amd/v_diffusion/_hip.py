@@ -131,6 +131,7 @@ _SIGNATURES = {
     "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
     "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_unipc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_abs_kth_rows": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
     "vd_solver_step_dyn": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_inpaint_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
@@ -864,6 +865,14 @@ def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=No
     arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
     _check(lib().vd_solver_step(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
                                 n, Cc, HW, stream()), "vd_solver_step")
+
+
+def unipc_step(xt, out, h0, h1, h2, k16, mot, cfg, clip, xn, xdup, xc_out, n, Cc, HW, k_dev=None):
+    """one UniPC node: k16 = 16 host floats, or None with k_dev = device tensor of 16 floats (graph-replayable form); h0, h1, h2 = the
+    last three guided predictions, shifted in place; xc_out (optional) receives the corrected state"""
+    arr = None if k16 is None else (_f32 * 16)(*[float(v) for v in k16])
+    _check(lib().vd_unipc_step(ptr(xt), ptr(out), ptr(h0), ptr(h1), ptr(h2), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
+                               ptr(xc_out), n, Cc, HW, stream()), "vd_unipc_step")
 
 
 def abs_kth_rows(x, n, N, r, kth):

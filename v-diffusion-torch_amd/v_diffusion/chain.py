@@ -1,5 +1,5 @@
-"""What the chains of this package share -- ``p_sample``, ``p_sample_solver``, ``p_sample_inpaint``, ``p_invert_noise``,
-``p_sample_replay``, ``p_encode`` and the two captured-graph paths: the guided label rows, the state buffers and the network call
+"""What the chains of this package share -- ``p_sample``, ``p_sample_solver``, ``p_sample_unipc``, ``p_sample_inpaint``,
+``p_invert_noise``, ``p_sample_replay``, ``p_encode`` and the captured-graph paths: the guided label rows, the state buffers and the network call
 (``Chain``), the capture of one step into a HIP graph (``captured_step``), and the argument checks more than one of them makes.  A sampler
 keeps what is its own: its coefficient table, its random draws and its one launch per step."""
 import contextlib
@@ -103,10 +103,10 @@ class Chain:
         return eng.fixed_weights() if eng is not None else contextlib.nullcontext()
 
 
-def captured_step(cache, limit, gd, denoise_fn, shape, label, device, launch, key=(), bufs=()):
+def captured_step(cache, limit, gd, denoise_fn, shape, label, device, launch, key=(), bufs=(), kwidth=8):
     """``(graph, state, pinned packs)`` of one step -- the network's forward and ``launch(chain, state, out)`` on the device-resident
     coefficients ``state["k"]`` -- captured once into a HIP graph and kept in ``cache``, a small LRU (a graph pins its activations).
-    ``state`` = dict(chain = an in-place ``Chain`` over buffers of its own, t = the (rows,) network time, k = the 8 coefficients,
+    ``state`` = dict(chain = an in-place ``Chain`` over buffers of its own, t = the (rows,) network time, k = the ``kwidth`` coefficients,
     and one image-shaped buffer per name in ``bufs``); the caller fills them and replays.  ``key``: what else the launch depends on."""
     net = getattr(denoise_fn, "module", denoise_fn)
     key = (id(denoise_fn), tuple(shape), gd._use_cfg(label), gd.model_out_type, None if label is None else tuple(label.shape),
@@ -121,7 +121,7 @@ def captured_step(cache, limit, gd, denoise_fn, shape, label, device, launch, ke
         ch.x_in.zero_()                                # the warm-up and the capture run on these buffers before load() fills them
     if ch.y_in is not None:
         ch.y_in = torch.zeros_like(ch.y_in)
-    st = dict(chain=ch, t=zeros((ch.rows,), F64), k=zeros((8,)), **{name: zeros(shape) for name in bufs})
+    st = dict(chain=ch, t=zeros((ch.rows,), F64), k=zeros((kwidth,)), **{name: zeros(shape) for name in bufs})
     body = lambda: launch(ch, st, ch.net(st["t"]))
     side = torch.cuda.Stream(device)
     side.wait_stream(torch.cuda.current_stream(device))

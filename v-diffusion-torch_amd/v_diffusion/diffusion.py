@@ -858,6 +858,20 @@ class GaussianDiffusion:
                                dynamic_quantile, dynamic_max).cpu()
 
     @torch.inference_mode()
+    def p_sample_unipc(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=None, order=3, variant="bh2",
+                       corrector=True, spacing="time", clip_denoised=True, use_graph=False):
+        """Deterministic reverse chain with the UniPC multistep predictor-corrector (extension, v_diffusion/unipc.py; Zhao et al. 2023):
+        a predictor of ``order`` 1, 2 or 3 and, with ``corrector``, a correction of every step from the network call the next step makes
+        anyway -- one order more at the same network calls.  ``variant`` = "bh2" (B(h) = e^h - 1) or "bh1" (B(h) = h);
+        ``variant="bh2", order=2, corrector=False`` is ``p_sample_solver(order=2)``.  The first steps of a chain run at orders 1, 2, ...
+        until the history holds enough predictions.  ``steps``, ``spacing``, the one draw (x_T, ``p_sample``'s for the seed) and
+        ``use_graph`` are ``p_sample_solver``'s.  ``clip_denoised``: True clips each branch's x0 prediction to [-1, 1] before guidance,
+        False clips nothing; "dynamic" raises NotImplementedError (``p_sample_solver`` has it).  Returns a CPU tensor."""
+        from .unipc import p_sample_unipc
+        return p_sample_unipc(self, denoise_fn, shape, noise, label, device, seed, steps, order, variant, corrector, spacing, clip_denoised,
+                              use_graph).cpu()
+
+    @torch.inference_mode()
     def p_sample_inpaint(self, denoise_fn, known, mask, label=None, device=None, seed=None, use_ddim=False, jump_length=1, resamplings=1,
                          start=None, clip_denoised=True):
         """Reverse chain conditioned on a given image (extension, v_diffusion/inpaint.py): RePaint inpainting (Lugmayr et al. 2022) and,
