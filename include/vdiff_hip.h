@@ -474,6 +474,48 @@ int vd_distill_loss_fwd(const float* xhat, const float* dhat, const float* zmid,
 /* dout = gloss[b] * omega_b * 2/(C*HW) * resid * b0x   (channels C..2C of a "both" student: * b0e) */
 int vd_distill_loss_bwd(const float* resid, const float* coef, const float* gloss, int32_t student_out_type, float* dout,
                         int32_t n, int32_t C, int32_t HW, void* stream);
+/* consistency distillation (Song et al. 2023; Luo et al. 2023) and consistency training (Song & Dhariwal 2024): the student at
+ * (z_t, t = i/N) regresses on a TARGET network at (z_s, s = (i-1)/N), where z_s is one DDIM step of a frozen teacher down from z_t
+ * (distillation) or the same x_0, eps noised to s (training).  Launches around the network forwards: vd_consist_mid or vd_consist_pair,
+ * vd_consist_loss_fwd / _bwd.  coef[n][24] (device), per sample, computed on the host in fp64 from the fp32-rounded log-SNRs, every
+ * slot rounded once on its own:
+ *    0  1  2   a0 b0x b0e of the TEACHER at t :  x_hat  = clip?(a0*z_t + b0x*out (+ b0e*out_eps))          (0 in training mode)
+ *    3  4      c1 c2 of the DDIM step s <- t  :  z_s    = c1*z_t + c2*x_hat          ((0, 1) where i = 1: z_0 is x_hat itself)
+ *    5  6  7   a0 b0x b0e of the TARGET at s  :  x_tgt  = a0*z_s + b0x*out (+ b0e*out_eps)     (the student's parameterisation)
+ *    8  9 10   a0 b0x b0e of the STUDENT at t :  x_stud = a0*z_t + b0x*out (+ b0e*out_eps)
+ *   11         omega, the loss weight of the sample       12  w_guide of the teacher
+ *   13         logsnr(t): vd_q_sample's argument; vd_consist_pair forms z_t from it exactly as vd_q_sample does
+ *   14 15 16   a0 - 1 of slots 0, 5, 8                    17  c1 + c2 - 1 (0 where i = 1)
+ *   18 19      alpha_s - alpha_t, sigma_s - sigma_t       20 21  alpha_s, sigma_s
+ *   22         1 where i = 1 (s = 0), else 0              23  0
+ * The residual is assembled from differences, as vd_distill_loss_fwd's and for its reason:
+ *   resid = [(a0_stud - 1) z_t + b0x out_stud] - [(a0_tgt - 1) z_s + b0x out_tgt] - dz,   dz = z_s - z_t from slots 17, 4 or 18, 19.
+ * Rows with slot 22 set take the boundary condition f(z, 0) = z: the target is z_s itself, SELECTED -- the target network's output is
+ * not read on such a row, so nothing in it reaches loss, resid or gradient.  No atomics, no workspace: the same call gives the same
+ * bits.  Any C*HW; 64-bit element offsets; dwordx4 accesses when C*HW is a multiple of 4 and all bases are 16-byte aligned, scalar
+ * otherwise, and the two agree bit for bit. */
+/* distillation mode.  teacher_out: n*(1+cfg) rows, cond/uncond interleaved, guided in x-space after the optional clip as in
+ * vd_distill_mid.  Writes z_s, dz = (c1 + c2 - 1) z_t + c2 (x_hat - z_t) and, when asked, x_hat (n rows each). */
+int vd_consist_mid(const float* zt, const float* teacher_out, const float* coef, int32_t teacher_out_type, int32_t cfg, int32_t clip,
+                   float* zs, float* dz, float* xhat, int32_t n, int32_t C, int32_t HW, void* stream);
+/* training mode, one pass: z_t = vd_q_sample's value bit for bit, z_s = alpha_s x_0 + sigma_s eps, dz = (alpha_s - alpha_t) x_0 +
+ * (sigma_s - sigma_t) eps */
+int vd_consist_pair(const float* x0, const float* eps, const float* coef, float* zt, float* zs, float* dz, int32_t n, int32_t C,
+                    int32_t HW, void* stream);
+/* student_out, target_out: n rows in the parameterisation out_type.  One workgroup per sample, fixed summation order, S = sum resid^2
+ * in fp64, D = C*HW.  metric 0 (l2): loss = omega S/D, aux = 2/D.  metric 1 (pseudo-Huber, huber_c = c > 0): loss = omega (sqrt(S + c^2)
+ * - c) evaluated as omega S/(sqrt(S + c^2) + c), aux = 1/sqrt(S + c^2).  resid (n, C, HW) and aux[n] serve the backward; target
+ * (optional) = the target image, z_s on rows with i = 1. */
+int vd_consist_loss_fwd(const float* zt, const float* zs, const float* dz, const float* student_out, const float* target_out,
+                        const float* coef, int32_t out_type, int32_t metric, double huber_c, float* loss, float* resid, float* aux,
+                        float* target, int32_t n, int32_t C, int32_t HW, void* stream);
+/* dout = gloss[b] * omega_b * aux[b] * resid * b0x   (channels C..2C of a "both" student: * b0e) */
+int vd_consist_loss_bwd(const float* resid, const float* coef, const float* gloss, const float* aux, int32_t out_type, float* dout,
+                        int32_t n, int32_t C, int32_t HW, void* stream);
+/* e <- e + (1 - decay) (p - e) over every tensor of a module in ONE launch.  items_dev = [n][8] int64 {dst e, src p, count, 0, 0, 0, 0,
+ * first block}, blocks of 256 elements, total_blocks = the sum of ceil(count/256).  1 - decay is rounded to fp32 once; decay = 0 copies
+ * (e <- p, selected), decay = 1 launches nothing. */
+int vd_ema_track_batched(const int64_t* items_dev, int32_t n, int64_t total_blocks, double decay, void* stream);
 /* one reverse step of DPM-Solver++(2M) (Lu et al. 2022, data-prediction form): the second-order multistep solver of the
  * probability-flow ODE in log-SNR time, for a batch that shares the step.  xt, hist, xn: n images (NCHW); out: n*(1+cfg) images,
  * cond/uncond interleaved when cfg, 2C channels for a "both" network; xdup (optional, cfg only): 2n images.

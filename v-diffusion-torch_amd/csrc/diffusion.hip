@@ -4,7 +4,7 @@
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
 //   learned variances (bound terms, hybrid loss, reverse step for outputs with variance channels)  the intent of diffusion.py:320-324
-//   progressive distillation, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
+//   progressive distillation, consistency distillation / training and the batched target-network update, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
 //   jump, the noise-map extraction of DDPM inversion and spherical interpolation: no counterpart in the reference
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 #include "common.h"
@@ -744,6 +744,206 @@ __global__ void distill_loss_bwd_kernel(const float* resid, const float* coef, c
     }
 }
 
+// ---- consistency distillation / training (Song et al. 2023; Song & Dhariwal 2024): the student at (z_t, t) regresses on a target
+// network at (z_s, s = t - 1/N), z_s one DDIM step of a teacher down from z_t (distillation) or the same x_0, eps noised to s
+// (training).  coef[n][24], see include/vdiff_hip.h.  As above the residual is assembled from differences: each prediction minus
+// the state it was made from, and dz = z_s - z_t from weights rounded on their own -- never from two nearly equal images.
+// The expressions are spelled out with contraction off: the wide and the scalar form give the same bits.
+enum { CK = 24, CK_LAST = 22 };
+
+__device__ __forceinline__ float consist_diff(float a0m1, float b0x, float b0e, bool both, float z, float o, float oe) {
+#pragma clang fp contract(off)
+    const float e = both ? b0e * oe : 0.f;
+    return __builtin_fmaf(b0x, o, a0m1 * z) + e;
+}
+
+struct ConsistMidArgs {
+    const float* zt; const float* out; const float* coef; int type, cfg, clip; float* zs; float* dz; float* xhat; int n; long long N;
+};
+
+// teacher prediction at t (guided_x0: x_hat and d_hat = x_hat - z_t) and the DDIM step to s: z_s = c1 z_t + c2 x_hat,
+// dz = (c1 + c2 - 1) z_t + c2 d_hat; rows with i = 1 (s = 0) take x_hat and d_hat themselves
+template <int V>
+__global__ void consist_mid_kernel(const ConsistMidArgs p) {
+    const long long N = p.N, total = (long long)p.n * N / V;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        const float* k = p.coef + CK * b;
+        float z[V], x[V], d[V], zs[V], dz[V];
+        ldv<V>(p.zt + e, z);
+        guided_x0<V>(p.out, b, N, i, p.type, p.cfg, p.clip, k[0], k[14], k[1], k[2], k[12], z, x, d);
+        const float c1 = k[3], c2 = k[4], c12m1 = k[17];
+        const bool last = k[CK_LAST] != 0.f;
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            zs[j] = last ? x[j] : axpby(c1, z[j], c2, x[j]);
+            dz[j] = last ? d[j] : axpby(c12m1, z[j], c2, d[j]);
+        }
+        stv<V>(p.zs + e, zs);
+        stv<V>(p.dz + e, dz);
+        if (p.xhat) stv<V>(p.xhat + e, x);
+    }
+}
+
+// q_sample_kernel's value as that kernel is compiled: two products, each rounded, then their sum (vd_consist_pair's z_t is
+// vd_q_sample's bit for bit: tests/test_consistency_gpu.py holds the two together)
+__device__ __forceinline__ float q_sample_value(float x0, float eps, float sa, float ss) {
+#pragma clang fp contract(off)
+    return x0 * sa + eps * ss;
+}
+
+// training mode: z_t (q_sample), z_s = alpha_s x_0 + sigma_s eps and dz = (alpha_s - alpha_t) x_0 + (sigma_s - sigma_t) eps in one pass
+template <int V>
+__global__ void consist_pair_kernel(const float* x0, const float* eps, const float* coef, float* zt, float* zs, float* dz, int n,
+                                    long long N) {
+    const long long total = (long long)n * N / V;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N;
+        const float* k = coef + CK * b;
+        const float l = k[13], da = k[18], ds = k[19], as = k[20], ss = k[21];
+        const float sat = sqrtf(1.f / (1.f + expf(-l))), sst = sqrtf(1.f / (1.f + expf(l)));
+        float x[V], ep[V], a[V], s[V], d[V];
+        ldv<V>(x0 + e, x);
+        ldv<V>(eps + e, ep);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            a[j] = q_sample_value(x[j], ep[j], sat, sst);
+            s[j] = axpby(as, x[j], ss, ep[j]);
+            d[j] = axpby(da, x[j], ds, ep[j]);
+        }
+        stv<V>(zt + e, a);
+        stv<V>(zs + e, s);
+        stv<V>(dz + e, d);
+    }
+}
+
+struct ConsistLossArgs {
+    const float* zt; const float* zs; const float* dz; const float* sout; const float* tout; const float* coef; int type, metric;
+    double c; int n; long long N;
+};
+
+// one workgroup per sample, fixed summation order.  resid = [student - z_t] - [target - z_s] - dz; rows with i = 1 SELECT the
+// boundary condition (target = z_s, its bracket 0) and never read the target network's output.  S = sum resid^2 in fp64;
+// metric 0 (l2): loss = omega S/N, aux = 2/N;  metric 1 (pseudo-Huber): loss = omega S/(sqrt(S + c^2) + c), aux = 1/sqrt(S + c^2)
+template <int V>
+__global__ __launch_bounds__(256) void consist_loss_fwd_kernel(const ConsistLossArgs p, float* loss, float* resid, float* aux,
+                                                               float* target) {
+    __shared__ double sh[8];
+    const long long b = blockIdx.x, N = p.N;
+    const float* k = p.coef + CK * b;
+    const bool both = p.type == OUT_BOTH, last = k[CK_LAST] != 0.f;
+    const int Co = both ? 2 : 1;
+    const float ga0 = k[5], gb0x = k[6], gb0e = k[7], sb0x = k[9], sb0e = k[10], ga0m1 = k[15], sa0m1 = k[16];
+    const float* sb = p.sout + b * Co * N;
+    const float* tb = p.tout + b * Co * N;
+    double acc = 0.0;
+    for (long long i = (long long)threadIdx.x * V; i < N; i += (long long)blockDim.x * V) {
+        float z[V], zs[V], dz[V], so[V], soe[V] = {}, go[V] = {}, goe[V] = {}, r[V];
+        ldv<V>(p.zt + b * N + i, z);
+        ldv<V>(p.zs + b * N + i, zs);
+        ldv<V>(p.dz + b * N + i, dz);
+        ldv<V>(sb + i, so);
+        if (both) ldv<V>(sb + N + i, soe);
+        if (!last) {
+            ldv<V>(tb + i, go);
+            if (both) ldv<V>(tb + N + i, goe);
+        }
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float ds = consist_diff(sa0m1, sb0x, sb0e, both, z[j], so[j], soe[j]);
+            const float dt = last ? 0.f : consist_diff(ga0m1, gb0x, gb0e, both, zs[j], go[j], goe[j]);
+            r[j] = (ds - dt) - dz[j];
+            acc += (double)r[j] * (double)r[j];
+        }
+        stv<V>(resid + b * N + i, r);
+        if (target) {
+            float tg[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) tg[j] = last ? zs[j] : x0_hat(ga0, gb0x, gb0e, both, zs[j], go[j], goe[j]);
+            stv<V>(target + b * N + i, tg);
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (threadIdx.x == 0) {
+        const double om = (double)k[11];
+        if (p.metric == 0) {
+            loss[b] = (float)(om * (acc / (double)N));
+            aux[b] = (float)(2.0 / (double)N);
+        } else {
+            const double q = sqrt(acc + p.c * p.c);
+            loss[b] = (float)(om * (acc / (q + p.c)));
+            aux[b] = (float)(1.0 / q);
+        }
+    }
+}
+
+// dout = gloss[b] * omega_b * aux[b] * resid * b0x (second half of a "both" student: * b0e)
+template <int V>
+__global__ void consist_loss_bwd_kernel(const float* resid, const float* coef, const float* gloss, const float* aux, int stype,
+                                        float* dout, int n, long long N) {
+#pragma clang fp contract(off)
+    const long long total = (long long)n * N / V;
+    const int Co = stype == OUT_BOTH ? 2 : 1;
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        const float* k = coef + CK * b;
+        const float g = gloss[b] * k[11] * aux[b], bx = k[9], be = k[10];
+        float r[V], d[V];
+        ldv<V>(resid + e, r);
+#pragma unroll
+        for (int j = 0; j < V; ++j) d[j] = g * r[j] * bx;
+        stv<V>(dout + b * Co * N + i, d);
+        if (stype == OUT_BOTH) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) d[j] = g * r[j] * be;
+            stv<V>(dout + b * Co * N + N + i, d);
+        }
+    }
+}
+
+// e <- e + (1 - decay) (p - e), adamw_ema_kernel's expression, over every tensor of a module in ONE launch.  items: device table,
+// 8 x int64 per tensor: {dst e, src p, count, 0, 0, 0, 0, first block}; blocks of 256 elements.  omd = 1 - decay; omd = 1 copies.
+// A wave owns EMA_U consecutive blocks: one search of the table for the first, a walk for the rest; a full block whose two bases are
+// 16-byte aligned moves as one dwordx4 per lane, any other as four coalesced dwords -- the same expression, the same bits.
+enum { EMA_U = 4 };
+
+__device__ __forceinline__ float ema_track(float e, float p, float omd) {
+#pragma clang fp contract(off)
+    return omd == 1.f ? p : e + omd * (p - e);
+}
+
+__global__ __launch_bounds__(256) void ema_track_batched_kernel(const long long* items, int n, long long total_blocks, float omd) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    long long blk = ((long long)blockIdx.x * 4 + wave) * EMA_U;
+    if (blk >= total_blocks) return;
+    int lo = 0, hi = n - 1;                                  // last item whose first block <= blk
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (items[8 * mid + 7] <= blk) lo = mid; else hi = mid - 1;
+    }
+    for (int u = 0; u < EMA_U && blk < total_blocks; ++u, ++blk) {
+        while (lo + 1 < n && items[8 * (lo + 1) + 7] <= blk) ++lo;
+        const long long* it = items + 8 * lo;
+        const long long count = it[2], base = (blk - it[7]) * 256;
+        float* dst = reinterpret_cast<float*>(it[0]) + base;
+        const float* src = reinterpret_cast<const float*>(it[1]) + base;
+        if (count - base >= 256 && ((reinterpret_cast<uintptr_t>(dst) | reinterpret_cast<uintptr_t>(src)) & 15) == 0) {
+            float e[4], p[4];
+            ldv<4>(dst + 4 * lane, e);
+            ldv<4>(src + 4 * lane, p);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e[j] = ema_track(e[j], p[j], omd);
+            stv<4>(dst + 4 * lane, e);
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = j * 64 + lane;
+                if (base + i < count) dst[i] = ema_track(dst[i], src[i], omd);
+            }
+        }
+    }
+}
+
 // ---- DPM-Solver++(2M) (Lu et al. 2022, data-prediction form): one reverse step of the probability-flow ODE in log-SNR time from the
 // guided x0 prediction g of this step and the one of the step before (hist).  k[8] = {a0, b0x, b0e, c1, c2, c2*rho, w_guide, 0} with
 // c1, c2 the DDIM weights of the step and rho = h / (2 h_prev); c2*rho = 0 gives the DDIM step, (c1, c2, c2*rho) = (0, 1, 0) the
@@ -1300,6 +1500,68 @@ extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const 
     launch_elems(distill_loss_bwd_kernel<4>, distill_loss_bwd_kernel<1>, N % 4 == 0 && all_aligned16(resid, dout), n * N, stream, resid, coef,
                  gloss, (int)student_type, dout, (int)n, N);
     VD_LAUNCH_CHECK("distill_loss_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_consist_mid(const float* zt, const float* out, const float* coef, int32_t teacher_type, int32_t cfg, int32_t clip,
+                              float* zs, float* dz, float* xhat, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3, "vd_consist_mid: bad model_out_type %d", teacher_type);
+    VD_REQUIRE(zt && out && coef && zs && dz, "vd_consist_mid: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_mid: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    ConsistMidArgs p = {zt, out, coef, teacher_type, cfg ? 1 : 0, clip ? 1 : 0, zs, dz, xhat, n, N};
+    launch_elems(consist_mid_kernel<4>, consist_mid_kernel<1>, N % 4 == 0 && all_aligned16(zt, out, zs, dz, xhat), n * N, stream, p);
+    VD_LAUNCH_CHECK("consist_mid_kernel");
+    return 0;
+}
+
+extern "C" int vd_consist_pair(const float* x0, const float* eps, const float* coef, float* zt, float* zs, float* dz, int32_t n,
+                               int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(x0 && eps && coef && zt && zs && dz, "vd_consist_pair: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_pair: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    launch_elems(consist_pair_kernel<4>, consist_pair_kernel<1>, N % 4 == 0 && all_aligned16(x0, eps, zt, zs, dz), n * N, stream, x0, eps,
+                 coef, zt, zs, dz, (int)n, N);
+    VD_LAUNCH_CHECK("consist_pair_kernel");
+    return 0;
+}
+
+extern "C" int vd_consist_loss_fwd(const float* zt, const float* zs, const float* dz, const float* student_out, const float* target_out,
+                                   const float* coef, int32_t out_type, int32_t metric, double huber_c, float* loss, float* resid,
+                                   float* aux, float* target, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(out_type >= 0 && out_type <= 3, "vd_consist_loss_fwd: bad model_out_type %d", out_type);
+    VD_REQUIRE(metric == 0 || (metric == 1 && huber_c > 0.0), "vd_consist_loss_fwd: metric must be 0 (l2) or 1 (huber, c > 0)");
+    VD_REQUIRE(zt && zs && dz && student_out && target_out && coef && loss && resid && aux, "vd_consist_loss_fwd: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_loss_fwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    ConsistLossArgs p = {zt, zs, dz, student_out, target_out, coef, out_type, metric, huber_c, n, N};
+    launch_rows(consist_loss_fwd_kernel<4>, consist_loss_fwd_kernel<1>,
+                N % 4 == 0 && all_aligned16(zt, zs, dz, student_out, target_out, resid, target), n, 256, stream, p, loss, resid, aux, target);
+    VD_LAUNCH_CHECK("consist_loss_fwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_consist_loss_bwd(const float* resid, const float* coef, const float* gloss, const float* aux, int32_t out_type,
+                                   float* dout, int32_t n, int32_t C, int32_t HW, void* stream) {
+    VD_REQUIRE(out_type >= 0 && out_type <= 3, "vd_consist_loss_bwd: bad model_out_type %d", out_type);
+    VD_REQUIRE(resid && coef && gloss && aux && dout, "vd_consist_loss_bwd: null pointer");
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_loss_bwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    const long long N = (long long)C * HW;
+    launch_elems(consist_loss_bwd_kernel<4>, consist_loss_bwd_kernel<1>, N % 4 == 0 && all_aligned16(resid, dout), n * N, stream, resid, coef,
+                 gloss, aux, (int)out_type, dout, (int)n, N);
+    VD_LAUNCH_CHECK("consist_loss_bwd_kernel");
+    return 0;
+}
+
+extern "C" int vd_ema_track_batched(const int64_t* items_dev, int32_t n, int64_t total_blocks, double decay, void* stream) {
+    VD_REQUIRE(items_dev && n > 0 && total_blocks > 0 && total_blocks < (1LL << 31), "vd_ema_track_batched: bad table");
+    VD_REQUIRE(decay >= 0.0 && decay <= 1.0, "vd_ema_track_batched: decay must lie in [0, 1]");
+    const float omd = (float)(1.0 - decay);                  // rounded once, as a tensor expression rounds its scalar
+    if (omd == 0.f) return 0;                                // decay = 1: the target stays as it is, whatever the source holds
+    const long long per_group = 4 * EMA_U;                  // blocks per workgroup of four waves
+    hipLaunchKernelGGL(ema_track_batched_kernel, dim3((unsigned)((total_blocks + per_group - 1) / per_group)), dim3(256), 0,
+                       (hipStream_t)stream, reinterpret_cast<const long long*>(items_dev), (int)n, (long long)total_blocks, omd);
+    VD_LAUNCH_CHECK("ema_track_batched_kernel");
     return 0;
 }
 

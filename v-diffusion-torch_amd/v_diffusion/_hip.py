@@ -130,6 +130,11 @@ _SIGNATURES = {
     "vd_distill_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vd_consist_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_consist_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_consist_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    "vd_consist_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
+    "vd_ema_track_batched": (C.c_int, [_vp, _i32, _i64, _f64, _vp]),
     "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_unipc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     "vd_abs_kth_rows": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
@@ -858,6 +863,35 @@ def distill_loss_fwd(xhat, dhat, zmid, tout, zt, sout, coef, tmot, smot, cfg, cl
 
 def distill_loss_bwd(resid, coef, gloss, smot, dout, n, Cc, HW):
     _check(lib().vd_distill_loss_bwd(ptr(resid), ptr(coef), ptr(gloss), smot, ptr(dout), n, Cc, HW, stream()), "vd_distill_loss_bwd")
+
+
+CONSIST_METRICS = {"l2": 0, "huber": 1}
+
+
+def consist_mid(zt, tout, coef, tmot, cfg, clip, zs, dz, xhat, n, Cc, HW):
+    """xhat may be None"""
+    _check(lib().vd_consist_mid(ptr(zt), ptr(tout), ptr(coef), tmot, int(cfg), int(clip), ptr(zs), ptr(dz), ptr(xhat), n, Cc, HW, stream()),
+           "vd_consist_mid")
+
+
+def consist_pair(x0, eps, coef, zt, zs, dz, n, Cc, HW):
+    _check(lib().vd_consist_pair(ptr(x0), ptr(eps), ptr(coef), ptr(zt), ptr(zs), ptr(dz), n, Cc, HW, stream()), "vd_consist_pair")
+
+
+def consist_loss_fwd(zt, zs, dz, sout, tout, coef, mot, metric, huber_c, loss, resid, aux, target, n, Cc, HW):
+    """metric: 0 l2, 1 pseudo-Huber with the absolute constant huber_c; target may be None"""
+    _check(lib().vd_consist_loss_fwd(ptr(zt), ptr(zs), ptr(dz), ptr(sout), ptr(tout), ptr(coef), mot, int(metric), float(huber_c), ptr(loss),
+                                     ptr(resid), ptr(aux), ptr(target), n, Cc, HW, stream()), "vd_consist_loss_fwd")
+
+
+def consist_loss_bwd(resid, coef, gloss, aux, mot, dout, n, Cc, HW):
+    _check(lib().vd_consist_loss_bwd(ptr(resid), ptr(coef), ptr(gloss), ptr(aux), mot, ptr(dout), n, Cc, HW, stream()), "vd_consist_loss_bwd")
+
+
+def ema_track_batched(table, n, total_blocks, decay):
+    """table: int64 device tensor [n][8], see vd_ema_track_batched"""
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+    _check(lib().vd_ema_track_batched(table.data_ptr(), n, total_blocks, float(decay), stream()), "vd_ema_track_batched")
 
 
 def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=None):

@@ -872,6 +872,20 @@ class GaussianDiffusion:
                               use_graph).cpu()
 
     @torch.inference_mode()
+    def p_sample_consistency(self, denoise_fn, shape, noise=None, label=None, device=None, seed=None, steps=1, clip_denoised=True):
+        """Multistep consistency sampling (extension, v_diffusion/consistency.py; Song et al. 2023, Algorithm 1) for a network trained
+        with ``ConsistencyDiffusion``: at each grid index the network is called once and its (clipped, guided) x0 prediction x_hat is
+        re-noised to the next index, x = alpha_next x_hat + sigma_next eps; the last index returns x_hat.  ``steps`` = an int n <=
+        sample_timesteps (the evenly spaced ``consistency_schedule(sample_timesteps, n)``; 1 = one network call) or a strictly
+        descending list of grid indices starting at sample_timesteps.  Each step is ONE launch of vd_sample_step with the row {a0, b0x,
+        b0e, 0, alpha_next, sigma_next, w_guide, 0} of ``consistency_sample_coefs`` (last_step = 1 at the end): no step kernel of its own.
+        Draw order of the seeded generator: x_T first (``p_sample``'s for the seed), then one image-shaped draw per non-final step.
+        Guidance is honoured; ``model_var_type="learned"`` and ``x0eps_coef`` are refused; there is no captured-graph path.  Returns a
+        CPU tensor."""
+        from .consistency import p_sample_consistency
+        return p_sample_consistency(self, denoise_fn, shape, noise, label, device, seed, steps, clip_denoised).cpu()
+
+    @torch.inference_mode()
     def p_sample_inpaint(self, denoise_fn, known, mask, label=None, device=None, seed=None, use_ddim=False, jump_length=1, resamplings=1,
                          start=None, clip_denoised=True):
         """Reverse chain conditioned on a given image (extension, v_diffusion/inpaint.py): RePaint inpainting (Lugmayr et al. 2022) and,

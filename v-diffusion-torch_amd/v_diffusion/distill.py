@@ -61,6 +61,19 @@ def _omega(reweight_type, lt64):
     raise NotImplementedError(reweight_type)
 
 
+def _snap_up(t, N):
+    """the (B,) fp64 grid index of ``t`` snapped UP to the N-step grid: the smallest i in 1..N with i/N >= t (t*N may round up past an
+    integer: 7/100 * 100 > 7 stays at 7)"""
+    tf = torch.as_tensor(t).reshape(-1).to(F64)
+    i = torch.ceil(tf * N)
+    return torch.where((i - 1) / N >= tf, i - 1, i).clamp(1, N)
+
+
+def _c12m1(ls64, lt64):
+    """c1 + c2 - 1 of the DDIM step s <- t in fp64, without forming c1 + c2: sigma_s/sigma_t - 1 - expm1((l_t - l_s)/2) alpha_s"""
+    return torch.exp(0.5 * (F.logsigmoid(-ls64) - F.logsigmoid(-lt64))) - torch.expm1(0.5 * (lt64 - ls64)) * torch.sigmoid(ls64).sqrt() - 1.0
+
+
 def distill_coefs(logsnr_fn, t, student_steps, student_out_type, teacher_out_type, reweight_type, teacher_w_guide=0.):
     """``(coef, (t, t_mid, t_end))``: the (B, 20) fp32 table of the vd_distill_* kernels (columns: the names above) and the three
     fp64 time tensors t = i/N (``t`` snapped UP to the student grid, i = 1..N), t - 1/(2N), t - 1/N.
@@ -72,16 +85,14 @@ def distill_coefs(logsnr_fn, t, student_steps, student_out_type, teacher_out_typ
     N = int(student_steps)
     if N < 1:
         raise ValueError(f"student_steps must be >= 1, got {student_steps}")
-    tf = torch.as_tensor(t).reshape(-1).to(F64)
-    i = torch.ceil(tf * N)
-    i = torch.where((i - 1) / N >= tf, i - 1, i).clamp(1, N)          # smallest i with i/N >= t (t*N may round up past an integer)
+    i = _snap_up(t, N)
     tt, tm, te = i / N, (2 * i - 1) / (2 * N), (i - 1) / N
     lt, lm, le = (logsnr_fn(v).to(torch.float32).reshape(-1) for v in (tt, tm, te))
     last = i == 1                                                      # t'' = 0: the target is the x0 prediction at t'
     c1, c2, _ = logsnr_to_posterior_ddim(lm, lt, eta=0.)
     l, m, e = lt.double(), lm.double(), le.double()
     # c1 + c2 - 1 of that step in fp64, rounded on its own: z_t' - z_t = (c1 + c2 - 1) z_t + c2 (x_hat - z_t)
-    c12m1 = torch.exp(0.5 * (F.logsigmoid(-m) - F.logsigmoid(-l))) - torch.expm1(0.5 * (l - m)) * torch.sigmoid(m).sqrt() - 1.0
+    c12m1 = _c12m1(m, l)
     # c2(s<-t) = alpha_s (1 - exp((l_t - l_s)/2)); alpha_t'' divides out of the ratio
     w2 = torch.expm1(0.5 * (m - e)) / torch.expm1(0.5 * (l - e))
     w2 = torch.where(last, torch.ones_like(w2), w2).float()
