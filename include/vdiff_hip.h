@@ -221,6 +221,27 @@ int vd_conv3x3_wgrad_wino43_phase(const float* xin, int64_t ldx, const float* dy
 /* split-K slabs per plane of the calling thread's last vd_conv3x3_wgrad_wino43 launch (test / profiling aid) */
 int vd_wino43_wgrad_last_kernel(void);
 
+/* Forward 3x3 convolution through PLANES (csrc/wino43.hip): the weight gradient's input transform writes V = B^T d B
+ * ([T/16][36][16][Cin], T = nimg (H/4) (W/4) tiles, vd_conv3x3_wino43_v_floats floats), the 36 products M[xi] = V[xi] U[xi]^T run as one
+ * batched launch of the split-operand tile engine and an HBM-bound pass writes y = A^T M A + bias (+ res) and the GroupNorm partials of y
+ * ([nimg][chunks][2][Cout], vd_conv3x3_wino43_fwd_chunk_rows pixels per chunk; fixed summation order).  w_oihw is the raw kernel
+ * [Cout][Cin][3][3]; ws: vd_conv3x3_wino43_fwd_planes_ws_bytes.  phase: 7 = everything, or 1 (pack + V transform), 2 (GEMMs), 4 (output
+ * transform) for per-kernel timing.  V is left behind for vd_conv3x3_wgrad_wino43_v: the same weight gradient as vd_conv3x3_wgrad_wino43,
+ * bit for bit, without its input transform.
+ * vd_conv3x3_fwd_planes_preferred: host rule (occupancy floor + same-box measurement) for where this form beats the fused forward kernel:
+ * `training` != 0 counts the weight gradient's saved transform, 0 the forward alone. */
+int vd_conv3x3_wino43_fwd_planes_supported(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int64_t ldx, int64_t ldy,
+                                           int64_t ldres);
+size_t vd_conv3x3_wino43_v_floats(int32_t nimg, int32_t H, int32_t W, int32_t Cin);
+size_t vd_conv3x3_wino43_fwd_planes_ws_bytes(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+int vd_conv3x3_fwd_planes_preferred(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t training);
+int vd_conv3x3_wino43_fwd_planes(const float* xin, int64_t ldx, const float* w_oihw, const float* bias, const float* res, int64_t ldres,
+                                 float* y, int64_t ldy, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, float* stats_part,
+                                 float* V, float* ws, size_t ws_bytes, int32_t phase, void* stream);
+int vd_conv3x3_wgrad_wino43_v(const float* V, const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                              float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws, size_t ws_bytes,
+                              int32_t phase, void* stream);
+
 /* all 3x3 kernels of a network in one launch: items_dev = [n][8] int64 {w, uf, ud, Cout, Cin, tiled, 0, first 256-thread block};
  * tiled = 1 (Cout, Cin multiples of 16): the tensor takes (Cout/16)*(Cin/16) blocks of one 16x16 tile, else ceil(Cout*Cin/256) */
 int vd_wino_pack_batched(const int64_t* items_dev, int32_t n, int64_t total_blocks, void* stream);

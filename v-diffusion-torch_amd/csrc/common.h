@@ -26,6 +26,9 @@ int vd_gemm_grouped_wgrad_kblk(const float* const* A, const float* const* B, flo
                                int32_t N, int32_t K, int64_t lda, int64_t ldb, int64_t ldc, int32_t splitk, float* ws, size_t ws_bytes,
                                void* stream, int64_t a_kblk, int64_t b_kblk, int32_t slabs_only);   // gemm.hip: grouped weight-gradient GEMMs on K-blocked operands
 int vd_gemm_grouped_wgrad_used_slabs(int32_t count, int32_t M, int32_t N, int32_t K, int32_t splitk);   // slabs such a launch fills
+// gemm.hip: vd_gemm on a ROW-kind A whose M rows are stored in blocks of 16 (row m at (m >> 4) * a_rblk + (m & 15) * lda): the K-blocked
+// V image of the F(4x4,3x3) weight gradient read as the row operand of the forward plane GEMMs (wino43.hip)
+int vd_gemm_rowblk(const vd_gemm_desc* d, int64_t a_rblk, void* stream);
 extern thread_local int vd_g_last_tile;      // code of the calling thread's last matmul-shaped launch (vd_gemm_last_tile)
 // (decimal fields [tr + 2 spl][kt: 2 digits][bm: 3][bn: 3]: transposed epilogue, split-operand form, K tile or 0 = register-staged kernel; _hip.tile_fields)
 inline int vd_tile_code(bool tr, bool spl, int kt, int bm, int bn) {

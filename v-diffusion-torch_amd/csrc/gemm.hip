@@ -46,6 +46,8 @@ struct GemmArgs {
     int lgW, lgHW;                            // log2 of W and H*W when both are powers of two, else -1 (shift/mask instead of divisions)
     long long a_kblk, b_kblk;                 // GROUPED COL operands stored in K BLOCKS of 16 rows: row k of an entry sits at (k >> 4) * kblk + (k & 15) * ld
                                               // (0: plain [K][ld] rows).  Lets 36 same-shape operands interleave block by block: [K/16][36][16][ld]
+                                              // UNGROUPED launches with a ROW-kind A (vd_gemm_rowblk): a_kblk != 0 = the M rows of A are stored in such blocks
+                                              // of 16 -- row m at (m >> 4) * a_kblk + (m & 15) * lda -- so the forward planes read the weight gradient's V
 };
 
 // timing-probe bits: compiled out of the product library (VD_PROBE_BUILD is a constant: every `PB(p) & bit` branch folds away);
@@ -537,7 +539,8 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
             const int c = (lane % RLPR) ^ swz_of<KT>(row);
             const int m = m0 + row;
             kcA[j] = c * 4;
-            voA[j] = (m < p.M) ? (unsigned)(row * (int)p.lda + c * 4) * 4u : OOB;      // < 2^31 by use_dma()
+            const int rowoff = (!GROUPED && AK == VD_ROW && p.a_kblk) ? (row >> 4) * (int)p.a_kblk + (row & 15) * (int)p.lda : row * (int)p.lda;
+            voA[j] = (m < p.M) ? (unsigned)(rowoff + c * 4) * 4u : OOB;      // < 2^31 by use_dma() (blocked rows: vd_gemm_rowblk)
             unsigned mk = 0;
             if (AK == VD_IM2COL) {
                 int y, x;
@@ -568,7 +571,7 @@ __device__ __forceinline__ void gemm_dma_body(const GemmArgs& p, const std::cond
         }
     }
     // block-constant parts of the source addresses
-    const float* Ablk = (AK == VD_COL) ? A + m0 : A + (long long)m0 * p.lda;
+    const float* Ablk = (AK == VD_COL) ? A + m0 : ((!GROUPED && AK == VD_ROW && p.a_kblk) ? A + (long long)(m0 >> 4) * p.a_kblk : A + (long long)m0 * p.lda);
     const float* Bblk = (BK == VD_ROW) ? B + (long long)n0 * p.ldb : ((BK == VD_COL) ? B + n0 : B + ci0);
     const long long tapoffB = (BK == VD_IM2COL) ? (long long)((tapN / 3 - 1) * p.W + (tapN % 3 - 1)) * p.ldb : 0;
 
@@ -1509,7 +1512,7 @@ void launch_tile(const GemmPlan& P, bool splitk, const GemmArgs& a, dim3 grid, h
     else launch_tile2<AK, BK, false>(P, a, grid, st);
 }
 
-int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
+int run_gemm(const vd_gemm_desc& d, hipStream_t st, long long a_rblk = 0) {
     VD_REQUIRE(d.M > 0 && d.N > 0 && d.K > 0, "vd_gemm: empty problem M=%d N=%d K=%d", d.M, d.N, d.K);
     VD_REQUIRE(d.A && d.B && d.C, "vd_gemm: null operand");
     VD_REQUIRE(vd_aligned16(d.A) && vd_aligned16(d.B), "vd_gemm: A/B must be 16-byte aligned");
@@ -1540,6 +1543,11 @@ int run_gemm(const vd_gemm_desc& d, hipStream_t st) {
     a.colsum = d.colsum; a.colsum_accumulate = d.colsum_accumulate;
     a.stats = d.stats; a.stats_hw = d.stats_hw;
     a.sBias = d.sBias;
+    a.group_S = 0; a.a_kblk = a_rblk; a.b_kblk = 0;
+    if (a_rblk) {           // A rows in blocks of 16 (vd_gemm_rowblk): the LDS-DMA kernels only, whole blocks, block offsets inside the 32-bit range
+        VD_REQUIRE(ak == VD_ROW && bk == VD_ROW && d.splitk <= 1 && d.M % 16 == 0 && a_rblk > 0 && a_rblk % 4 == 0 && use_dma(a) &&
+                   16 * a_rblk + 16 * d.lda + 256 < 0x70000000LL / 4, "vd_gemm_rowblk: needs ROW/ROW operands, M %% 16 == 0 and a block pitch in range");
+    }
     a.lgW = a.lgHW = -1;
     if ((conv || wgrad) && (d.W & (d.W - 1)) == 0 && ((d.H * d.W) & (d.H * d.W - 1)) == 0) {
         a.lgW = __builtin_ctz((unsigned)d.W); a.lgHW = __builtin_ctz((unsigned)(d.H * d.W));
@@ -1780,6 +1788,11 @@ extern "C" int vd_gemm_plan_tile(int32_t M, int32_t N, int32_t K, int32_t a_kind
 extern "C" int vd_gemm(const vd_gemm_desc* d, void* stream) {
     VD_REQUIRE(d != nullptr, "vd_gemm: null descriptor");
     return run_gemm(*d, (hipStream_t)stream);
+}
+
+int vd_gemm_rowblk(const vd_gemm_desc* d, int64_t a_rblk, void* stream) {
+    VD_REQUIRE(d != nullptr, "vd_gemm_rowblk: null descriptor");
+    return run_gemm(*d, (hipStream_t)stream, a_rblk);
 }
 
 extern "C" int vd_conv3x3(const float* xin, int64_t ldx, const float* wpack, const float* bias, const float* res,

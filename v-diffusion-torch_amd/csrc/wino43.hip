@@ -35,6 +35,7 @@
 //     memory (36 linear DMA pieces) and a lane's fragment for both 16-channel blocks
 //     and both k-steps is one conflict-free ds_read_b128.
 #include "common.h"
+#include <stdlib.h>
 #include <type_traits>
 
 namespace {
@@ -646,16 +647,19 @@ struct WgT43 {
     const float* x; long long ldx; const float* dy; long long lddy;
     float* V; float* dM;                       // [T/16][36][16][Cin], [T/16][36][16][Cout]: blocks of 16 tiles, the 36 planes of a block adjacent
     int nimg, H, W, Cin, Cout, TW, TPI, T;     // tiles per row / image / in all
+    int z0;                                    // half of a grid.z = 1 launch: 0 = the input patches alone (the forward through planes writes V, which the
+                                               // weight gradient then takes as given), 1 = the gradients alone
 };
 
-// block (64 channel quads, 4 tiles); grid (ceil(max(Cin, Cout) / 256), T / 4, 2): z = 0 transforms the input patches, z = 1 the gradients
+// block (64 channel quads, 4 tiles); grid (T / 4, ceil(max(Cin, Cout) / 256), 2): z = 0 transforms the input patches, z = 1 the gradients
+// (grid.z = 1: the half p.z0 alone)
 __global__ __launch_bounds__(256) void wino43_wgrad_transform_kernel(const WgT43 p) {
     const int quad = blockIdx.y * 64 + threadIdx.x, tile = blockIdx.x * 4 + threadIdx.y;      // (tiles on grid.x: no 65 535 bound)
     if (tile >= p.T) return;
     const int img = tile / p.TPI, tin = tile - img * p.TPI;
     const int ty = tin / p.TW, tx = tin - ty * p.TW;
     const int c4 = 4 * quad;
-    if (blockIdx.z == 0) {
+    if ((int)blockIdx.z + p.z0 == 0) {
         if (c4 >= p.Cin) return;
         f32x4 R[6][6];
 #pragma unroll
@@ -815,6 +819,112 @@ __global__ __launch_bounds__(384) void wino43_wgrad_reduce_finish_kernel(const f
     o[2] = accumulate ? o[2] + w2 : w2;
 }
 
+// ==================================================================================================================
+// FORWARD through planes (round 8): the three pieces of the fused forward kernel as three launches, for batches large enough that
+// the 36 plane products M[xi] = V[xi] . U[xi]^T fill the chip as ONE batched launch of the split-operand tile engine (gemm.hip):
+//   V   = wino43_wgrad_transform_kernel's input half (the SAME device code, layout and bits the weight gradient computes: V stays on
+//         the tape and the weight gradient transforms dY alone),
+//   M   = 36 ROW/ROW GEMMs, rows = tiles, K = Cin, N = Cout, plane-major [36][T][Cout],
+//   y   = A^T M A + bias (+ res) and the GroupNorm partial sums (kernel below), A^T the dyadic one of the fused epilogue.
+// ==================================================================================================================
+// plane-major forward image U[xi][co][ci] = (G w[co][ci] G^T)[xi]: the values of pack43_tile(fwd = 1) as the ROW-kind B operand
+__global__ __launch_bounds__(256) void wino43_pack_planes_kernel(const float* w, float* U, int Cout, int Cin) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, plane = (long long)Cout * Cin;
+    if (idx >= plane) return;
+    const float* src = w + idx * 9;
+    const double Gd[6][3] = {{64.0 / 81, 0.0, 0.0}, {-128.0 / 243, -32.0 / 81, -8.0 / 27}, {-128.0 / 243, 32.0 / 81, -8.0 / 27},
+                             {32.0 / 243, 16.0 / 81, 8.0 / 27}, {32.0 / 243, -16.0 / 81, 8.0 / 27}, {0.0, 0.0, 1.0}};
+    double g[3][3], tmp[6][3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = 0; b < 3; ++b) g[a][b] = (double)src[a * 3 + b];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tmp[a][c] = Gd[a][0] * g[0][c] + Gd[a][1] * g[1][c] + Gd[a][2] * g[2][c];
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = 0; b < 6; ++b) U[(6 * a + b) * plane + idx] = (float)(tmp[a][0] * Gd[b][0] + tmp[a][1] * Gd[b][1] + tmp[a][2] * Gd[b][2]);
+}
+
+// A^T of {0, +-3/4, +-3/2, inf}, 4 x 6: [1 1 1 1 1 0 ; 0 3/4 -3/4 3/2 -3/2 0 ; 0 9/16 9/16 9/4 9/4 0 ; 0 27/64 -27/64 27/8 -27/8 1]
+__device__ __forceinline__ void at4(const f32x4 (&m)[6], f32x4 (&o)[4]) {
+    const f32x4 p12 = m[1] + m[2], q12 = m[1] - m[2], p34 = m[3] + m[4], q34 = m[3] - m[4];
+    o[0] = m[0] + p12 + p34;
+    o[1] = 0.75f * q12 + 1.5f * q34;
+    o[2] = 0.5625f * p12 + 2.25f * p34;
+    o[3] = 0.421875f * q12 + 3.375f * q34 + m[5];
+}
+
+struct Out43 {
+    const float* M; long long plane;           // [36][T][Cout], plane = T * Cout
+    const float* bias; const float* res; long long ldr;
+    float* y; long long ldy;
+    float* stats;                              // [chunk][2][Cout] or NULL: chunk = CT consecutive tiles (one image, or 16 rows of a 64-wide one)
+    int H, W, Cout, TW, TPI, T, CT;
+};
+
+// HBM-bound: block (16 channel quads, 16 tiles) = one statistics chunk x 64 channels, grid (T / CT, ceil(Cout / 64)); a thread walks the
+// chunk's tiles tl, tl + 16, ... (CT = 16 or 64).  The partial sums of a chunk are summed in fixed order: per thread over its tiles, then
+// over the 16 tile lanes through LDS -- no atomics.
+__global__ __launch_bounds__(256) void wino43_out_transform_kernel(const Out43 p) {
+    __shared__ float ssum[2][16][64];
+    const int q = threadIdx.x, tl = threadIdx.y;
+    const int c4 = blockIdx.y * 64 + 4 * q;
+    const bool in = c4 < p.Cout;
+    f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = s1;
+    if (in) {
+        f32x4 bv = {0.f, 0.f, 0.f, 0.f};
+        if (p.bias) bv = *reinterpret_cast<const f32x4*>(p.bias + c4);
+        for (int i = 0; i < p.CT; i += 16) {
+            const int tile = blockIdx.x * p.CT + i + tl;
+            if (tile >= p.T) break;
+            const int img = tile / p.TPI, tin = tile - img * p.TPI;
+            const int ty = tin / p.TW, tx = tin - ty * p.TW;
+            const float* mp = p.M + (long long)tile * p.Cout + c4;
+            f32x4 S[6][4];
+#pragma unroll
+            for (int a = 0; a < 6; ++a) {
+                f32x4 m[6];
+#pragma unroll
+                for (int b = 0; b < 6; ++b) m[b] = *reinterpret_cast<const f32x4*>(mp + (long long)(6 * a + b) * p.plane);
+                at4(m, S[a]);                                       // along the row: S[a][v] = sum_b A^T[v][b] M[a][b]
+            }
+            const long long pix0 = ((long long)img * p.H + 4 * ty) * p.W + 4 * tx;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const f32x4 col[6] = {S[0][v], S[1][v], S[2][v], S[3][v], S[4][v], S[5][v]};
+                f32x4 o[4];
+                at4(col, o);                                        // y[u][v] = sum_a A^T[u][a] S[a][v]
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const long long pix = pix0 + (long long)u * p.W + v;
+                    f32x4 val = o[u] + bv;
+                    if (p.res) val += *reinterpret_cast<const f32x4*>(p.res + pix * p.ldr + c4);
+                    s1 += val; s2 += val * val;
+                    *reinterpret_cast<f32x4*>(p.y + pix * p.ldy + c4) = val;
+                }
+            }
+        }
+    }
+    if (!p.stats) return;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { ssum[0][tl][4 * q + j] = s1[j]; ssum[1][tl][4 * q + j] = s2[j]; }
+    __syncthreads();
+    const int tid = tl * 16 + q;
+    if (tid < 128) {
+        const int st = tid >> 6, ch = tid & 63;
+        if (blockIdx.y * 64 + ch < p.Cout) {
+            float v = 0.f;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) v += ssum[st][k][ch];
+            p.stats[((long long)blockIdx.x * 2 + st) * p.Cout + blockIdx.y * 64 + ch] = v;
+        }
+    }
+}
+
 struct Wg43Plan { bool ok; int T, S; size_t v_f, m_f, u_f, cs_f, gemm_bytes; };
 Wg43Plan wg43_plan(int nimg, int H, int W, int Cin, int Cout) {
     Wg43Plan g = {};
@@ -830,6 +940,20 @@ Wg43Plan wg43_plan(int nimg, int H, int W, int Cin, int Cout) {
     return g;
 }
 
+// floor and verdicts of vd_conv3x3_fwd_planes_preferred (profiles/r08_conv_planes_geometries.txt): same-box, forward + weight gradient, ms,
+// fused pair vs planes pair -- 256 -> 256 @32x32 B = 128 (8192 tiles) 0.884 vs 0.787, 512 -> 256 @32x32 1.588 vs 1.268; @16x16 B = 128 (2048
+// tiles) 0.246 vs 0.243 and 0.438 vs 0.415, inside the run-to-run spread; 256 -> 256 @32x32 B = 64 (4096 tiles) 0.420 vs 0.435: slower.  The 36
+// plane GEMMs are 36 x T / 128 x Cout / 256 workgroups of 128 x 256 on 512 resident slots: 4.5 rounds at 8192 tiles, 2.25 at 4096, 1.1 at 2048.
+// The forward ALONE is 4 % (256 -> 256) to 19 % (512 -> 256) faster at 8192 tiles, inside the spread for the narrow layers: inference stays fused.
+#ifndef VD_PLANES_MIN_TILES
+#define VD_PLANES_MIN_TILES 8192
+#endif
+#ifndef VD_PLANES_TRAINING
+#define VD_PLANES_TRAINING 1
+#endif
+#ifndef VD_PLANES_INFERENCE
+#define VD_PLANES_INFERENCE 0
+#endif
 thread_local int g_last43 = 0;
 #ifdef VD_PROBES
 unsigned long long* g_probe43 = nullptr;   // probe library only (vd_wino43_set_probe)
@@ -1000,26 +1124,30 @@ extern "C" size_t vd_conv3x3_wgrad_wino43_ws_bytes(int32_t nimg, int32_t H, int3
  * reduction of wide layers: FUSED_FINISH_MIN); 7 = all */
 static int wgrad43_impl(const float* xin, int64_t ldx, const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cin,
                         int32_t Cout, float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws,
-                        size_t ws_bytes, void* stream, int phases) {
-    VD_REQUIRE(xin && dy && dw_oihw && ws, "vd_conv3x3_wgrad_wino43: null operand");
+                        size_t ws_bytes, void* stream, int phases, const float* Vgiven = nullptr) {
+    // Vgiven: the V image of xin that vd_conv3x3_wino43_fwd_planes left behind ([T/16][36][16][Cin], the same kernel's output): the
+    // transform pass then runs its dY half alone and xin is not read
+    VD_REQUIRE((xin || Vgiven) && dy && dw_oihw && ws, "vd_conv3x3_wgrad_wino43: null operand");
+    VD_REQUIRE(!Vgiven || vd_aligned16(Vgiven), "vd_conv3x3_wgrad_wino43: V must be 16-byte aligned");
     VD_REQUIRE(vd_conv3x3_wgrad_wino43_supported(nimg, H, W, Cin, Cout, ldx, lddy),
                "vd_conv3x3_wgrad_wino43: unsupported geometry nimg=%d H=%d W=%d Cin=%d Cout=%d", nimg, H, W, Cin, Cout);
     VD_REQUIRE(Cin_w <= Cin && Cout_w <= Cout, "vd_conv3x3_wgrad_wino43: real dims exceed padded dims");
-    VD_REQUIRE(vd_aligned16(xin) && vd_aligned16(dy) && vd_aligned16(ws), "vd_conv3x3_wgrad_wino43: operands must be 16-byte aligned");
+    VD_REQUIRE((!xin || vd_aligned16(xin)) && vd_aligned16(dy) && vd_aligned16(ws), "vd_conv3x3_wgrad_wino43: operands must be 16-byte aligned");
     VD_REQUIRE(ws_bytes >= vd_conv3x3_wgrad_wino43_ws_bytes(nimg, H, W, Cin, Cout), "vd_conv3x3_wgrad_wino43: workspace too small");
     const Wg43Plan g = wg43_plan(nimg, H, W, Cin, Cout);
-    float* V = ws;
-    float* dM = V + g.v_f;
+    const float* V = Vgiven ? Vgiven : ws;
+    float* dM = ws + g.v_f;
     float* dU = dM + g.m_f;
     float* cs = dU + g.u_f;
     float* gws = cs + g.cs_f;
     hipStream_t st = (hipStream_t)stream;
     if (phases & 1) {
         WgT43 t = {};
-        t.x = xin; t.ldx = ldx; t.dy = dy; t.lddy = lddy; t.V = V; t.dM = dM;
+        t.x = xin; t.ldx = ldx; t.dy = dy; t.lddy = lddy; t.V = ws; t.dM = dM;
         t.nimg = nimg; t.H = H; t.W = W; t.Cin = Cin; t.Cout = Cout; t.TW = W / 4; t.TPI = (H / 4) * (W / 4); t.T = g.T;
-        const int cmax = Cin > Cout ? Cin : Cout;
-        hipLaunchKernelGGL(wino43_wgrad_transform_kernel, dim3((unsigned)(g.T / 4), (unsigned)((cmax + 255) / 256), 2), dim3(64, 4), 0, st, t);
+        t.z0 = Vgiven ? 1 : 0;
+        const int cmax = Vgiven ? Cout : (Cin > Cout ? Cin : Cout);
+        hipLaunchKernelGGL(wino43_wgrad_transform_kernel, dim3((unsigned)(g.T / 4), (unsigned)((cmax + 255) / 256), Vgiven ? 1 : 2), dim3(64, 4), 0, st, t);
         VD_LAUNCH_CHECK("wino43_wgrad_transform_kernel");
     }
     if (phases & 2) {
@@ -1064,3 +1192,97 @@ extern "C" int vd_conv3x3_wgrad_wino43_phase(const float* xin, int64_t ldx, cons
 
 /* split-K slabs per xi plane of the calling thread's last vd_conv3x3_wgrad_wino43 launch (0: none yet) -- test / profiling aid */
 extern "C" int vd_wino43_wgrad_last_kernel(void) { return g_last43w; }
+
+/* the same weight gradient with the V image of the input GIVEN (vd_conv3x3_wino43_fwd_planes wrote it during the forward pass): only dY is
+ * transformed; bitwise the result of vd_conv3x3_wgrad_wino43 on the input V was made from.  phase: 7 = all, or 1 / 2 / 4 as above. */
+extern "C" int vd_conv3x3_wgrad_wino43_v(const float* V, const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cin,
+                                         int32_t Cout, float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate,
+                                         float* ws, size_t ws_bytes, int32_t phase, void* stream) {
+    VD_REQUIRE(V, "vd_conv3x3_wgrad_wino43_v: null V");
+    VD_REQUIRE(phase == 7 || phase == 1 || phase == 2 || phase == 4, "vd_conv3x3_wgrad_wino43_v: phase must be 7, 1, 2 or 4");
+    return wgrad43_impl(nullptr, Cin, dy, lddy, nimg, H, W, Cin, Cout, dw_oihw, dbias, Cin_w, Cout_w, accumulate, ws, ws_bytes, stream, phase, V);
+}
+
+/* ---- FORWARD through planes: y = conv3x3(x, w) + bias (+ res) as V transform -> 36 plane GEMMs on the split-operand tile engine -> output
+ * transform, leaving V = the weight gradient's input image ([T/16][36][16][Cin], vd_conv3x3_wino43_v_floats floats) behind.
+ * Geometries of the fused forward (32x32, 64-wide with H % 16 == 0, 16x16 images; any image count), Cin, Cout multiples of 4, rows
+ * 16-byte aligned.  stats_part as vd_conv3x3_wino43_fwd: [nimg][chunks][2][Cout], vd_conv3x3_wino43_fwd_chunk_rows pixels per chunk. */
+extern "C" int vd_conv3x3_wino43_fwd_planes_supported(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int64_t ldx, int64_t ldy,
+                                                      int64_t ldres) {
+    if (nimg <= 0 || Cin <= 0 || Cout <= 0 || Cin % 4 || Cout % 4 || ldx % 4 || ldy % 4 || ldres % 4) return 0;
+    if (!((W == 32 && H == 32) || (W == 64 && H % 16 == 0 && H >= 16) || (W == 16 && H == 16))) return 0;
+    const long long T = (long long)nimg * (H / 4) * (W / 4);
+    if (T >= (1LL << 22) || 36LL * 16 * Cin * 16 + 16LL * Cin + 256 >= 0x70000000LL / 4) return 0;      // (row tiles of the GEMM, its block pitch)
+    if (128LL * Cin + 128 >= 0x70000000LL / 4 || 128LL * Cout + 128 >= 0x70000000LL / 4) return 0;
+    return 1;
+}
+
+extern "C" size_t vd_conv3x3_wino43_v_floats(int32_t nimg, int32_t H, int32_t W, int32_t Cin) {
+    return (size_t)36 * ((size_t)nimg * (H / 4) * (W / 4)) * Cin;
+}
+
+extern "C" size_t vd_conv3x3_wino43_fwd_planes_ws_bytes(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout) {
+    const size_t T = (size_t)nimg * (H / 4) * (W / 4);
+    return ((size_t)36 * Cout * Cin + (size_t)36 * T * Cout) * sizeof(float);
+}
+
+/* occupancy and measurement rule: 1 where the forward through planes beats the fused F(4x4,3x3) forward kernel.
+ * training: V stays on the tape and the weight gradient skips its input transform, so the pair (forward, weight gradient) decides;
+ * inference: the forward alone decides (no geometry measured clearly faster: 0).  The plane GEMMs need enough 128-row tiles to fill
+ * the chip in several rounds: a floor of 8192 tiles (32x32 images at batch 128), Cout a multiple of 256 (the 128 x 256 tile), from the
+ * same-box measurement of profiles/r08_conv_planes_geometries.txt. */
+extern "C" int vd_conv3x3_fwd_planes_preferred(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t training) {
+    if (!vd_conv3x3_wino43_fwd_planes_supported(nimg, H, W, Cin, Cout, Cin, Cout, Cout)) return 0;
+    const long long T = (long long)nimg * (H / 4) * (W / 4);
+    // (A/B switches, read once: VD_PLANES_MIN_TILES = the floor, VD_PLANES_INFERENCE = 1: inference forwards above the floor too)
+    static const long long floor_t = getenv("VD_PLANES_MIN_TILES") ? atoll(getenv("VD_PLANES_MIN_TILES")) : VD_PLANES_MIN_TILES;
+    static const int inference = getenv("VD_PLANES_INFERENCE") ? atoi(getenv("VD_PLANES_INFERENCE")) : VD_PLANES_INFERENCE;
+    if (T < floor_t || Cout % 256 || Cin % 16) return 0;
+    return training ? VD_PLANES_TRAINING : (inference != 0);
+}
+
+extern "C" int vd_conv3x3_wino43_fwd_planes(const float* xin, int64_t ldx, const float* w_oihw, const float* bias, const float* res,
+                                            int64_t ldres, float* y, int64_t ldy, int32_t nimg, int32_t H, int32_t W, int32_t Cin,
+                                            int32_t Cout, float* stats_part, float* V, float* ws, size_t ws_bytes, int32_t phase, void* stream) {
+    VD_REQUIRE(xin && w_oihw && y && V && ws, "vd_conv3x3_wino43_fwd_planes: null operand");
+    VD_REQUIRE(vd_conv3x3_wino43_fwd_planes_supported(nimg, H, W, Cin, Cout, ldx, ldy, res ? ldres : 0),
+               "vd_conv3x3_wino43_fwd_planes: unsupported geometry nimg=%d H=%d W=%d Cin=%d Cout=%d", nimg, H, W, Cin, Cout);
+    VD_REQUIRE(vd_aligned16(xin) && vd_aligned16(y) && vd_aligned16(V) && vd_aligned16(ws) && (!res || vd_aligned16(res)) &&
+               (!bias || vd_aligned16(bias)), "vd_conv3x3_wino43_fwd_planes: operands must be 16-byte aligned");
+    VD_REQUIRE(ws_bytes >= vd_conv3x3_wino43_fwd_planes_ws_bytes(nimg, H, W, Cin, Cout), "vd_conv3x3_wino43_fwd_planes: workspace too small");
+    VD_REQUIRE(phase == 7 || phase == 1 || phase == 2 || phase == 4, "vd_conv3x3_wino43_fwd_planes: phase must be 7, 1, 2 or 4");
+    const int TPI = (H / 4) * (W / 4), T = nimg * TPI;
+    float* Up = ws;
+    float* Mb = ws + (size_t)36 * Cout * Cin;
+    hipStream_t st = (hipStream_t)stream;
+    if (phase & 1) {
+        const long long plane = (long long)Cout * Cin;
+        hipLaunchKernelGGL(wino43_pack_planes_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, w_oihw, Up, Cout, Cin);
+        VD_LAUNCH_CHECK("wino43_pack_planes_kernel");
+        WgT43 t = {};
+        t.x = xin; t.ldx = ldx; t.V = V;
+        t.nimg = nimg; t.H = H; t.W = W; t.Cin = Cin; t.Cout = Cout; t.TW = W / 4; t.TPI = TPI; t.T = T;
+        t.z0 = 0;
+        hipLaunchKernelGGL(wino43_wgrad_transform_kernel, dim3((unsigned)(T / 4), (unsigned)((Cin + 255) / 256), 1), dim3(64, 4), 0, st, t);
+        VD_LAUNCH_CHECK("wino43_wgrad_transform_kernel(V)");
+    }
+    if (phase & 2) {
+        vd_gemm_desc d = {};
+        d.A = V; d.B = Up; d.C = Mb;
+        d.M = T; d.N = Cout; d.K = Cin; d.a_kind = VD_ROW; d.b_kind = VD_ROW;
+        d.lda = Cin; d.ldb = Cin; d.ldc = Cout;
+        d.batch = 36; d.nh = 1; d.alpha = 1.f;
+        d.sAb = 16LL * Cin; d.sBb = (long long)Cout * Cin; d.sCb = (long long)T * Cout;
+        const int rc = vd_gemm_rowblk(&d, 36LL * 16 * Cin, stream);
+        if (rc) return rc;
+    }
+    if (phase & 4) {
+        Out43 o = {};
+        o.M = Mb; o.plane = (long long)T * Cout; o.bias = bias; o.res = res; o.ldr = ldres; o.y = y; o.ldy = ldy; o.stats = stats_part;
+        o.H = H; o.W = W; o.Cout = Cout; o.TW = W / 4; o.TPI = TPI; o.T = T;
+        o.CT = vd_conv3x3_wino43_fwd_chunk_rows(H, W) / 16;
+        hipLaunchKernelGGL(wino43_out_transform_kernel, dim3((unsigned)(T / o.CT), (unsigned)((Cout + 63) / 64)), dim3(16, 16), 0, st, o);
+        VD_LAUNCH_CHECK("wino43_out_transform_kernel");
+    }
+    return 0;
+}

@@ -73,6 +73,13 @@ _SIGNATURES = {
     "vd_conv3x3_wgrad_wino43_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
     "vd_conv3x3_wgrad_wino43": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "vd_wino43_wgrad_last_kernel": (C.c_int, []),
+    "vd_conv3x3_wino43_fwd_planes_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64]),
+    "vd_conv3x3_wino43_v_floats": (_sz, [_i32, _i32, _i32, _i32]),
+    "vd_conv3x3_wino43_fwd_planes_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    "vd_conv3x3_fwd_planes_preferred": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
+    "vd_conv3x3_wino43_fwd_planes": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz,
+                                               _i32, _vp]),
+    "vd_conv3x3_wgrad_wino43_v": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "vd_conv3x3_wgrad_wino43_phase": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
     "vd_gn_stats_from_partials": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
     "vd_gn_coef_from_partials": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
@@ -491,6 +498,54 @@ def conv3x3_wino43_fwd(x, ldx, U43f, bias, y, ldy, nimg, H, W, Cin, Cout, res=No
     _note_bytes(name, 4.0 * (nimg * H * W * (Cin + Cout + (Cout if res is not None else 0)) + 36 * Cout * Cin))
 
 
+# forward 3x3 convolutions through PLANES (csrc/wino43.hip: V transform -> 36 plane GEMMs on the split-operand tile engine -> output
+# transform) where vd_conv3x3_fwd_planes_preferred says they beat the fused kernel; a training forward keeps V on the tape and the weight
+# gradient skips its input transform.  CONV_PLANES (VD_CONV_PLANES): "0" never, "1" by that rule, "2" wherever supported (tests, A/B runs)
+CONV_PLANES = os.environ.get("VD_CONV_PLANES", "1")
+
+
+def conv3x3_fwd_planes_preferred(nimg, H, W, Cin, Cout, training):
+    return bool(lib().vd_conv3x3_fwd_planes_preferred(nimg, H, W, Cin, Cout, int(bool(training))))
+
+
+def conv_planes_supported(nimg, H, W, Cin, Cout, ldx, ldy, ldres=0, training=False):
+    """does the forward convolution of this call go through planes?  A training forward (``training``: the tape keeps V in place of the
+    input) also needs the F(4x4,3x3) weight gradient, the only reader of V, to serve the geometry."""
+    if CONV_PLANES == "0" or not (WINO and WINO43_FWD):
+        return False
+    if not lib().vd_conv3x3_wino43_fwd_planes_supported(nimg, H, W, Cin, Cout, ldx, ldy, ldres):
+        return False
+    if training and not wgrad43_supported(nimg, H, W, Cin, Cout, Cin, Cout):
+        return False
+    return CONV_PLANES == "2" or conv3x3_fwd_planes_preferred(nimg, H, W, Cin, Cout, training)
+
+
+def conv3x3_wino43_fwd_planes(x, ldx, w, bias, y, ldy, nimg, H, W, Cin, Cout, res=None, ldres=0, stats_part=None, v=None):
+    """y = conv3x3(x, w) + bias (+ res) through planes (vd_conv3x3_wino43_fwd_planes); ``w``: the raw [Cout][Cin][3][3] kernel.  ``v``: the
+    tensor that receives V (vd_conv3x3_wino43_v_floats floats; a training forward keeps it for the weight gradient) -- None: scratch."""
+    nv = lib().vd_conv3x3_wino43_v_floats(nimg, H, W, Cin)
+    if v is None:
+        v = workspace(nv * 4, x.device, "planes_v")
+    assert v.numel() >= nv and w.is_contiguous() and tuple(w.shape) == (Cout, Cin, 3, 3)
+    ws = workspace(lib().vd_conv3x3_wino43_fwd_planes_ws_bytes(nimg, H, W, Cin, Cout), x.device, "planes")
+    args = (ptr(x), ldx, ptr(w), ptr(bias), ptr(res), ldres, ptr(y), ldy, nimg, H, W, Cin, Cout, ptr(stats_part), ptr(v), ws.data_ptr(),
+            ws.numel() * 4)
+    phase = lambda ph: _check(lib().vd_conv3x3_wino43_fwd_planes(*args, ph, stream()), "vd_conv3x3_wino43_fwd_planes")
+    if PROFILE is None:
+        phase(7)
+        return
+    T = nimg * (H // 4) * (W // 4)
+    with _TimedBytes("wino43_wgrad_transform_kernel", 4.0 * nimg * H * W * Cin * (1 + 2.25)):
+        phase(1)
+    # the 36 planes as ONE batched launch of the tile engine, recorded under that instantiation's name with the work it EXECUTES (a quarter
+    # of the direct convolution's 2*M*N*K: the name carries no tag a reader could scale by)
+    with _TimedTile("gemm_dma_kernel<{tile}, 0, 0, false, {kt}>", 2.0 * 36 * T * Cout * Cin):
+        phase(2)
+    _note_bytes(PROFILE[-1][0], 4.0 * 36.0 * (T * (Cin + Cout) + Cout * Cin))
+    with _TimedBytes("wino43_out_transform_kernel", 4.0 * (36.0 * T * Cout + nimg * H * W * Cout * (2 if res is not None else 1))):
+        phase(4)
+
+
 def conv3x3_dgrad_wino43(dy, lddy, U43, dx, lddx, nimg, H, W, Cin, Cout):
     """dx = input gradient of the Cin -> Cout 3x3 convolution (Winograd F(4x4,3x3), see vd_conv3x3_dgrad_wino43); `flops` recorded =
     the direct convolution's (algorithmic) count, of which the matrix cores execute 1/4"""
@@ -550,29 +605,45 @@ def wgrad43_supported(nimg, H, W, Cin, Cout, ldx, lddy):
             and bool(lib().vd_conv3x3_wgrad_wino43_supported(nimg, H, W, Cin, Cout, ldx, lddy)))
 
 
-def conv3x3_wgrad_wino43(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None):
-    """F(4x4,3x3) weight gradient, unfused (vd_conv3x3_wgrad_wino43): transforms -> 36 grouped GEMMs -> finish"""
+def conv3x3_wgrad_wino43(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None, v=None):
+    """F(4x4,3x3) weight gradient, unfused (vd_conv3x3_wgrad_wino43): transforms -> 36 grouped GEMMs -> finish.  ``v``: the V image of x
+    that conv3x3_wino43_fwd_planes left behind -- the transform pass then runs its dy half alone (x is not read and may be None)"""
     nb = lib().vd_conv3x3_wgrad_wino43_ws_bytes(nimg, H, W, Cin, Cout)
-    ws = workspace(nb, x.device, "wgrad43")
-    args = _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws)
+    ws = workspace(nb, dy.device, "wgrad43")
+    if v is not None:
+        assert v.numel() == lib().vd_conv3x3_wino43_v_floats(nimg, H, W, Cin)
+        vargs = (ptr(v), ptr(dy), lddy, nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(),
+                 ws.numel() * 4)
+        phase = lambda ph: _check(lib().vd_conv3x3_wgrad_wino43_v(*vargs, ph, stream()), "vd_conv3x3_wgrad_wino43_v")
+    else:
+        args = _wgrad_args(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, dbias, Cin_w, Cout_w, accumulate, ws)
+        phase = lambda ph: _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, ph, stream()), "vd_conv3x3_wgrad_wino43_phase")
     if PROFILE is None:
-        _check(lib().vd_conv3x3_wgrad_wino43(*args, stream()), "vd_conv3x3_wgrad_wino43")
+        if v is not None:
+            phase(7)
+        else:
+            _check(lib().vd_conv3x3_wgrad_wino43(*args, stream()), "vd_conv3x3_wgrad_wino43")
         return
-    with _TimedBytes("wino43_wgrad_transform_kernel", 4.0 * nimg * H * W * (Cin + Cout) * (1 + 2.25)):
-        _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, 1, stream()), "vd_conv3x3_wgrad_wino43_phase")
+    with _TimedBytes("wino43_wgrad_transform_kernel", 4.0 * nimg * H * W * ((Cin if v is None else 0) + Cout) * (1 + 2.25)):
+        phase(1)
     # the 36 planes run as ONE grouped launch of the tile engine: recorded under that instantiation's rocprof name (from vd_gemm_last_tile),
     # tagged so that the bench knows its recorded work is the direct convolution's 2*M*N*K, of which the planes execute 1/4
     with _TimedTile("gemm_dma_kernel<{tile}, 1, 1, true, {kt}, true> " + W43_WGRAD_TAG, 2.0 * nimg * H * W * Cout * 9 * Cin) as t:
-        _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, 2, stream()), "vd_conv3x3_wgrad_wino43_phase")
+        phase(2)
     # (its operands are the transformed images: 36 planes of [tiles][Cin] and [tiles][Cout], read once, + the 36 x Cout x Cin result)
     _note_bytes(PROFILE[-1][0], 4.0 * (36.0 * nimg * (H // 4) * (W // 4) * (Cin + Cout) + 36.0 * Cout * Cin))
     with _TimedName("wino43_wgrad_finish_kernel", 0.0):
-        _check(lib().vd_conv3x3_wgrad_wino43_phase(*args, 4, stream()), "vd_conv3x3_wgrad_wino43_phase")
+        phase(4)
 
 
-def conv3x3_wgrad(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None, direct=False):
+def conv3x3_wgrad(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None, direct=False, v=None):
     """weight (and bias) gradient of the 3x3 convolution: Winograd-domain kernels wherever the geometry is served -- F(4x4,3x3)
-    unfused for the large layers, F(2x2,3x3) fused otherwise (VD_WINO=0 or direct=True: the implicit GEMM over pixels)"""
+    unfused for the large layers, F(2x2,3x3) fused otherwise (VD_WINO=0 or direct=True: the implicit GEMM over pixels).  ``v``: the forward
+    through planes kept V in place of x (conv_planes_supported(training=True) promised the F(4x4,3x3) weight gradient for this geometry)"""
+    if v is not None:
+        if direct or not wgrad43_supported(nimg, H, W, Cin, Cout, Cin, lddy):
+            raise HipError("conv3x3_wgrad: a V image was kept for a geometry the F(4x4,3x3) weight gradient does not serve")
+        return conv3x3_wgrad_wino43(None, Cin, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate, dbias, v=v)
     if not direct and wgrad43_supported(nimg, H, W, Cin, Cout, ldx, lddy):
         return conv3x3_wgrad_wino43(x, ldx, dy, lddy, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate, dbias)
     if WINO and not direct and lib().vd_conv3x3_wgrad_wino_supported(nimg, H, W, Cin, Cout, ldx, lddy):

@@ -336,12 +336,14 @@ class UNetEngine:
     # wherever a gradient is declared complete: at every `progress` call when a reducer listens, else once at the end of backward.
     # Results are bitwise those of the one-stream order (every gradient tensor has one writer); per-kernel profiling (H.PROFILE) runs
     # on one stream so that a kernel's events bracket that kernel alone.
-    def _cwgrad(self, x, ldx, dy, lddy, *args, **kw):
+    def _cwgrad(self, x, ldx, dy, lddy, *args, v=None, **kw):
+        if v is not None:                      # the forward went through planes and kept V in place of x (_conv): the transform of x is skipped
+            kw["v"] = v
         side = self._side
         if side is None:
             return H.conv3x3_wgrad(x, ldx, dy, lddy, *args, **kw)
         side.wait_stream(torch.cuda.current_stream())
-        x.record_stream(side)
+        (x if v is None else v).record_stream(side)
         dy.record_stream(side)
         with torch.cuda.stream(side):
             H.conv3x3_wgrad(x, ldx, dy, lddy, *args, **kw)
@@ -457,11 +459,21 @@ class UNetEngine:
         """the images the packs in flight hold for kernel ``w``"""
         return self._packs.layers.get(id(w), _NO_PACK) if self._packs is not None else _NO_PACK
 
-    def _conv(self, x, ldx, w, bias, y, ldy, B, Hh, Ww, Cin, Cout, dgrad=False, res=None, ldres=0, stats_part=None):
+    def _conv(self, x, ldx, w, bias, y, ldy, B, Hh, Ww, Cin, Cout, dgrad=False, res=None, ldres=0, stats_part=None, keep_v=None):
         """3x3 convolution with kernel ``w`` (forward) or its input gradient (``dgrad``: x = dy, Cin/Cout are the GEMM's):
         Winograd F(4x4,3x3) / F(2x2,3x3) wherever the geometry is served, the direct implicit GEMM otherwise.  Returns the pixel rows per
-        chunk of the GroupNorm partial sums it left in ``stats_part`` (the consuming norm needs the chunk count: _parts)."""
+        chunk of the GroupNorm partial sums it left in ``stats_part`` (the consuming norm needs the chunk count: _parts).
+        ``keep_v`` (a list, training forwards with a tape): a forward that goes through planes appends the V image it made -- the tape
+        keeps it in place of ``x``, which only the weight gradient would read."""
         pk, p = self._packs, self._layer(w)
+        if not dgrad and p is not _NO_PACK and pk.wino and H.conv_planes_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0,
+                                                                                 training=keep_v is not None):
+            v = None
+            if keep_v is not None:
+                v = torch.empty(36 * B * (Hh // 4) * (Ww // 4) * Cin, dtype=torch.float32, device=x.device)
+                keep_v.append(v)
+            H.conv3x3_wino43_fwd_planes(x, ldx, w, bias, y, ldy, B, Hh, Ww, Cin, Cout, res=res, ldres=ldres, stats_part=stats_part, v=v)
+            return H.wino43_fwd_chunk_rows(Hh, Ww)
         if not dgrad and p.u43f is not None and H.wino43_fwd_supported(B, Hh, Ww, Cin, Cout, ldx, ldy, ldres if res is not None else 0):
             # forward pass through F(4x4,3x3) (csrc/wino43.hip, dyadic interpolation points); its GroupNorm partials come one chunk per
             # (image, work item)
@@ -643,7 +655,8 @@ class UNetEngine:
         coef1 = self._norm(x, x_parts, mod.norm1, None, 1, 0.0, 0, rs, a1, B, Hh, Ww, Cin)
         h1 = self._new(x, B, Ho, Wo, Cout)
         ph = self._part(x, B, Ho * Wo, Cout)
-        rows = self._conv(a1, Cin, mod.conv1.weight, mod.conv1.bias, h1, Cout, B, Ho, Wo, Cin, Cout, stats_part=ph)
+        v1, v2 = ([], []) if tape is not None else (None, None)
+        rows = self._conv(a1, Cin, mod.conv1.weight, mod.conv1.bias, h1, Cout, B, Ho, Wo, Cin, Cout, stats_part=ph, keep_v=v1)
         h1_parts = self._parts(ph, Cout, Ho * Wo, rows)
         c2, fi = blk.film
         film = films[c2][fi]                              # [B][2*Cout], contiguous slice of the group's batched GEMM output
@@ -663,11 +676,12 @@ class UNetEngine:
             sk = xs
         pd = self._part(x, B, Ho * Wo, Cout)
         rows = self._conv(a2, Cout, mod.conv2.weight, mod.conv2.bias, dest, _ld(dest), B, Ho, Wo, Cout, Cout, res=sk,
-                          ldres=_ld(sk), stats_part=pd)
+                          ldres=_ld(sk), stats_part=pd, keep_v=v2)
         out_parts = self._parts(pd, Cout, Ho * Wo, rows)
         if tape is not None:
-            tape[prefix] = dict(x=x, coef1=coef1, a1=a1, h1=h1, coef2=coef2, a2=a2, film=film, xs=xs if has_skip else None,
-                                seed=seed, p=p_drop)
+            # (a convolution that went through planes left its V image: the tape keeps that in place of the activation)
+            tape[prefix] = dict(x=x, coef1=coef1, a1=None if v1 else a1, h1=h1, coef2=coef2, a2=None if v2 else a2, film=film,
+                                xs=xs if has_skip else None, seed=seed, p=p_drop, v1=v1[0] if v1 else None, v2=v2[0] if v2 else None)
         return out_parts
 
     def _res_bwd(self, blk, ctx, dy, dx, dx_accumulate, ta, dfilms, G):
@@ -678,7 +692,7 @@ class UNetEngine:
         _, Ho, Wo, Cout, lddy = _chk(dy)
         rs = blk.rs
         # conv2
-        self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"])
+        self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"], v=ctx["v2"])
         da2 = self._new(x, B, Ho, Wo, Cout)
         self._conv(dy, lddy, mod.conv2.weight, None, da2, Cout, B, Ho, Wo, Cout, Cout, dgrad=True)
         # norm2 + FiLM + SiLU + dropout
@@ -690,7 +704,7 @@ class UNetEngine:
                        pgb_keep=self._pgb(B, Cout, g["norm2.weight"], g["norm2.bias"]))
         del da2
         # conv1
-        self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"])
+        self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"], v=ctx["v1"])
         da1 = self._new(x, B, Ho, Wo, Cin)
         self._conv(dh1, Cout, mod.conv1.weight, None, da1, Cin, B, Ho, Wo, Cout, Cin, dgrad=True)
         del dh1
