@@ -1,10 +1,9 @@
 """Host side of consistency distillation / training and multistep consistency sampling (v_diffusion/consistency.py): the per-sample
 coefficient table, the sampler's rows and the index schedule against the float64 restatement of tests/consist_ref.py and against
-identities; the order of the objective itself on Gaussian data, where everything is known in closed form; the C ABI declarations; and
+identities; the order of the objective itself on Gaussian data, where everything is known in closed form; the public names; and
 every refusal that needs no GPU.  No kernel is launched here."""
 import math
 import os
-import re
 import sys
 
 import pytest
@@ -13,11 +12,9 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import consist_ref as R                                           # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = (1, 2, 4, 1024)
 SCHEDULES = ("cosine", "linear")
 REWEIGHTS = ("constant", "snr", "snr_trunc", "snr_1plus")
-NEW_EXPORTS = ("vd_consist_mid", "vd_consist_pair", "vd_consist_loss_fwd", "vd_consist_loss_bwd", "vd_ema_track_batched")
 NEW_NAMES = ("ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule")
 
 
@@ -245,15 +242,9 @@ def test_training_residual_is_unbiased_for_the_distillation_residual():
 
 
 def test_entry_points_are_declared_and_bound():
+    """(declarations and ctypes signatures of the entry points: tests/test_host_cpu.py pins the whole C ABI)"""
     import v_diffusion as vd
     from v_diffusion import _hip
-    hdr = open(os.path.join(ROOT, "include", "vdiff_hip.h")).read()
-    for name in NEW_EXPORTS:
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), f"{name} not declared"
-        assert name in _hip.EXPORTS
-        res, args = _hip._SIGNATURES[name]
-        decl = re.search(name + r"\s*\((.*?)\)\s*;", hdr, re.S).group(1)
-        assert len(args) == len(decl.split(",")), name                               # one ctypes argument per C parameter
     for fn in ("consist_mid", "consist_pair", "consist_loss_fwd", "consist_loss_bwd", "ema_track_batched"):
         assert callable(getattr(_hip, fn))
     for name in NEW_NAMES:

@@ -1,8 +1,7 @@
 """Host side of progressive distillation (v_diffusion/distill.py): the per-sample coefficient table against the float64 restatement of
-tests/distill_ref.py, the handling of a rescaling schedule, next_stage's refusal of odd step counts, and the C ABI declarations.
+tests/distill_ref.py, the handling of a rescaling schedule, next_stage's refusal of odd step counts, and the launch wrappers' presence.
 No kernel is launched here."""
 import os
-import re
 import sys
 
 import pytest
@@ -11,7 +10,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import distill_ref as R                                           # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STEPS = (1, 2, 4, 1024)
 SCHEDULES = ("cosine", "linear")
 
@@ -156,12 +154,6 @@ def test_next_stage_halves_and_refuses_odd_step_counts():
 
 
 def test_entry_points_are_declared_and_bound():
+    """(their declarations and ctypes signatures: tests/test_host_cpu.py pins the whole C ABI)"""
     from v_diffusion import _hip
-    hdr = open(os.path.join(ROOT, "include", "vdiff_hip.h")).read()
-    for name in ("vd_distill_mid", "vd_distill_loss_fwd", "vd_distill_loss_bwd"):
-        assert re.search(r"\bint\s+" + name + r"\s*\(", hdr), f"{name} not declared"
-        assert name in _hip.EXPORTS
-        res, args = _hip._SIGNATURES[name]
-        decl = re.search(name + r"\s*\((.*?)\)\s*;", hdr, re.S).group(1)
-        assert len(args) == len(decl.split(",")), name                               # one ctypes argument per C parameter
     assert callable(_hip.distill_mid) and callable(_hip.distill_loss_fwd) and callable(_hip.distill_loss_bwd)

@@ -1,6 +1,11 @@
 """CPU-side checks of the host package: C ABI export table, state_dict contract, engine plan, host schedule math.
-No compute kernels are launched here (there is no GPU in this tier)."""
+No compute kernels are launched here (there is no GPU in this tier).
+
+    python tests/test_host_cpu.py --record      rewrites tests/golden/c_abi.json from include/vdiff_hip.h -- only for a change that is
+                                                MEANT to add an entry point or to alter one
+"""
 import ctypes
+import json
 import math
 import os
 import re
@@ -33,6 +38,83 @@ def test_c_abi_exports_every_declared_symbol():
         assert hasattr(lib, name), f"{name} not exported"
     lib.vd_version.restype = ctypes.c_int
     assert lib.vd_version() == 100
+
+
+C_ABI = os.path.join(ROOT, "tests", "golden", "c_abi.json")
+
+
+def _parsed_abi():
+    """what v_diffusion._hip reads from include/vdiff_hip.h, in the form of the fixture: {"product" | "probe": [[name, return type,
+    [parameter, ...]], ...]} in header order, every type and parameter as whitespace-normalised C text"""
+    from v_diffusion import _hip
+    with open(_hip.HEADER_PATH) as f:
+        tables = _hip._parse_header(f.read())
+    return {part: [[name, ret, params] for name, (ret, params) in t.items()] for part, t in zip(("product", "probe"), tables)}
+
+
+def test_the_whole_c_abi_is_as_recorded():
+    """every entry point of the header -- name, position, return type, and each parameter's type AND name, so that two same-typed
+    parameters changing places moves it too -- against tests/golden/c_abi.json.  The one place that pins a declaration: the feature
+    tests check their wrappers and public names only, so an entry that is added or altered on purpose is re-recorded here (--record)."""
+    with open(C_ABI) as f:
+        want = json.load(f)
+    got = _parsed_abi()
+    assert sorted(want) == ["probe", "product"]
+    for part in ("product", "probe"):
+        assert [e[0] for e in got[part]] == [e[0] for e in want[part]], f"{part} entry points: names or order moved"
+        for g, w in zip(got[part], want[part]):
+            assert g == w, f"{w[0]} moved: recorded {w[1]} ({', '.join(w[2])}), the header now says {g[1]} ({', '.join(g[2])})"
+    counts = {e[0]: len(e[2]) for e in want["product"]}
+    assert (counts["vd_sample_step"], counts["vd_solver_step"], counts["vd_unipc_step"], counts["vd_version"]) == (15, 14, 17, 0)
+
+
+def test_every_entry_binds_by_the_type_rule():
+    """the ctypes signature of every recorded entry is its C text mapped by THIS table: by-value types to the ctypes type of that name
+    and width, every pointer to c_void_p (host float arrays included: `k` of the sampler steps, `frac` of vd_slerp_rows), the GEMM
+    descriptor to its mirror, `const char*` returned as c_char_p.  The table is also the complete list of types the header uses."""
+    import ctypes as C
+    from v_diffusion import _hip
+    pointers = ("const float*", "float*", "const double*", "double*", "const int32_t*", "int32_t*", "const int64_t*", "const uint8_t*",
+                "uint8_t*", "const uint16_t*", "unsigned*", "unsigned long long*", "const float* const*", "float* const*", "void*")
+    params = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+              "float": C.c_float, "double": C.c_double, **{p: C.c_void_p for p in pointers},
+              "const vd_gemm_desc*": C.POINTER(_hip.GemmDesc)}
+    returns = {"int": C.c_int, "size_t": C.c_size_t, "const char*": C.c_char_p}
+    with open(C_ABI) as f:
+        want = json.load(f)
+    seen = set()
+    for part, table in (("product", _hip._SIGNATURES), ("probe", _hip.PROBE_EXPORTS)):
+        assert list(table) == [e[0] for e in want[part]]
+        for name, ret, decl in want[part]:
+            res, args = table[name]
+            assert res is returns[ret], f"{name}: returns {ret}, bound as {res}"
+            assert len(args) == len(decl), f"{name}: {len(decl)} parameters, {len(args)} ctypes arguments"
+            for p, a in zip(decl, args):
+                ctype = p.rpartition(" ")[0]
+                seen.add(ctype)
+                assert a is params[ctype], f"{name}: parameter `{p}` bound as {a}"
+    assert seen == set(params)
+    assert _hip.EXPORTS == tuple(_hip._SIGNATURES) and _hip._SIGNATURES["vd_gemm"][1][0] is C.POINTER(_hip.GemmDesc)
+
+
+def test_the_header_parser_refuses_what_it_cannot_bind(monkeypatch):
+    from v_diffusion import _hip
+    text = ("int vd_a(int32_t n,\n   float*  out /* or NULL */, void* stream);\n#ifdef VD_PROBES\n/* int vd_not(void); */\n"
+            "int vd_p(unsigned* buf);\n#endif\nsize_t vd_b(void);\n")
+    product, probe = _hip._parse_header(text)
+    assert list(product.items()) == [("vd_a", ("int", ["int32_t n", "float* out", "void* stream"])), ("vd_b", ("size_t", []))]
+    assert probe == {"vd_p": ("int", ["unsigned* buf"])}                     # inside the #ifdef: the probe table only
+    assert _hip._ctypes_of("vd_a", *product["vd_a"]) == (ctypes.c_int, [ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p])
+    bad, _ = _hip._parse_header("int vd_bad(int32_t n, long count, void* stream);\nlong vd_ret(void);\n")
+    with pytest.raises(RuntimeError, match="vd_bad.*long count"):            # an unknown by-value type: no default, the entry is named
+        _hip._ctypes_of("vd_bad", *bad["vd_bad"])
+    with pytest.raises(RuntimeError, match="vd_ret.*long"):
+        _hip._ctypes_of("vd_ret", *bad["vd_ret"])
+    with pytest.raises(RuntimeError, match="declaration"):                   # a declaration the pattern cannot read is not dropped silently
+        _hip._parse_header("int vd_ok(void);\nint vd_callback(void (*fn)(int), void* stream);\n")
+    monkeypatch.setattr(_hip, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    with pytest.raises(RuntimeError, match="no_such_header.h not found"):
+        _hip._header_signatures()
 
 
 def test_product_library_has_no_probe_or_experiment_code():
@@ -588,3 +670,13 @@ def test_grad_segments_cover_the_completion_order():
         assert all(names[-1] == b for b, names in segs[:-1])
         assert segs[-1][1][:2] == ["in_conv.weight", "in_conv.bias"]
         assert all(k in segs[-1][1] for k in dict(model.named_parameters()) if k.startswith(("time_embed", "class_embed")) or ".norm" in k)
+
+
+if __name__ == "__main__":
+    assert _sys.argv[1:] == ["--record"], __doc__
+    _sys.path.insert(0, os.path.join(ROOT, "v-diffusion-torch_amd"))
+    abi = _parsed_abi()
+    rows = lambda part: ",\n".join(json.dumps(e, separators=(",", ":")) for e in abi[part])
+    with open(C_ABI, "w") as f:
+        f.write('{\n"product": [\n' + rows("product") + '\n],\n"probe": [\n' + rows("probe") + "\n]\n}\n")
+    print(f"{len(abi['product'])} + {len(abi['probe'])} entry points -> {C_ABI}")

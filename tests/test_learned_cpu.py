@@ -1,9 +1,8 @@
 """Learned variances without a GPU: the CPU restatement (tests/learned_ref.py) against the fixture made from the reference's own
 functions (tests/golden/learned_var.npz, tests/make_golden_learned.py), the host coefficient tables against fp64 closed forms, the
-constructor and refusal rules, and the agreement of the C header, ``EXPORTS`` and ``_SIGNATURES`` for the five new entries."""
+constructor and refusal rules, and the wrappers and definitions of the five new entries."""
 import math
 import os
-import re
 
 import numpy as np
 import pytest
@@ -137,25 +136,11 @@ def test_constructor_and_refusal_rules():
 
 
 def test_header_exports_and_signatures_agree():
-    """every new entry is declared in include/vdiff_hip.h with as many parameters as its ctypes signature has, of matching kinds; the
-    existing entries they sit beside are as they were"""
-    import ctypes as C
+    """every new entry has its launch wrapper and its definition in csrc/diffusion.hip (declarations and ctypes signatures:
+    tests/test_host_cpu.py pins the whole C ABI)"""
     from v_diffusion import _hip
-    header = open(os.path.join(ROOT, "include", "vdiff_hip.h")).read()
-    kinds = {C.c_void_p: "ptr", C.c_int32: "int32_t", C.c_float: "float", C.POINTER(C.c_float): "ptr"}
     for name in NEW:
-        assert name in _hip.EXPORTS and callable(getattr(_hip, name[3:]))
-        m = re.search(r"\bint " + name + r"\(([^;]*)\);", header)
-        assert m, f"{name} is not declared in the header"
-        params = [p.strip() for p in m.group(1).replace("\n", " ").split(",")]
-        res, args = _hip._SIGNATURES[name]
-        assert res is C.c_int and len(params) == len(args), name
-        for p, a in zip(params, args):
-            kind = "ptr" if "*" in p else p.split()[0]
-            assert kinds[a] == kind, f"{name}: header parameter {p!r} against ctypes {a}"
-    n = lambda name: len(_hip._SIGNATURES[name][1])
-    assert (n("vd_bpd_terms_lv"), n("vd_bpd_bwd_lv"), n("vd_hybrid_loss_fwd"), n("vd_hybrid_loss_bwd"), n("vd_sample_step_lv")) == (14, 14, 16, 17, 14)
-    assert (n("vd_bpd_terms"), n("vd_bpd_bwd"), n("vd_loss_fwd"), n("vd_loss_bwd"), n("vd_sample_step")) == (14, 13, 13, 14, 15)
+        assert callable(getattr(_hip, name[3:]))
     src = open(os.path.join(ROOT, "v-diffusion-torch_amd", "csrc", "diffusion.hip")).read()
     for name in NEW:
         assert f'extern "C" int {name}(' in src

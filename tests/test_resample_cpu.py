@@ -1,5 +1,5 @@
 """Loss-aware timestep resampling without a GPU: the invariants of the numpy restatement tests/lsm_ref.py (the yardstick of
-test_resample_gpu.py), the constructor's checks, the export and the binding table."""
+test_resample_gpu.py), the constructor's checks and the export."""
 import math
 
 import numpy as np
@@ -82,7 +82,6 @@ def test_bad_rows_are_skipped():
 
 def test_constructor_checks_and_export():
     import v_diffusion as vd
-    from v_diffusion import _hip
     assert "LossSecondMomentResampler" in vd.__all__ and "LossSecondMomentResampler" in vd._HOT and callable(vd.LossSecondMomentResampler)
     for kw in (dict(num_timesteps=0), dict(num_timesteps=65537), dict(num_timesteps=8, history_per_term=0),
                dict(num_timesteps=8, uniform_prob=-0.1), dict(num_timesteps=8, uniform_prob=1.5)):
@@ -90,8 +89,6 @@ def test_constructor_checks_and_export():
             vd.LossSecondMomentResampler(device="cpu", **kw)
     with pytest.raises(RuntimeError, match="must live on an MI355X"):
         vd.LossSecondMomentResampler(8, device="cpu")
-    assert "vd_lsm_draw" in _hip.EXPORTS and "vd_lsm_update" in _hip.EXPORTS
-    assert len(_hip._SIGNATURES["vd_lsm_draw"][1]) == 12 and len(_hip._SIGNATURES["vd_lsm_update"][1]) == 9
 
 
 def test_trainer_refuses_resampling_without_a_grid():

@@ -1,5 +1,5 @@
 """Host side of dynamic thresholding in the DPM-Solver++ sampler: the rank rule against numpy's "higher" quantile, the argument checks,
-the properties of the float64 restatement the GPU tests are held to (tests/threshold_ref.py), and the C ABI rows.  No kernel is
+the properties of the float64 restatement the GPU tests are held to (tests/threshold_ref.py), and the public names.  No kernel is
 launched here."""
 import math
 import os
@@ -12,7 +12,6 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import threshold_ref as T                                         # noqa: E402
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZES = (1, 2, 75, 192, 972, 3072, 12288, 49152)
 QUANTILES = (0.5, 0.9, 0.95, 0.995, 0.999, 1.0)
 
@@ -116,17 +115,9 @@ def test_restated_step_and_chain_agree_with_the_solver_restatement():
 
 
 def test_c_abi_declares_the_two_entries():
-    import ctypes as C
+    """(declarations and ctypes signatures of the entry points: tests/test_host_cpu.py pins the whole C ABI)"""
     import v_diffusion as vd
     from v_diffusion import _hip
-    hdr = open(os.path.join(ROOT, "include", "vdiff_hip.h")).read()
-    assert "int vd_abs_kth_rows(const float* x, int32_t n, int64_t N, int64_t r, float* kth, void* stream);" in hdr
-    assert "int vd_solver_step_dyn(const float* xt, const float* out, float* hist, const float* k, const float* k_dev," in hdr
-    kth, dyn = _hip._SIGNATURES["vd_abs_kth_rows"], _hip._SIGNATURES["vd_solver_step_dyn"]
-    assert "vd_abs_kth_rows" in _hip.EXPORTS and "vd_solver_step_dyn" in _hip.EXPORTS
-    assert kth[0] is C.c_int and len(kth[1]) == 6 and kth[1][2] is C.c_int64 and kth[1][3] is C.c_int64
-    assert dyn[0] is C.c_int and len(dyn[1]) == 16 and dyn[1][7] is C.c_int64 and dyn[1][8] is C.c_float
-    assert len(_hip._SIGNATURES["vd_solver_step"][1]) == 14        # the static entry is as it was
     for name in ("threshold_rank", "dynamic_threshold"):
         assert name in vd.__all__ and callable(getattr(vd, name))
     assert callable(_hip.abs_kth_rows) and callable(_hip.solver_step_dyn)

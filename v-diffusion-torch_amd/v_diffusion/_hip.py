@@ -6,11 +6,13 @@ There is NO fallback: a missing library, a CPU tensor or a non-zero return code 
 """
 import ctypes as C
 import os
+import re
 
 import numpy as np
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vdiff_hip.h")
 LIB_PATH = os.environ.get("VDIFF_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvdiff_hip.so")   # (override: A/B builds)
 
 ROW, COL, IM2COL = 0, 1, 2
@@ -19,7 +21,7 @@ RS_NONE, RS_DOWN, RS_UP = 0, 1, 2
 OUT_TYPES = {"v": 0, "x0": 1, "eps": 2, "both": 3}
 REWEIGHTS = {"constant": 0, "snr": 1, "snr_trunc": 2, "snr_1plus": 3}
 
-_i32, _i64, _f32, _f64, _u64, _vp, _sz = C.c_int32, C.c_int64, C.c_float, C.c_double, C.c_uint64, C.c_void_p, C.c_size_t
+_i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
 
 
 class GemmDesc(C.Structure):
@@ -34,148 +36,56 @@ class GemmDesc(C.Structure):
                 ("colsum", _vp), ("colsum_accumulate", _i32), ("stats", _vp), ("stats_hw", _i32), ("sBias", _i64)]
 
 
-_SIGNATURES = {
-    "vd_version": (C.c_int, []),
-    "vd_last_error": (C.c_char_p, []),
-    "vd_set_reserved_cus": (C.c_int, [_i32]),
-    "vd_reserved_cus": (C.c_int, []),
-    "vd_mfma_calibrate": (C.c_int, [_vp, _vp, _i32, _i32, C.c_uint32, _vp]),
-    "vd_gemm": (C.c_int, [C.POINTER(GemmDesc), _vp]),
-    "vd_gemm_last_tile": (C.c_int, []),
-    "vd_gemm_split_forms": (C.c_int, []),
-    "vd_gemm_plan_tile": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32]),
-    "vd_gemm_grouped_wgrad_ws_bytes": (_sz, [_i32, _i32, _i32, _i32]),
-    "vd_gemm_grouped_wgrad_auto_split": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
-    "vd_gemm_grouped_wgrad": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _i32, _vp, _sz, _vp]),
-    "vd_conv3x3": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
-    "vd_conv3x3_wino_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64]),
-    "vd_conv3x3_wino": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
-    "vd_wino_pack": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
-    "vd_conv3x3_wgrad_wino_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64]),
-    "vd_conv3x3_wgrad_wino_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    "vd_conv3x3_wgrad_wino": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "vd_conv3x3_wgrad_wino_phase": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
-    "vd_wino_last_kernel": (C.c_int, []),
-    "vd_wino_wgrad_last_kernel": (C.c_int, []),
-    "vd_wino_pack_batched": (C.c_int, [_vp, _i32, _i64, _vp]),
-    "vd_conv3x3_dgrad_wino43_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64]),
-    "vd_wino43_u_floats": (_sz, [_i32, _i32]),
-    "vd_conv3x3_dgrad_wino43": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp]),
-    "vd_wino43_last_kernel": (C.c_int, []),
-    "vd_conv3x3_wino43_fwd_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64]),
-    "vd_conv3x3_wino43_preferred": (C.c_int, [_i32, _i32, _i32, _i32]),
-    "vd_wino43_pack_fwd": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
-    "vd_conv3x3_wino43_fwd_chunk_rows": (C.c_int, [_i32, _i32]),
-    "vd_conv3x3_wino43_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
-    "vd_wino43_pack": (C.c_int, [_vp, _i32, _i32, _vp, _vp]),
-    "vd_wino43_pack_batched": (C.c_int, [_vp, _i32, _i64, _vp]),
-    "vd_conv3x3_wgrad_wino43_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64]),
-    "vd_conv3x3_wgrad_wino43_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    "vd_conv3x3_wgrad_wino43": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "vd_wino43_wgrad_last_kernel": (C.c_int, []),
-    "vd_conv3x3_wino43_fwd_planes_supported": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64]),
-    "vd_conv3x3_wino43_v_floats": (_sz, [_i32, _i32, _i32, _i32]),
-    "vd_conv3x3_wino43_fwd_planes_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    "vd_conv3x3_fwd_planes_preferred": (C.c_int, [_i32, _i32, _i32, _i32, _i32, _i32]),
-    "vd_conv3x3_wino43_fwd_planes": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _sz,
-                                               _i32, _vp]),
-    "vd_conv3x3_wgrad_wino43_v": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
-    "vd_conv3x3_wgrad_wino43_phase": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
-    "vd_gn_stats_from_partials": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
-    "vd_gn_coef_from_partials": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
-    "vd_conv3x3_wgrad_ws_bytes": (_sz, [_i32, _i32, _i32, _i32, _i32]),
-    "vd_conv3x3_wgrad": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "vd_conv3x3_wgrad_phase": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _sz, _i32, _vp]),
-    "vd_pack_conv3x3": (C.c_int, [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _vp]),
-    "vd_pack_conv3x3_batched": (C.c_int, [_vp, _i32, _i64, _vp]),
-    "vd_gn_ws_bytes": (_sz, [_i32, _i32, _i32]),
-    "vd_gn_stats": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _sz, _vp]),
-    "vd_gn_apply": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _u64, _i32, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
-    "vd_gn_apply_from_partials": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _i32, _f32, _u64, _i32, _vp, _i64, _i32,
-                                            _i32, _i32, _i32, _i32, _f32, _vp, _vp]),
-    "vd_gn_apply_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _u64, _i32, _vp, _i64, _vp, _i64, _i32,
-                                  _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "vd_gn_bwd_last_kernel": (C.c_int, []),
-    "vd_gn_apply_bwd_keep": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _f32, _u64, _i32, _vp, _i64, _vp, _i64, _i32,
-                                       _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "vd_gn_param_sums_batched": (C.c_int, [_vp, _i32, _i64, _vp]),
-    "vd_colsum_ws_bytes": (_sz, [_i64, _i32]),
-    "vd_colsum": (C.c_int, [_vp, _i64, _i64, _i32, _vp, _i32, _vp, _sz, _vp]),
-    "vd_axpby": (C.c_int, [_vp, _i64, _f32, _vp, _i64, _f32, _i64, _i32, _vp]),
-    "vd_silu": (C.c_int, [_vp, _vp, _i64, _vp]),
-    "vd_silu_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp]),
-    "vd_softmax_rows": (C.c_int, [_vp, _i64, _i32, _vp]),
-    "vd_softmax_rows_bwd": (C.c_int, [_vp, _vp, _i64, _i32, _f32, _vp]),
-    "vd_attn_supported": (C.c_int, [_i32, _i32, _i32]),
-    "vd_attn_fwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _i32, _f32, _vp]),
-    "vd_attn_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, _vp]),
-    "vd_attn_bwd_phase": (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32,
-                                    _i32, _vp]),
-    "vd_nchw_to_nhwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp]),
-    "vd_nhwc_to_nchw": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "vd_images_to_uint8_hwc": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_images_from_uint8_hwc": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "vd_timestep_embedding": (C.c_int, [_vp, _vp, _i32, _i32, _f64, _vp]),
-    "vd_class_embed": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_class_embed_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "vd_multitag_norm": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
-    "vd_im2col3x3": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _vp]),
-    "vd_tap_gather": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "vd_tap_spread": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "vd_thin_wgrad_finish": (C.c_int, [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp, _vp]),
-    "vd_q_sample": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_bpd_terms": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_bpd_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_sample_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_bpd_terms_lv": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_bpd_bwd_lv": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_hybrid_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_hybrid_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_sample_step_lv": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_distill_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_distill_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_distill_loss_bwd": (C.c_int, [_vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_consist_mid": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_consist_pair": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_consist_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_consist_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp]),
-    "vd_ema_track_batched": (C.c_int, [_vp, _i32, _i64, _f64, _vp]),
-    "vd_solver_step": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_unipc_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_abs_kth_rows": (C.c_int, [_vp, _i32, _i64, _i64, _vp, _vp]),
-    "vd_solver_step_dyn": (C.c_int, [_vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i64, _f32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_inpaint_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32,
-                                  _vp]),
-    "vd_forward_jump": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
-    "vd_noise_extract": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(_f32), _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_slerp_rows": (C.c_int, [_vp, _vp, C.POINTER(_f32), _vp, _vp, _vp, _i32, _i64, _vp]),
-    "vd_lsm_draw": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _f64, _vp]),
-    "vd_lsm_update": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
-    "vd_sumsq_ws_bytes": (_sz, [_i64]),
-    "vd_sumsq": (C.c_int, [_vp, _i64, _vp, _vp, _sz, _vp]),
-    "vd_adamw_ema": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64, _i32,
-                               _f32, _f32, _vp]),
-    "vd_adamw_ema_flagged": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _f32, _i64, _i64,
-                                       _vp, _vp, _f64, _f64, _vp]),
-    "vd_rows_sqnorm_f16": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
-    "vd_knn_kth_ws_bytes": (_sz, [_i64, _i64, _i32]),
-    "vd_knn_kth_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
-    "vd_manifold_hits_ws_bytes": (_sz, [_i64]),
-    "vd_manifold_hits_f16": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _sz, _vp]),
-    "vd_fid_shift": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp]),
-    "vd_fid_accum": (C.c_int, [_vp, _i64, _i32, _i64, _vp, _vp, _vp, _vp]),
-    "vd_atb_f64": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _i64, _i64, _vp]),
-    "vd_kid_ws_bytes": (_sz, [_i32, _i32, _i32]),
-    "vd_kid_sums": (C.c_int, [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _i32, _i32, _i32, _f64, _f64, _i32, _vp, _vp, _sz, _vp]),
-    "vd_is_ws_bytes": (_sz, [_i64, _i32, _i32]),
-    "vd_is_scores": (C.c_int, [_vp, _i64, _i32, _i64, _i32, _vp, _vp, _sz, _vp]),
-}
+_BY_VALUE = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+             "float": C.c_float, "double": C.c_double}
+_RETURNS = {**_BY_VALUE, "int": C.c_int, "const char*": C.c_char_p}
+_STRUCTS = {"vd_gemm_desc": GemmDesc}          # `const <struct>*` parameters bound to their ctypes mirror; every other pointer is c_void_p
+_DECL = re.compile(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(vd_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _parse_header(text):
+    """The declarations of the C header: ({name: (return type, [parameter, ...])} of the product entries, the same of the entries inside
+    #ifdef VD_PROBES ... #endif), each in header order, types and parameters as whitespace-normalised C text ("const float* xt")."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    tables = ({}, {})
+    for i, part in enumerate(re.split(r"#ifdef\s+VD_PROBES\b(.*?)#endif", text, flags=re.S)):       # odd parts: inside the #ifdef
+        decls = _DECL.findall(part)
+        if len(decls) != len(re.findall(r"\bvd_\w+\s*\(", part)):
+            raise RuntimeError(f"{HEADER_PATH}: a vd_* declaration is not of the form `type vd_name(parameters);`")
+        for ret, name, params in decls:
+            params = [" ".join(q.split()) for q in params.split(",")]
+            tables[i % 2][name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return tables
+
+
+def _ctypes_of(name, ret, params):
+    """(restype, [argtypes]) of one parsed declaration.  A by-value type outside _BY_VALUE / _RETURNS raises: there is no default type."""
+    def arg(q):
+        ctype = q.rpartition(" ")[0]
+        if "*" in q:
+            m = re.fullmatch(r"const (\w+)\*", ctype)
+            return C.POINTER(_STRUCTS[m.group(1)]) if m and m.group(1) in _STRUCTS else _vp
+        if ctype not in _BY_VALUE:
+            raise RuntimeError(f"{HEADER_PATH}: {name}: no ctypes type for the parameter `{q}`")
+        return _BY_VALUE[ctype]
+    if ret not in _RETURNS:
+        raise RuntimeError(f"{HEADER_PATH}: {name}: no ctypes type for the return type `{ret}`")
+    return _RETURNS[ret], [arg(q) for q in params]
+
+
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} not found: the ctypes binding is read from the C header of the source tree")
+    with open(HEADER_PATH) as f:
+        tables = _parse_header(f.read())
+    return [{name: _ctypes_of(name, *decl) for name, decl in t.items()} for t in tables]
+
+
+# name -> (restype, [argtypes]) of every entry point the header declares.  PROBE_EXPORTS: the extra entry points of libvdiff_hip_probe.so
+# (built with -DVD_PROBES; tests/probe/*.py load it through VDIFF_HIP_LIB): bound when the loaded library has them, absent from the product
+# library
+_SIGNATURES, PROBE_EXPORTS = _header_signatures()
 EXPORTS = tuple(_SIGNATURES)
-# extra entry points of libvdiff_hip_probe.so (built with -DVD_PROBES; tests/probe/*.py load it through VDIFF_HIP_LIB): bound when
-# the loaded library has them, absent from the product library
-PROBE_EXPORTS = {"vd_wino_set_probe": (C.c_int, [_vp]), "vd_wino43_set_probe": (C.c_int, [_vp]), "vd_gn_set_spin_probe": (C.c_int, [_vp])}
 
 _lib = None
 
@@ -204,6 +114,9 @@ class HipError(RuntimeError):
     pass
 
 
+_CPU_TENSOR = "v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)"
+
+
 def _check(rc, what):
     if rc != 0:
         raise HipError(f"{what} failed (rc={rc}): {lib().vd_last_error().decode(errors='replace')}")
@@ -213,7 +126,7 @@ def ptr(t):
     if t is None:
         return None
     if not t.is_cuda:
-        raise HipError("v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)")
+        raise HipError(_CPU_TENSOR)
     if t.dtype not in (torch.float32, torch.float64, torch.uint8, torch.int32):
         raise HipError(f"unsupported dtype {t.dtype}")
     return t.data_ptr()
@@ -221,6 +134,17 @@ def ptr(t):
 
 def stream():
     return torch.cuda.current_stream().cuda_stream
+
+
+def _host_floats(k, n):
+    """the `const float*` argument of an entry point that reads n coefficients on the host: a ctypes array of them, or None (NULL) for None"""
+    return None if k is None else (_f32 * n)(*[float(v) for v in k])
+
+
+def _table_ptr(table):
+    """device pointer of the int64 item table of a *_batched entry point"""
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+    return table.data_ptr()
 
 
 _ws_cache = {}
@@ -399,8 +323,7 @@ def wino_pack(w, Cout, Cin, uf=None, ud=None):
 
 
 def wino_pack_batched(table, n, total_blocks):
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
-    _check(lib().vd_wino_pack_batched(table.data_ptr(), n, total_blocks, stream()), "vd_wino_pack_batched")
+    _check(lib().vd_wino_pack_batched(_table_ptr(table), n, total_blocks, stream()), "vd_wino_pack_batched")
 
 
 def conv3x3_wino(x, ldx, U, bias, y, ldy, nimg, H, W, Cin, Cout, res=None, ldres=0, stats_part=None):
@@ -466,8 +389,7 @@ def wino43_pack(w, Cout, Cin, U43):
 
 
 def wino43_pack_batched(table, n, total_blocks):
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
-    _check(lib().vd_wino43_pack_batched(table.data_ptr(), n, total_blocks, stream()), "vd_wino43_pack_batched")
+    _check(lib().vd_wino43_pack_batched(_table_ptr(table), n, total_blocks, stream()), "vd_wino43_pack_batched")
 
 
 # forward convolutions of the 16x16 / 32x32 / 64-wide layers through F(4x4,3x3) with the dyadic interpolation points (csrc/wino43.hip:
@@ -685,8 +607,7 @@ def pack_conv3x3(w, Cout_w, Cin_w, wf=None, Cin_p=0, wd=None, Cout_p=0):
 
 def pack_conv3x3_batched(table, n, total_blocks):
     """table: int64 device tensor [n][8], see vd_pack_conv3x3_batched"""
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
-    _check(lib().vd_pack_conv3x3_batched(table.data_ptr(), n, total_blocks, stream()), "vd_pack_conv3x3_batched")
+    _check(lib().vd_pack_conv3x3_batched(_table_ptr(table), n, total_blocks, stream()), "vd_pack_conv3x3_batched")
 
 
 def gn_stats(x, ldx, nimg, HW, Cc, stats, G=32, eps=1e-6):
@@ -742,8 +663,7 @@ def gn_apply_bwd(dy, lddy, x, ldx, coef, gamma, beta, film, act, p_drop, seed, r
 
 
 def gn_param_sums_batched(table, n, total_blocks):
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
-    _check(lib().vd_gn_param_sums_batched(table.data_ptr(), n, total_blocks, stream()), "vd_gn_param_sums_batched")
+    _check(lib().vd_gn_param_sums_batched(_table_ptr(table), n, total_blocks, stream()), "vd_gn_param_sums_batched")
 
 
 def _gn_apply_bwd_call(dy, lddy, x, ldx, coef, gamma, beta, film, act, p_drop, seed, resample, add, ldadd, dx, lddx,
@@ -887,7 +807,7 @@ def bpd_bwd(x0, xt, out, coef, use_kl, gloss, mot, clip, dout, n, Cc, HW):
 
 def sample_step(xt, out, noise, k8, mot, cfg, last, clip, xn, xdup, n, Cc, HW, k_dev=None):
     """k8: 8 host floats, or None with k_dev = device tensor of 8 floats (graph-replayable form)"""
-    arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
+    arr = _host_floats(k8, 8)
     _check(lib().vd_sample_step(ptr(xt), ptr(out), ptr(noise), arr, ptr(k_dev), mot, int(cfg), int(last), int(clip), ptr(xn),
                                 ptr(xdup), n, Cc, HW, stream()), "vd_sample_step")
 
@@ -917,7 +837,7 @@ def hybrid_loss_bwd(x0, eps, xt, out, logsnr, coef, use_kl, aux, gloss, mot, rw,
 
 def sample_step_lv(xt, out, noise, k10, mot, cfg, last, clip, xn, xdup, n, Cc, HW):
     """sample_step for a learned-variance output; k10: 10 host floats (slot 5 = lvmin, slot 8 = delta); noise may be None"""
-    arr = (_f32 * 10)(*[float(v) for v in k10])
+    arr = _host_floats(k10, 10)
     _check(lib().vd_sample_step_lv(ptr(xt), ptr(out), ptr(noise), arr, mot, int(cfg), int(last), int(clip), ptr(xn), ptr(xdup),
                                    n, Cc, HW, stream()), "vd_sample_step_lv")
 
@@ -961,13 +881,12 @@ def consist_loss_bwd(resid, coef, gloss, aux, mot, dout, n, Cc, HW):
 
 def ema_track_batched(table, n, total_blocks, decay):
     """table: int64 device tensor [n][8], see vd_ema_track_batched"""
-    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
-    _check(lib().vd_ema_track_batched(table.data_ptr(), n, total_blocks, float(decay), stream()), "vd_ema_track_batched")
+    _check(lib().vd_ema_track_batched(_table_ptr(table), n, total_blocks, float(decay), stream()), "vd_ema_track_batched")
 
 
 def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=None):
     """k8: 8 host floats, or None with k_dev = device tensor of 8 floats (graph-replayable form)"""
-    arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
+    arr = _host_floats(k8, 8)
     _check(lib().vd_solver_step(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
                                 n, Cc, HW, stream()), "vd_solver_step")
 
@@ -975,7 +894,7 @@ def solver_step(xt, out, hist, k8, mot, cfg, clip, xn, xdup, n, Cc, HW, k_dev=No
 def unipc_step(xt, out, h0, h1, h2, k16, mot, cfg, clip, xn, xdup, xc_out, n, Cc, HW, k_dev=None):
     """one UniPC node: k16 = 16 host floats, or None with k_dev = device tensor of 16 floats (graph-replayable form); h0, h1, h2 = the
     last three guided predictions, shifted in place; xc_out (optional) receives the corrected state"""
-    arr = None if k16 is None else (_f32 * 16)(*[float(v) for v in k16])
+    arr = _host_floats(k16, 16)
     _check(lib().vd_unipc_step(ptr(xt), ptr(out), ptr(h0), ptr(h1), ptr(h2), arr, ptr(k_dev), mot, int(cfg), int(clip), ptr(xn), ptr(xdup),
                                ptr(xc_out), n, Cc, HW, stream()), "vd_unipc_step")
 
@@ -987,7 +906,7 @@ def abs_kth_rows(x, n, N, r, kth):
 
 def solver_step_dyn(xt, out, hist, k8, mot, cfg, r, s_max, s_out, xn, xdup, n, Cc, HW, k_dev=None):
     """solver_step with the guided prediction thresholded at its rank-r magnitude (s_max = inf: no cap); s_out optional, n floats"""
-    arr = None if k8 is None else (_f32 * 8)(*[float(v) for v in k8])
+    arr = _host_floats(k8, 8)
     _check(lib().vd_solver_step_dyn(ptr(xt), ptr(out), ptr(hist), arr, ptr(k_dev), mot, int(cfg), int(r), float(s_max), ptr(s_out),
                                     ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_solver_step_dyn")
 
@@ -995,21 +914,21 @@ def solver_step_dyn(xt, out, hist, k8, mot, cfg, r, s_max, s_out, xn, xdup, n, C
 def inpaint_step(xt, out, noise, known, mask, knoise, k10, mot, cfg, last, clip, mask_c, xn, xdup, n, Cc, HW, k_dev=None):
     """sample_step merged with ak*known + bk*knoise by the mask (n x mask_c x HW floats, mask_c 1 or C; 1 keeps the known image).
     k10: sample_step's 8 host floats + (ak, bk), or None with k_dev = device tensor of 10 floats (graph-replayable form)"""
-    arr = None if k10 is None else (_f32 * 10)(*[float(v) for v in k10])
+    arr = _host_floats(k10, 10)
     _check(lib().vd_inpaint_step(ptr(xt), ptr(out), ptr(noise), ptr(known), ptr(mask), ptr(knoise), arr, ptr(k_dev), mot, int(cfg),
                                  int(last), int(clip), int(mask_c), ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_inpaint_step")
 
 
 def forward_jump(x, noise, k2, xn, xdup, n, N, k_dev=None):
     """xn = a*x + b*noise over n rows of N floats (xdup optional: 2n interleaved rows); k2 = (a, b) host floats, or None with k_dev"""
-    arr = None if k2 is None else (_f32 * 2)(*[float(v) for v in k2])
+    arr = _host_floats(k2, 2)
     _check(lib().vd_forward_jump(ptr(x), ptr(noise), arr, ptr(k_dev), ptr(xn), ptr(xdup), n, int(N), stream()), "vd_forward_jump")
 
 
 def noise_extract(xt, out, x0, eps, k10, mot, cfg, last, clip, xs, z, xdup, n, Cc, HW, k_dev=None):
     """xs = ak*x0 + bk*eps and the noise map z = (xs - guided mean of sample_step)/k[5] (vd_noise_extract).  k10: inpaint_step's ten host
     floats, or None with k_dev = device tensor of 10 floats; eps may be None when bk = 0; xs may alias xt"""
-    arr = None if k10 is None else (_f32 * 10)(*[float(v) for v in k10])
+    arr = _host_floats(k10, 10)
     _check(lib().vd_noise_extract(ptr(xt), ptr(out), ptr(x0), ptr(eps), arr, ptr(k_dev), mot, int(cfg), int(last), int(clip), ptr(xs),
                                   ptr(z), ptr(xdup), n, Cc, HW, stream()), "vd_noise_extract")
 
@@ -1017,7 +936,7 @@ def noise_extract(xt, out, x0, eps, k10, mot, cfg, last, clip, xs, z, xdup, n, C
 def slerp_rows(a, b, frac, out, w_out, n, N, frac_dev=None):
     """out = spherical interpolation of n pairs of rows of N floats (vd_slerp_rows); frac = one host float, or None with frac_dev =
     device tensor of n floats; w_out optional, n x 2 floats"""
-    arr = None if frac is None else (_f32 * 1)(float(frac))
+    arr = _host_floats(None if frac is None else [frac], 1)
     _check(lib().vd_slerp_rows(ptr(a), ptr(b), arr, ptr(frac_dev), ptr(out), ptr(w_out), n, int(N), stream()), "vd_slerp_rows")
 
 
@@ -1062,7 +981,7 @@ def features_f16(x):
     """[n, d] fp16 device features as the distance kernels take them: contiguous, 16-byte aligned, d zero-padded to a multiple of
     KNN_K_STEP (a copy only when one of those does not hold already)"""
     if not x.is_cuda:
-        raise HipError("v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)")
+        raise HipError(_CPU_TENSOR)
     if x.dtype != torch.float16 or x.dim() != 2 or x.shape[0] < 1 or x.shape[1] < 1:
         raise HipError(f"features must be a non-empty [n, d] float16 tensor, got {x.dtype} {tuple(x.shape)}")
     pad = -x.shape[1] % KNN_K_STEP
@@ -1123,7 +1042,7 @@ def manifold_hits_f16(q, q_sq, s, s_sq, radius):
 def _dev_rows(x, dtype, what):
     """a 2-D device tensor of `dtype` whose rows are contiguous (any row pitch): (pointer, rows, columns, pitch)"""
     if not x.is_cuda:
-        raise HipError("v_diffusion HIP op received a CPU tensor: the hot path runs on an MI355X only (no CPU fallback)")
+        raise HipError(_CPU_TENSOR)
     if x.dtype != dtype or x.dim() != 2 or x.shape[0] < 1 or x.stride(1) != 1:
         raise HipError(f"{what} must be a non-empty 2-D {dtype} tensor with contiguous rows, got {x.dtype} {tuple(x.shape)} "
                        f"strides {tuple(x.stride())}")
