@@ -401,7 +401,10 @@ int vd_multitag_norm(const float* y, float* out, int32_t n, int32_t ncls, void* 
 
 /* ------------------------------------------------------------------ diffusion process (diffusion.py)
  * All images NCHW (the reference call surface); the UNet converts to NHWC at its own boundary.
- * model_out_type: 0 = v, 1 = x0, 2 = eps, 3 = both ; reweight: 0 = constant, 1 = snr, 2 = snr_trunc, 3 = snr_1plus */
+ * model_out_type: 0 = v, 1 = x0, 2 = eps, 3 = both ; reweight: 0 = constant, 1 = snr, 2 = snr_trunc, 3 = snr_1plus
+ * Every entry of this section returns 1 before any launch for a model_out_type outside 0..3 or a null buffer it would read or write
+ * (buffers called optional may be null), and for n, C or HW < 1 -- except vd_q_sample, vd_loss_bwd, vd_bpd_bwd and vd_sample_step,
+ * where an empty batch is a no-op. */
 /* q_sample (diffusion.py:242-245): xt = sqrt(sigmoid(l_b)) x0 + sqrt(sigmoid(-l_b)) eps */
 int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C, int32_t HW, void* stream);
 /* train_loss mse branch (diffusion.py:520-541 with the conversions of :466-490): per-sample loss[n];

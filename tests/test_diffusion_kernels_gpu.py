@@ -176,10 +176,13 @@ def test_sample_step_grid_wraps(H):
     sw.done()
 
 
-@pytest.mark.parametrize("mot,cfg,shape", [("both", 1, (3, 3, 33, 17)), ("v", 0, (5, 3, 8, 8)), ("eps", 1, (2, 1, 5, 3)), ("x0", 0, (3, 3, 33, 17))])
+@pytest.mark.parametrize("mot,cfg,shape", [("both", 1, (3, 3, 33, 17)), ("v", 0, (5, 3, 8, 8)), ("eps", 1, (2, 1, 5, 3)), ("x0", 0, (3, 3, 33, 17))] +
+                         [(m, c, s) for s in ((2, 3, 18, 18), (3, 3, 5, 5)) for m in ("both", "v") for c in (1, 0)])
 def test_sample_step_contracts(H, mot, cfg, shape):
     """what the samplers rely on, bitwise: device-resident coefficients, in-place update, the duplicated output of the guided
-    chain, no noise pointer when the noise scale is zero, ``last`` = the (guided, clipped) x0 prediction whatever c1, c2 are"""
+    chain, no noise pointer when the noise scale is zero, ``last`` = the (guided, clipped) x0 prediction whatever c1, c2 are;
+    and the same bits from 16-byte-aligned buffers (the dwordx4 form where C*HW is a multiple of 4: 972 at (2,3,18,18)) as from the
+    same data one float further on (always the scalar form; 75 at (3,3,5,5) is scalar either way)"""
     from oracle import diffusion_ref as dref
     B, C, Hh, Ww = shape
     T, step, w = 8, 3, (1.5 if cfg else 0.0)
@@ -196,6 +199,18 @@ def test_sample_step_contracts(H, mot, cfg, shape):
     base, base_ok = guarded(shape)
     call(xt_d, noise_d, k8, base)
     assert base_ok()
+
+    # every buffer 16-byte aligned, then every buffer one float past such an address: the offset call can only take the scalar form
+    def placed(t, off):
+        v = torch.empty(t.numel() + 4, device=DEV)[off:off + t.numel()].view(t.shape)
+        assert v.data_ptr() % 16 == 4 * off
+        return v.copy_(t)
+    xn_a, xn_o = (placed(torch.zeros(shape), off) for off in (0, 1))
+    dup_a, dup_o = (placed(torch.zeros((2 * B, C, Hh, Ww)), off) for off in (0, 1))
+    H.sample_step(placed(xt_d, 0), placed(out_d, 0), placed(noise_d, 0), k8, mid, cfg, False, True, xn_a, dup_a, B, C, Hh * Ww)
+    H.sample_step(placed(xt_d, 1), placed(out_d, 1), placed(noise_d, 1), k8, mid, cfg, False, True, xn_o, dup_o, B, C, Hh * Ww)
+    assert torch.equal(xn_a, xn_o) and torch.equal(dup_a, dup_o), "aligned and offset buffers give different bits"
+    assert torch.equal(xn_a, base) and torch.equal(dup_a[0::2], base) and torch.equal(dup_a[1::2], base)
     # device-resident coefficients (k8 = None, k_dev = 8 floats): the form a captured graph replays
     kd = torch.tensor(k8, dtype=torch.float32).to(DEV)
     assert torch.equal(call(xt_d, noise_d, None, torch.empty(shape, device=DEV), k_dev=kd), base)

@@ -117,6 +117,73 @@ def test_the_header_parser_refuses_what_it_cannot_bind(monkeypatch):
         _hip._header_signatures()
 
 
+# the buffers each of the six oldest diffusion entries dereferences (pred, mse, noise, xdup stay optional)
+OLD_ENTRY_BUFFERS = {
+    "vd_q_sample": ("x0", "eps", "logsnr", "xt"),
+    "vd_loss_fwd": ("x0", "eps", "xt", "out", "logsnr", "loss", "aux"),
+    "vd_loss_bwd": ("x0", "eps", "xt", "out", "logsnr", "aux", "gloss", "dout"),
+    "vd_sample_step": ("xt", "out", "xn"),
+    "vd_bpd_terms": ("x0", "xt", "out", "coef", "kl", "nll"),
+    "vd_bpd_bwd": ("x0", "xt", "out", "coef", "use_kl", "gloss", "dout"),
+}
+# one required buffer of each entry that already refused a null pointer: the shared helper reports under the entry's own name
+CHECKED_ENTRY_BUFFER = {
+    "vd_bpd_terms_lv": "coef", "vd_bpd_bwd_lv": "use_kl", "vd_hybrid_loss_fwd": "logsnr", "vd_hybrid_loss_bwd": "gloss",
+    "vd_sample_step_lv": "xn", "vd_distill_mid": "zmid", "vd_distill_loss_fwd": "dhat", "vd_distill_loss_bwd": "resid",
+    "vd_consist_mid": "dz", "vd_consist_pair": "zs", "vd_consist_loss_fwd": "target_out", "vd_consist_loss_bwd": "aux",
+    "vd_solver_step": "hist",
+}
+
+
+def test_diffusion_entries_refuse_bad_arguments_before_any_launch():
+    """csrc/diffusion.hip: a null required buffer, a model_out_type outside 0..3 and (where the grid is n workgroups) an empty batch are
+    refused with rc 1 and a message under the entry's own name.  A refused call returns before any HIP call, so this needs no device:
+    the pointers are null or host-side dummy addresses that nothing dereferences, n, C, HW = 2, 3, 64."""
+    from v_diffusion import _hip
+    lib = _hip.lib()
+    with open(_hip.HEADER_PATH) as f:
+        decls = _hip._parse_header(f.read())[0]
+    dummy = ctypes.create_string_buffer(64)
+    k16 = (ctypes.c_float * 16)()                             # the host coefficients ARE read (k[5] = 0: no noise needed)
+    SNR_TRUNC = 2
+
+    def call(name, **over):
+        args = []
+        for p in decls[name][1]:
+            ctype, _, pname = p.rpartition(" ")
+            if pname in over:
+                args.append(over[pname])
+            elif pname in ("stream", "k_dev"):
+                args.append(None)
+            elif pname == "k":
+                args.append(ctypes.addressof(k16))
+            elif ctype.endswith("*"):
+                args.append(ctypes.addressof(dummy))
+            else:
+                args.append({"n": 2, "C": 3, "HW": 64, "reweight": SNR_TRUNC}.get(pname, 0))
+        return getattr(lib, name)(*args), lib.vd_last_error().decode()
+
+    for name, buffers in OLD_ENTRY_BUFFERS.items():
+        for b in buffers:
+            rc, msg = call(name, **{b: None})
+            assert rc == 1 and msg == f"{name}: null pointer", (name, b, rc, msg)
+        if name != "vd_q_sample":                             # (it takes no output type)
+            rc, msg = call(name, model_out_type=7)
+            assert rc == 1 and msg == f"{name}: bad model_out_type 7", (name, rc, msg)
+    for name in ("vd_loss_fwd", "vd_bpd_terms"):
+        rc, msg = call(name, n=0)
+        assert rc == 1 and msg == f"{name}: empty batch or image (n=0, C=3, HW=64)", (name, rc, msg)
+    for name in ("vd_loss_fwd", "vd_loss_bwd"):              # "both" goes with snr_trunc only
+        for rw in (0, 1, 3):
+            rc, msg = call(name, model_out_type=3, reweight=rw)
+            assert rc == 1 and msg.startswith(f"{name}: 'both' output needs snr_trunc"), (name, rw, rc, msg)
+        rc, msg = call(name, reweight=4)
+        assert rc == 1 and msg == f"{name}: bad reweight 4", (name, rc, msg)
+    for name, b in CHECKED_ENTRY_BUFFER.items():
+        rc, msg = call(name, **{b: None})
+        assert rc == 1 and msg == f"{name}: null pointer", (name, b, rc, msg)
+
+
 def test_product_library_has_no_probe_or_experiment_code():
     """Round-2 review: the shipped .so honoured VD_WINO_EXP (timing variants that compute WRONG results) and exported
     vd_wino_set_probe.  Those live in libvdiff_hip_probe.so now (-DVD_PROBES, tests/probe/ only): the product library must not

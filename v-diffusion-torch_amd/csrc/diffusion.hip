@@ -4,9 +4,11 @@
 //   one reverse step (p_mean_var + CFG + noise)  diffusion.py:317-392
 //   variational-bound terms (KL / discretised decoder NLL, loss_type "kl") forward/backward  diffusion.py:446-464,497-515
 //   learned variances (bound terms, hybrid loss, reverse step for outputs with variance channels)  the intent of diffusion.py:320-324
-//   progressive distillation, consistency distillation / training and the batched target-network update, the DPM-Solver++(2M) reverse step and its dynamically thresholded form, the RePaint masked reverse step and the forward
-//   jump, the noise-map extraction of DDPM inversion and spherical interpolation: no counterpart in the reference
+// Without a counterpart in the reference: progressive distillation; consistency distillation / training and the batched
+// target-network update; the DPM-Solver++(2M) reverse step, its dynamically thresholded form and the UniPC step; the RePaint
+// masked reverse step and the forward jump; the noise-map extraction of DDPM inversion; spherical interpolation.
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
+// Device side first, then the host helpers (launch, coefficient carrier, the refusals every entry shares), then the C entries.
 #include "common.h"
 
 namespace {
@@ -33,14 +35,25 @@ __device__ __forceinline__ PredCoef pred_coef(int type, float l) {
     return k;
 }
 
+// alpha = sqrt(sigmoid(l)), sigma = sqrt(sigmoid(-l))
+struct AlphaSigma { float sa, ss; };
+
+__device__ __forceinline__ AlphaSigma alpha_sigma(float l) { return {sqrtf(1.f / (1.f + expf(-l))), sqrtf(1.f / (1.f + expf(l)))}; }
+
+// z_t = alpha x_0 + sigma eps: two products, each rounded, then their sum (vd_consist_pair's z_t is vd_q_sample's bit for bit:
+// tests/test_consistency_gpu.py holds the two together)
+__device__ __forceinline__ float q_sample_value(float x0, float eps, float sa, float ss) {
+#pragma clang fp contract(off)
+    return x0 * sa + eps * ss;
+}
+
 __global__ void q_sample_kernel(const float* x0, const float* eps, const float* logsnr, float* xt, long long n,
                                 long long CHW) {
     const long long total = n * CHW;
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
          idx += (long long)gridDim.x * blockDim.x) {
-        const float l = logsnr[idx / CHW];
-        const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
-        xt[idx] = x0[idx] * sa + eps[idx] * ss;
+        const auto [sa, ss] = alpha_sigma(logsnr[idx / CHW]);
+        xt[idx] = q_sample_value(x0[idx], eps[idx], sa, ss);
     }
 }
 
@@ -62,13 +75,17 @@ struct LossArgs {
     const float* logsnr; int type, rw; int n, C; long long HW;
 };
 
+// The MSE loss.  These two kernels and the hybrid kernels (loss_sq / loss_grad below) write the same expression, each in its own
+// text: which product of a0*xt + b0x*o + b0e*oe stays unfused is the compiler's choice, and it chooses differently for the two
+// spellings.  Routed through loss_sq / loss_grad, both kernels moved their snr_trunc results on an MI355X, the other reweightings
+// not: 9 of 78 forward and 20 of 78 backward cases, up to 1.5e-7 of a row's loss and 4.7e-4 of a row's largest gradient (FINDINGS.md).
 // one workgroup per sample
 __global__ __launch_bounds__(256) void loss_fwd_kernel(const LossArgs p, float* loss, float* aux) {
     __shared__ float sh[8];
     const int b = blockIdx.x;
     const float l = p.logsnr[b];
     const PredCoef k = pred_coef(p.type, l);
-    const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+    const auto [sa, ss] = alpha_sigma(l);
     float e0 = 0.f, e1 = 0.f;
     const long long N = (long long)p.C * p.HW;
     const int Co = p.type == OUT_BOTH ? 2 * p.C : p.C;
@@ -105,7 +122,7 @@ __global__ void loss_bwd_kernel(const LossArgs p, const float* aux, const float*
         const long long b = idx / N, i = idx % N;
         const float l = p.logsnr[b];
         const PredCoef k = pred_coef(p.type, l);
-        const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+        const auto [sa, ss] = alpha_sigma(l);
         const float g = gloss[b] * 2.f / (float)N;
         const float* ob = p.out + b * Co * p.HW;
         float* db = dout + b * Co * p.HW;
@@ -339,9 +356,8 @@ __global__ void bpd_bwd_lv_kernel(const BpdArgs p, const float* use_kl, const fl
 // ---- hybrid loss (Nichol & Dhariwal 2021, eq. 16): loss_b = mse_b + vlb * (use_kl[b] ? kl_b : nll_b), mse_b loss_fwd_kernel's on the
 // prediction channels and the bound term bpd_terms_lv_kernel's without clipping, whose mean is a constant to the gradient.
 // aux[b][4] = {the two snr_trunc means, kl_b, nll_b}.
-// The mse part is loss_fwd_kernel's and loss_bwd_kernel's expression per element, restated as values (those two kernels keep their own
-// text: their bits are pinned by the training parity checks): the squared errors one element adds (e1: the eps error of snr_trunc,
-// else 0) and their gradient g * d e / d out (ge: for the second half of a "both" output).
+// The mse part is loss_fwd_kernel's and loss_bwd_kernel's expression per element, as values: the squared errors one element adds
+// (e1: the eps error of snr_trunc, else 0) and their gradient g * d e / d out (ge: for the second half of a "both" output).
 struct SqErr { float e0, e1; };
 struct OutGrad { float gx, ge; };
 
@@ -374,7 +390,7 @@ __global__ __launch_bounds__(256) void hybrid_fwd_kernel(const LossArgs p, const
     const int b = blockIdx.x;
     const float l = p.logsnr[b];
     const PredCoef k = pred_coef(p.type, l);
-    const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+    const auto [sa, ss] = alpha_sigma(l);
     const LvCoef q = lv_coef(coef + 8 * b);
     const long long N = (long long)p.C * p.HW, Np = p.type == OUT_BOTH ? 2 * N : N;
     const float* ob = p.out + (long long)b * (Np + N);
@@ -409,7 +425,7 @@ __global__ void hybrid_bwd_kernel(const LossArgs p, const float* coef, const flo
         const long long b = idx / N, i = idx % N;
         const float l = p.logsnr[b];
         const PredCoef k = pred_coef(p.type, l);
-        const float sa = sqrtf(1.f / (1.f + expf(-l))), ss = sqrtf(1.f / (1.f + expf(l)));
+        const auto [sa, ss] = alpha_sigma(l);
         const LvCoef q = lv_coef(coef + 8 * b);
         const float* ob = p.out + b * (Np + N);
         float* db = dout + b * (Np + N);
@@ -563,49 +579,32 @@ __device__ __forceinline__ void guided(const StepCommon& s, long long b, long lo
 
 struct StepArgs { StepCommon s; const float* noise; };
 
-// one reverse step for a batch sharing the step index: xn = guided mean_plain + k[5]*noise (when noise is given).  Scalar.
-__global__ void sample_step_kernel(const StepArgs p) {
-    const StepCommon& s = p.s;
-    const long long N = s.N, total = (long long)s.n * N;
-    const float* k = coefs(s.c);
-    const StepMean<false> f = step_mean<false>(s, k);
-    const float nscale = k[5], w = k[6];
-    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total;
-         idx += (long long)gridDim.x * blockDim.x) {
-        const long long b = idx / N, i = idx % N;
-        float z[1], v[1];
-        ldv<1>(s.xt + idx, z);
-        guided<1>(s, b, i, w, z, f, v);
-        if (p.noise) v[0] = axpby(1.f, v[0], nscale, p.noise[idx]);
-        st_dup<1>(s.xn, s.xdup, b, N, i, v);
-    }
-}
-
-// the same step for a network with learned variances (s.row = prediction channels + N): k = {a0, b0x, b0e, c1, c2, lvmin, w_guide, c3,
-// delta, 0}, host floats only;  xn = guided mean_plain + exp(0.5 (lvmin + delta*sigmoid(nu))) * noise, nu the variance channels of the
-// CONDITIONAL row (diffusion.py:386-387), when noise is given and the step is not the last.  Without noise this is sample_step_kernel
-// on the prediction channels, bit for bit.
 __device__ __forceinline__ float lv_sigma(float lvmin, float delta, float nu) { return expf(0.5f * lv_logvar(lvmin, delta, lv_frac(nu).frac)); }
 
-template <int V>
-__global__ void sample_step_lv_kernel(const StepArgs p) {
+// one reverse step for a batch sharing the step index: xn = guided mean_plain + sigma * noise.
+// Fixed variance (LV = false): sigma = k[5], added whenever noise is given, on the last step too.
+// Learned variances (LV = true; s.row = prediction channels + N): k = {a0, b0x, b0e, c1, c2, lvmin, w_guide, c3, delta, 0} and per
+// element sigma = exp(0.5 (lvmin + delta*sigmoid(nu))), nu the variance channels of the CONDITIONAL row (diffusion.py:386-387), added
+// when noise is given and the step is not the last.  Without noise the two forms agree bit for bit on the prediction channels.
+template <int V, bool LV>
+__global__ void sample_step_kernel(const StepArgs p) {
     const StepCommon& s = p.s;
     const long long N = s.N, total = (long long)s.n * N / V;
-    const float* k = s.c.k;
+    const float* k = coefs(s.c);
     const StepMean<false> f = step_mean<false>(s, k);
-    const float lvmin = k[5], w = k[6], delta = k[8];
-    const bool noisy = p.noise && !s.last;
+    const float k5 = k[5], w = k[6], delta = LV ? k[8] : 0.f;             // (k5: the noise scale, or lvmin)
+    const bool noisy = p.noise && !(LV && s.last);
     for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
         const long long e = idx * V, b = e / N, i = e % N;
         float z[V], v[V];
         ldv<V>(s.xt + e, z);
         guided<V>(s, b, i, w, z, f, v);
         if (noisy) {
-            float nu[V], nz[V];
-            ldv<V>(s.out + b * (1 + s.cfg) * s.row + (s.row - N) + i, nu);
+            float nu[V] = {}, nz[V];
+            if constexpr (LV) ldv<V>(s.out + b * (1 + s.cfg) * s.row + (s.row - N) + i, nu);
             ldv<V>(p.noise + e, nz);
 #pragma unroll
-            for (int j = 0; j < V; ++j) v[j] = axpby(1.f, v[j], lv_sigma(lvmin, delta, nu[j]), nz[j]);
+            for (int j = 0; j < V; ++j) v[j] = axpby(1.f, v[j], LV ? lv_sigma(k5, delta, nu[j]) : k5, nz[j]);
         }
         st_dup<V>(s.xn, s.xdup, b, N, i, v);
     }
@@ -785,13 +784,6 @@ __global__ void consist_mid_kernel(const ConsistMidArgs p) {
     }
 }
 
-// q_sample_kernel's value as that kernel is compiled: two products, each rounded, then their sum (vd_consist_pair's z_t is
-// vd_q_sample's bit for bit: tests/test_consistency_gpu.py holds the two together)
-__device__ __forceinline__ float q_sample_value(float x0, float eps, float sa, float ss) {
-#pragma clang fp contract(off)
-    return x0 * sa + eps * ss;
-}
-
 // training mode: z_t (q_sample), z_s = alpha_s x_0 + sigma_s eps and dz = (alpha_s - alpha_t) x_0 + (sigma_s - sigma_t) eps in one pass
 template <int V>
 __global__ void consist_pair_kernel(const float* x0, const float* eps, const float* coef, float* zt, float* zs, float* dz, int n,
@@ -801,7 +793,7 @@ __global__ void consist_pair_kernel(const float* x0, const float* eps, const flo
         const long long e = idx * V, b = e / N;
         const float* k = coef + CK * b;
         const float l = k[13], da = k[18], ds = k[19], as = k[20], ss = k[21];
-        const float sat = sqrtf(1.f / (1.f + expf(-l))), sst = sqrtf(1.f / (1.f + expf(l)));
+        const auto [sat, sst] = alpha_sigma(l);
         float x[V], ep[V], a[V], s[V], d[V];
         ldv<V>(x0 + e, x);
         ldv<V>(eps + e, ep);
@@ -1315,13 +1307,45 @@ inline StepCommon step_common(const float* xt, const float* out, int type, int c
     return s;
 }
 
-// the refusals the step entries share (the first that applies is the one reported); ptrs = the entry's own buffers are all given
+inline LossArgs loss_args(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr, int type, int rw, int n,
+                          int C, int HW) {
+    return {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
+}
+
+inline BpdArgs bpd_args(const float* x0, const float* xt, const float* out, const float* coef, int type, int clip, int n, int C, int HW) {
+    return {x0, xt, out, coef, type, clip ? 1 : 0, n, C, (long long)HW};
+}
+
+// The refusals the entries share, each in one wording; the first that applies is the one reported.  A refused call has launched nothing.
+// ptrs = the buffers the kernel dereferences for these arguments are all given
+inline int args_given(const char* who, int type, bool ptrs) {
+    VD_REQUIRE(type >= 0 && type <= 3, "%s: bad model_out_type %d", who, type);
+    VD_REQUIRE(ptrs, "%s: null pointer", who);
+    return 0;
+}
+
+inline int not_empty(const char* who, int n, int C, int HW) {
+    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "%s: empty batch or image (n=%d, C=%d, HW=%d)", who, n, C, HW);
+    return 0;
+}
+
+inline int args_checks(const char* who, int type, bool ptrs, int n, int C, int HW) {          // both
+    VD_TRY(args_given(who, type, ptrs));
+    return not_empty(who, n, C, HW);
+}
+
+// the mse and hybrid loss entries: the reweighting too, and the reference's shape rule
+inline int loss_checks(const char* who, int type, int rw, bool ptrs) {
+    VD_REQUIRE(rw >= 0 && rw <= 3, "%s: bad reweight %d", who, rw);
+    VD_TRY(args_given(who, type, ptrs));
+    VD_REQUIRE(!(type == OUT_BOTH && rw != RW_SNR_TRUNC), "%s: 'both' output needs snr_trunc (reference shape rule)", who);
+    return 0;
+}
+
+// the step entries: the coefficients too
 inline int step_checks(const char* who, StepCommon& s, const float* k, const float* k_dev, int count, bool ptrs, int C, int HW) {
     VD_TRY(set_coefs(who, s.c, k, k_dev, count));
-    VD_REQUIRE(s.type >= 0 && s.type <= 3, "%s: bad model_out_type %d", who, s.type);
-    VD_REQUIRE(ptrs, "%s: null pointer", who);
-    VD_REQUIRE(s.n > 0 && C > 0 && HW > 0, "%s: empty batch or image (n=%d, C=%d, HW=%d)", who, s.n, C, HW);
-    return 0;
+    return args_checks(who, s.type, ptrs, s.n, C, HW);
 }
 
 inline int dup_is_guided(const char* who, const StepCommon& s) {
@@ -1333,7 +1357,8 @@ inline int dup_is_guided(const char* who, const StepCommon& s) {
 
 extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsnr, float* xt, int32_t n, int32_t C,
                            int32_t HW, void* stream) {
-    const long long chw = (long long)C * HW;
+    VD_TRY(args_given("vd_q_sample", OUT_V, x0 && eps && logsnr && xt));          // (no output type here)
+    const long long chw = (long long)C * HW;                                     // an empty call launches one idle workgroup
     hipLaunchKernelGGL(q_sample_kernel, dim3(grid_for(n * chw)), dim3(256), 0, (hipStream_t)stream, x0, eps, logsnr, xt,
                        (long long)n, chw);
     VD_LAUNCH_CHECK("q_sample_kernel");
@@ -1342,10 +1367,10 @@ extern "C" int vd_q_sample(const float* x0, const float* eps, const float* logsn
 
 extern "C" int vd_loss_fwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
                            int32_t type, int32_t rw, float* loss, float* aux, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3 && rw >= 0 && rw <= 3, "vd_loss_fwd: bad model_out_type/reweight (%d,%d)", type, rw);
-    VD_REQUIRE(!(type == OUT_BOTH && rw != RW_SNR_TRUNC), "vd_loss_fwd: 'both' output needs snr_trunc (reference shape rule)");
-    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
-    hipLaunchKernelGGL(loss_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, loss, aux);
+    VD_TRY(loss_checks("vd_loss_fwd", type, rw, x0 && eps && xt && out && logsnr && loss && aux));
+    VD_TRY(not_empty("vd_loss_fwd", n, C, HW));
+    hipLaunchKernelGGL(loss_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, loss_args(x0, eps, xt, out, logsnr, type, rw, n, C, HW),
+                       loss, aux);
     VD_LAUNCH_CHECK("loss_fwd_kernel");
     return 0;
 }
@@ -1353,31 +1378,32 @@ extern "C" int vd_loss_fwd(const float* x0, const float* eps, const float* xt, c
 extern "C" int vd_loss_bwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
                            const float* aux, const float* gloss, int32_t type, int32_t rw, float* dout, int32_t n, int32_t C,
                            int32_t HW, void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3 && rw >= 0 && rw <= 3, "vd_loss_bwd: bad model_out_type/reweight");
-    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
-    hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, aux, gloss,
-                       dout);
+    VD_TRY(loss_checks("vd_loss_bwd", type, rw, x0 && eps && xt && out && logsnr && aux && gloss && dout));
+    hipLaunchKernelGGL(loss_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                       loss_args(x0, eps, xt, out, logsnr, type, rw, n, C, HW), aux, gloss, dout);
     VD_LAUNCH_CHECK("loss_bwd_kernel");
     return 0;
 }
 
+// (xdup is accepted without guidance, and an empty batch is a no-op: no dup_is_guided, no not_empty)
 extern "C" int vd_sample_step(const float* xt, const float* out, const float* noise, const float* k, const float* k_dev,
                               int32_t type, int32_t cfg, int32_t last_step, int32_t clip, float* xn, float* xdup, int32_t n,
                               int32_t C, int32_t HW, void* stream) {
     StepArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, HW), noise};
     VD_TRY(set_coefs("vd_sample_step", p.s.c, k, k_dev, 8));
+    VD_TRY(args_given("vd_sample_step", type, xt && out && xn));
     VD_REQUIRE(noise != nullptr || k_dev != nullptr || k[5] == 0.f, "vd_sample_step: noise required when the noise scale is non-zero");
-    hipLaunchKernelGGL(sample_step_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p);
+    launch_elems(sample_step_kernel<4, false>, sample_step_kernel<1, false>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, xn, xdup),
+                 n * p.s.N, stream, p);
     VD_LAUNCH_CHECK("sample_step_kernel");
     return 0;
 }
 
 extern "C" int vd_bpd_terms(const float* x0, const float* xt, const float* out, const float* coef, int32_t type, int32_t clip,
                             float* kl, float* nll, float* pred, float* mse, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_terms: bad model_out_type %d", type);
-    VD_REQUIRE(x0 && xt && out && coef && kl && nll, "vd_bpd_terms: null pointer");
-    BpdArgs p = {x0, xt, out, coef, type, clip, n, C, (long long)HW};
-    hipLaunchKernelGGL(bpd_terms_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, kl, nll, pred, mse);
+    VD_TRY(args_checks("vd_bpd_terms", type, x0 && xt && out && coef && kl && nll, n, C, HW));
+    hipLaunchKernelGGL(bpd_terms_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, bpd_args(x0, xt, out, coef, type, clip, n, C, HW), kl,
+                       nll, pred, mse);
     VD_LAUNCH_CHECK("bpd_terms_kernel");
     return 0;
 }
@@ -1385,22 +1411,18 @@ extern "C" int vd_bpd_terms(const float* x0, const float* xt, const float* out, 
 extern "C" int vd_bpd_bwd(const float* x0, const float* xt, const float* out, const float* coef, const float* use_kl,
                           const float* gloss, int32_t type, int32_t clip, float* dout, int32_t n, int32_t C, int32_t HW,
                           void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_bwd: bad model_out_type %d", type);
-    VD_REQUIRE(x0 && xt && out && coef && use_kl && gloss && dout, "vd_bpd_bwd: null pointer");
-    BpdArgs p = {x0, xt, out, coef, type, clip, n, C, (long long)HW};
-    hipLaunchKernelGGL(bpd_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, use_kl, gloss,
-                       dout);
+    VD_TRY(args_given("vd_bpd_bwd", type, x0 && xt && out && coef && use_kl && gloss && dout));
+    hipLaunchKernelGGL(bpd_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                       bpd_args(x0, xt, out, coef, type, clip, n, C, HW), use_kl, gloss, dout);
     VD_LAUNCH_CHECK("bpd_bwd_kernel");
     return 0;
 }
 
 extern "C" int vd_bpd_terms_lv(const float* x0, const float* xt, const float* out, const float* coef, int32_t type, int32_t clip,
                                float* kl, float* nll, float* pred, float* mse, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_terms_lv: bad model_out_type %d", type);
-    VD_REQUIRE(x0 && xt && out && coef && kl && nll, "vd_bpd_terms_lv: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_bpd_terms_lv: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
-    BpdArgs p = {x0, xt, out, coef, type, clip ? 1 : 0, n, C, (long long)HW};
-    hipLaunchKernelGGL(bpd_terms_lv_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, kl, nll, pred, mse);
+    VD_TRY(args_checks("vd_bpd_terms_lv", type, x0 && xt && out && coef && kl && nll, n, C, HW));
+    hipLaunchKernelGGL(bpd_terms_lv_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, bpd_args(x0, xt, out, coef, type, clip, n, C, HW),
+                       kl, nll, pred, mse);
     VD_LAUNCH_CHECK("bpd_terms_lv_kernel");
     return 0;
 }
@@ -1408,30 +1430,19 @@ extern "C" int vd_bpd_terms_lv(const float* x0, const float* xt, const float* ou
 extern "C" int vd_bpd_bwd_lv(const float* x0, const float* xt, const float* out, const float* coef, const float* use_kl,
                              const float* gloss, int32_t type, int32_t clip, int32_t mean_grad, float* dout, int32_t n, int32_t C,
                              int32_t HW, void* stream) {
-    VD_REQUIRE(type >= 0 && type <= 3, "vd_bpd_bwd_lv: bad model_out_type %d", type);
-    VD_REQUIRE(x0 && xt && out && coef && use_kl && gloss && dout, "vd_bpd_bwd_lv: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_bpd_bwd_lv: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
-    BpdArgs p = {x0, xt, out, coef, type, clip ? 1 : 0, n, C, (long long)HW};
-    hipLaunchKernelGGL(bpd_bwd_lv_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, use_kl, gloss,
-                       (int)(mean_grad ? 1 : 0), dout);
+    VD_TRY(args_checks("vd_bpd_bwd_lv", type, x0 && xt && out && coef && use_kl && gloss && dout, n, C, HW));
+    hipLaunchKernelGGL(bpd_bwd_lv_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream,
+                       bpd_args(x0, xt, out, coef, type, clip, n, C, HW), use_kl, gloss, (int)(mean_grad ? 1 : 0), dout);
     VD_LAUNCH_CHECK("bpd_bwd_lv_kernel");
-    return 0;
-}
-
-// the refusals the two hybrid entries share
-static int hybrid_checks(const char* who, int type, int rw, bool ptrs, int n, int C, int HW) {
-    VD_REQUIRE(type >= 0 && type <= 3 && rw >= 0 && rw <= 3, "%s: bad model_out_type/reweight (%d,%d)", who, type, rw);
-    VD_REQUIRE(!(type == OUT_BOTH && rw != RW_SNR_TRUNC), "%s: 'both' output needs snr_trunc (reference shape rule)", who);
-    VD_REQUIRE(ptrs, "%s: null pointer", who);
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "%s: empty batch or image (n=%d, C=%d, HW=%d)", who, n, C, HW);
     return 0;
 }
 
 extern "C" int vd_hybrid_loss_fwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
                                   const float* coef, const float* use_kl, int32_t type, int32_t rw, float vlb_weight, float* loss,
                                   float* aux, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_TRY(hybrid_checks("vd_hybrid_loss_fwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && loss && aux, n, C, HW));
-    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
+    VD_TRY(loss_checks("vd_hybrid_loss_fwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && loss && aux));
+    VD_TRY(not_empty("vd_hybrid_loss_fwd", n, C, HW));
+    const LossArgs p = loss_args(x0, eps, xt, out, logsnr, type, rw, n, C, HW);
     hipLaunchKernelGGL(hybrid_fwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p, coef, use_kl, vlb_weight, loss, aux);
     VD_LAUNCH_CHECK("hybrid_fwd_kernel");
     return 0;
@@ -1440,8 +1451,9 @@ extern "C" int vd_hybrid_loss_fwd(const float* x0, const float* eps, const float
 extern "C" int vd_hybrid_loss_bwd(const float* x0, const float* eps, const float* xt, const float* out, const float* logsnr,
                                   const float* coef, const float* use_kl, const float* aux, const float* gloss, int32_t type, int32_t rw,
                                   float vlb_weight, float* dout, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_TRY(hybrid_checks("vd_hybrid_loss_bwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && aux && gloss && dout, n, C, HW));
-    LossArgs p = {x0, eps, xt, out, logsnr, type, rw, n, C, (long long)HW};
+    VD_TRY(loss_checks("vd_hybrid_loss_bwd", type, rw, x0 && eps && xt && out && logsnr && coef && use_kl && aux && gloss && dout));
+    VD_TRY(not_empty("vd_hybrid_loss_bwd", n, C, HW));
+    const LossArgs p = loss_args(x0, eps, xt, out, logsnr, type, rw, n, C, HW);
     hipLaunchKernelGGL(hybrid_bwd_kernel, dim3(grid_for((long long)n * C * HW)), dim3(256), 0, (hipStream_t)stream, p, coef, use_kl,
                        vlb_weight, aux, gloss, dout);
     VD_LAUNCH_CHECK("hybrid_bwd_kernel");
@@ -1455,17 +1467,15 @@ extern "C" int vd_sample_step_lv(const float* xt, const float* out, const float*
     VD_TRY(step_checks("vd_sample_step_lv", p.s, k, nullptr, 10, xt && out && xn, C, HW));
     VD_TRY(dup_is_guided("vd_sample_step_lv", p.s));
     p.s.row += p.s.N;                                         // the variance channels follow the prediction channels
-    launch_elems(sample_step_lv_kernel<4>, sample_step_lv_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, xn, xdup), n * p.s.N,
-                 stream, p);
-    VD_LAUNCH_CHECK("sample_step_lv_kernel");
+    launch_elems(sample_step_kernel<4, true>, sample_step_kernel<1, true>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, xn, xdup),
+                 n * p.s.N, stream, p);
+    VD_LAUNCH_CHECK("sample_step_kernel (learned variances)");
     return 0;
 }
 
 extern "C" int vd_distill_mid(const float* zt, const float* out, const float* coef, int32_t teacher_type, int32_t cfg, int32_t clip,
                               float* xhat, float* dhat, float* zmid, float* zdup, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3, "vd_distill_mid: bad model_out_type %d", teacher_type);
-    VD_REQUIRE(zt && out && coef && xhat && dhat && zmid, "vd_distill_mid: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_mid: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_distill_mid", teacher_type, zt && out && coef && xhat && dhat && zmid, n, C, HW));
     VD_REQUIRE(!zdup || cfg, "vd_distill_mid: the duplicated state is the guided teacher's input (cfg = 1)");
     const long long N = (long long)C * HW;
     DistillMidArgs p = {zt, out, coef, teacher_type, cfg ? 1 : 0, clip ? 1 : 0, xhat, dhat, zmid, zdup, n, N};
@@ -1478,11 +1488,9 @@ extern "C" int vd_distill_loss_fwd(const float* xhat, const float* dhat, const f
                                    const float* student_out, const float* coef, int32_t teacher_type, int32_t student_type, int32_t cfg,
                                    int32_t clip, float* loss, float* resid, float* xtilde, int32_t n, int32_t C, int32_t HW,
                                    void* stream) {
-    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3 && student_type >= 0 && student_type <= 3,
-               "vd_distill_loss_fwd: bad model_out_type (%d,%d)", teacher_type, student_type);
-    VD_REQUIRE(dhat && zmid && teacher_out && zt && student_out && coef && loss && resid && (xhat || !xtilde),
-               "vd_distill_loss_fwd: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_fwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_given("vd_distill_loss_fwd", teacher_type, true));
+    VD_TRY(args_checks("vd_distill_loss_fwd", student_type,
+                       dhat && zmid && teacher_out && zt && student_out && coef && loss && resid && (xhat || !xtilde), n, C, HW));
     const long long N = (long long)C * HW;
     DistillLossArgs p = {xhat, dhat, zmid, teacher_out, zt, student_out, coef, teacher_type, student_type, cfg ? 1 : 0, clip ? 1 : 0, n, N};
     launch_rows(distill_loss_fwd_kernel<4>, distill_loss_fwd_kernel<1>,
@@ -1493,9 +1501,7 @@ extern "C" int vd_distill_loss_fwd(const float* xhat, const float* dhat, const f
 
 extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const float* gloss, int32_t student_type, float* dout,
                                    int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(student_type >= 0 && student_type <= 3, "vd_distill_loss_bwd: bad model_out_type %d", student_type);
-    VD_REQUIRE(resid && coef && gloss && dout, "vd_distill_loss_bwd: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_distill_loss_bwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_distill_loss_bwd", student_type, resid && coef && gloss && dout, n, C, HW));
     const long long N = (long long)C * HW;
     launch_elems(distill_loss_bwd_kernel<4>, distill_loss_bwd_kernel<1>, N % 4 == 0 && all_aligned16(resid, dout), n * N, stream, resid, coef,
                  gloss, (int)student_type, dout, (int)n, N);
@@ -1505,9 +1511,7 @@ extern "C" int vd_distill_loss_bwd(const float* resid, const float* coef, const 
 
 extern "C" int vd_consist_mid(const float* zt, const float* out, const float* coef, int32_t teacher_type, int32_t cfg, int32_t clip,
                               float* zs, float* dz, float* xhat, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(teacher_type >= 0 && teacher_type <= 3, "vd_consist_mid: bad model_out_type %d", teacher_type);
-    VD_REQUIRE(zt && out && coef && zs && dz, "vd_consist_mid: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_mid: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_consist_mid", teacher_type, zt && out && coef && zs && dz, n, C, HW));
     const long long N = (long long)C * HW;
     ConsistMidArgs p = {zt, out, coef, teacher_type, cfg ? 1 : 0, clip ? 1 : 0, zs, dz, xhat, n, N};
     launch_elems(consist_mid_kernel<4>, consist_mid_kernel<1>, N % 4 == 0 && all_aligned16(zt, out, zs, dz, xhat), n * N, stream, p);
@@ -1517,8 +1521,7 @@ extern "C" int vd_consist_mid(const float* zt, const float* out, const float* co
 
 extern "C" int vd_consist_pair(const float* x0, const float* eps, const float* coef, float* zt, float* zs, float* dz, int32_t n,
                                int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(x0 && eps && coef && zt && zs && dz, "vd_consist_pair: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_pair: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_consist_pair", OUT_V, x0 && eps && coef && zt && zs && dz, n, C, HW));          // (no output type here)
     const long long N = (long long)C * HW;
     launch_elems(consist_pair_kernel<4>, consist_pair_kernel<1>, N % 4 == 0 && all_aligned16(x0, eps, zt, zs, dz), n * N, stream, x0, eps,
                  coef, zt, zs, dz, (int)n, N);
@@ -1529,10 +1532,8 @@ extern "C" int vd_consist_pair(const float* x0, const float* eps, const float* c
 extern "C" int vd_consist_loss_fwd(const float* zt, const float* zs, const float* dz, const float* student_out, const float* target_out,
                                    const float* coef, int32_t out_type, int32_t metric, double huber_c, float* loss, float* resid,
                                    float* aux, float* target, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(out_type >= 0 && out_type <= 3, "vd_consist_loss_fwd: bad model_out_type %d", out_type);
     VD_REQUIRE(metric == 0 || (metric == 1 && huber_c > 0.0), "vd_consist_loss_fwd: metric must be 0 (l2) or 1 (huber, c > 0)");
-    VD_REQUIRE(zt && zs && dz && student_out && target_out && coef && loss && resid && aux, "vd_consist_loss_fwd: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_loss_fwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_consist_loss_fwd", out_type, zt && zs && dz && student_out && target_out && coef && loss && resid && aux, n, C, HW));
     const long long N = (long long)C * HW;
     ConsistLossArgs p = {zt, zs, dz, student_out, target_out, coef, out_type, metric, huber_c, n, N};
     launch_rows(consist_loss_fwd_kernel<4>, consist_loss_fwd_kernel<1>,
@@ -1543,9 +1544,7 @@ extern "C" int vd_consist_loss_fwd(const float* zt, const float* zs, const float
 
 extern "C" int vd_consist_loss_bwd(const float* resid, const float* coef, const float* gloss, const float* aux, int32_t out_type,
                                    float* dout, int32_t n, int32_t C, int32_t HW, void* stream) {
-    VD_REQUIRE(out_type >= 0 && out_type <= 3, "vd_consist_loss_bwd: bad model_out_type %d", out_type);
-    VD_REQUIRE(resid && coef && gloss && aux && dout, "vd_consist_loss_bwd: null pointer");
-    VD_REQUIRE(n > 0 && C > 0 && HW > 0, "vd_consist_loss_bwd: empty batch or image (n=%d, C=%d, HW=%d)", n, C, HW);
+    VD_TRY(args_checks("vd_consist_loss_bwd", out_type, resid && coef && gloss && aux && dout, n, C, HW));
     const long long N = (long long)C * HW;
     launch_elems(consist_loss_bwd_kernel<4>, consist_loss_bwd_kernel<1>, N % 4 == 0 && all_aligned16(resid, dout), n * N, stream, resid, coef,
                  gloss, aux, (int)out_type, dout, (int)n, N);
