@@ -35,6 +35,7 @@
 //     memory (36 linear DMA pieces) and a lane's fragment for both 16-channel blocks
 //     and both k-steps is one conflict-free ds_read_b128.
 #include "common.h"
+#include "../../include/vdiff_hip_dgrad_planes.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -828,10 +829,8 @@ __global__ __launch_bounds__(384) void wino43_wgrad_reduce_finish_kernel(const f
 //   y   = A^T M A + bias (+ res) and the GroupNorm partial sums (kernel below), A^T the dyadic one of the fused epilogue.
 // ==================================================================================================================
 // plane-major forward image U[xi][co][ci] = (G w[co][ci] G^T)[xi]: the values of pack43_tile(fwd = 1) as the ROW-kind B operand
-__global__ __launch_bounds__(256) void wino43_pack_planes_kernel(const float* w, float* U, int Cout, int Cin) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, plane = (long long)Cout * Cin;
-    if (idx >= plane) return;
-    const float* src = w + idx * 9;
+// (pack43_planes: the 36 values of one (co, ci) kernel at dst, dst + plane, ...)
+__device__ __forceinline__ void pack43_planes(const float* src, float* dst, long long plane) {
     const double Gd[6][3] = {{64.0 / 81, 0.0, 0.0}, {-128.0 / 243, -32.0 / 81, -8.0 / 27}, {-128.0 / 243, 32.0 / 81, -8.0 / 27},
                              {32.0 / 243, 16.0 / 81, 8.0 / 27}, {32.0 / 243, -16.0 / 81, 8.0 / 27}, {0.0, 0.0, 1.0}};
     double g[3][3], tmp[6][3];
@@ -846,7 +845,22 @@ __global__ __launch_bounds__(256) void wino43_pack_planes_kernel(const float* w,
 #pragma unroll
     for (int a = 0; a < 6; ++a)
 #pragma unroll
-        for (int b = 0; b < 6; ++b) U[(6 * a + b) * plane + idx] = (float)(tmp[a][0] * Gd[b][0] + tmp[a][1] * Gd[b][1] + tmp[a][2] * Gd[b][2]);
+        for (int b = 0; b < 6; ++b) dst[(6 * a + b) * plane] = (float)(tmp[a][0] * Gd[b][0] + tmp[a][1] * Gd[b][1] + tmp[a][2] * Gd[b][2]);
+}
+
+__global__ __launch_bounds__(256) void wino43_pack_planes_kernel(const float* w, float* U, int Cout, int Cin) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, plane = (long long)Cout * Cin;
+    if (idx >= plane) return;
+    pack43_planes(w + idx * 9, U + idx, plane);
+}
+
+// the same image transposed, Ut[xi][ci][co]: the ROW-kind B operand of the input gradient's plane GEMMs (N = Cin, K = Cout); threads walk
+// the OUTPUT order, so the 36 stores of a wavefront stay contiguous
+__global__ __launch_bounds__(256) void wino43_pack_planes_t_kernel(const float* w, float* Ut, int Cout, int Cin) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x, plane = (long long)Cout * Cin;
+    if (idx >= plane) return;
+    const long long ci = idx / Cout, co = idx - ci * Cout;
+    pack43_planes(w + (co * Cin + ci) * 9, Ut + idx, plane);
 }
 
 // A^T of {0, +-3/4, +-3/2, inf}, 4 x 6: [1 1 1 1 1 0 ; 0 3/4 -3/4 3/2 -3/2 0 ; 0 9/16 9/16 9/4 9/4 0 ; 0 27/64 -27/64 27/8 -27/8 1]
@@ -923,6 +937,103 @@ __global__ __launch_bounds__(256) void wino43_out_transform_kernel(const Out43 p
             p.stats[((long long)blockIdx.x * 2 + st) * p.Cout + blockIdx.y * 64 + ch] = v;
         }
     }
+}
+
+// ==================================================================================================================
+// INPUT GRADIENT through planes (round 9): the exact adjoint of the forward above with respect to x,
+//   dM = A dY A^T      the image the weight gradient's transform pass writes every step (wino43_wgrad_transform_kernel, z = 1 half),
+//   dV[xi] = dM[xi] Ut[xi]    36 ROW/ROW GEMMs, rows = tiles, K = Cout, N = Cin, plane-major [36][T][Cin],
+//   dx = overlap-add of the 6x6 patches B dV_tile B^T at stride 4 (kernel below), B = the transpose of bt6's matrix.
+// dY is read and transformed ONCE per step for both gradients; no rotated kernel image is needed.
+// ==================================================================================================================
+// o = B v: o[q] = sum_b B^T[b][q] v[b] (the columns of bt6's matrix)
+__device__ __forceinline__ void b6(const f32x4 (&v)[6], f32x4 (&o)[6]) {
+    const f32x4 p12 = v[1] + v[2], q12 = v[2] - v[1], p34 = v[3] + v[4], q34 = v[4] - v[3];
+    o[0] = 1.265625f * v[0];
+    o[1] = 1.6875f * q12 + 0.84375f * q34 + 1.265625f * v[5];
+    o[2] = -2.8125f * v[0] - 2.25f * p12 - 0.5625f * p34;
+    o[3] = -0.75f * q12 - 1.5f * q34 - 2.8125f * v[5];
+    o[4] = v[0] + p12 + p34;
+    o[5] = v[5];
+}
+
+struct In43 {
+    const float* dV; long long plane;          // [36][T][Cin], plane = T * Cin
+    float* dx; long long lddx;
+    int Cin;
+};
+
+// HBM-bound: a workgroup owns ONE image x a channel slice -- thread (tile, quad), 256 / (TW * TW) quads of 4 channels: 16 channels of a
+// 32x32 image, 64 of a 16x16 one; grid (channel slices, images).  Patch row / column 0 of a tile lands on the last pixel row / column
+// of its upper / left neighbour, 5 on the first of its lower / right one: those 20 ring values travel through LDS in two phases, at
+// most 12 per thread at a time.
+//   phase 1 (along the rows): R[a][.] = B dV[a][.]; R[a][0] and R[a][5] go to LDS; S[a][c] = R[a][c + 1], then S[a][0] += the left
+//           neighbour's R[a][5], S[a][3] += the right neighbour's R[a][0]
+//   phase 2 (along the columns): P[.][c] = B S[.][c]; P[0][c] and P[5][c] go to LDS; pixel (u, c) = P[u + 1][c], then row 0 += the upper
+//           neighbour's P[5][c], row 3 += the lower neighbour's P[0][c] (which carry the diagonal tiles' share from phase 1)
+// Every sum has this one order: bitwise reproducible, no atomics, every dx[..., :Cin] written once, every dV element loaded once.  A
+// neighbour outside the image is the padding: its share is dropped.
+template <int TW>
+__global__ __launch_bounds__(256) void wino43_in_transpose_kernel(const In43 p) {
+    constexpr int TPI = TW * TW, NQ = 256 / TPI;
+    __shared__ f32x4 ring[12][256];
+    const int tid = threadIdx.x, q = tid % NQ, tile = tid / NQ;
+    const int ty = tile / TW, tx = tile - ty * TW;
+    const int c4 = ((int)blockIdx.x * NQ + q) * 4;
+    const bool in = c4 < p.Cin;                 // (a thread past Cin owns nothing, exports nothing, and nobody reads its ring slots: the
+    f32x4 S[6][4];                              //  neighbours of a quad are the SAME quad of other tiles)
+    if (in) {
+        const float* vp = p.dV + ((long long)blockIdx.y * TPI + tile) * p.Cin + c4;
+#pragma unroll
+        for (int a = 0; a < 6; ++a) {
+            f32x4 v[6], r[6];
+#pragma unroll
+            for (int b = 0; b < 6; ++b) v[b] = *reinterpret_cast<const f32x4*>(vp + (long long)(6 * a + b) * p.plane);
+            b6(v, r);
+            ring[a][tid] = r[0]; ring[6 + a][tid] = r[5];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) S[a][c] = r[c + 1];
+        }
+    }
+    __syncthreads();
+    if (in) {
+        if (tx > 0) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a) S[a][0] += ring[6 + a][tid - NQ];
+        }
+        if (tx < TW - 1) {
+#pragma unroll
+            for (int a = 0; a < 6; ++a) S[a][3] += ring[a][tid + NQ];
+        }
+    }
+    __syncthreads();                            // (phase 2 reuses the ring)
+    f32x4 P[4][4];
+    if (in) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+            const f32x4 col[6] = {S[0][c], S[1][c], S[2][c], S[3][c], S[4][c], S[5][c]};
+            f32x4 o[6];
+            b6(col, o);
+            ring[c][tid] = o[0]; ring[4 + c][tid] = o[5];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) P[u][c] = o[u + 1];
+        }
+    }
+    __syncthreads();
+    if (!in) return;
+    if (ty > 0) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) P[0][c] += ring[4 + c][tid - TW * NQ];
+    }
+    if (ty < TW - 1) {
+#pragma unroll
+        for (int c = 0; c < 4; ++c) P[3][c] += ring[c][tid + TW * NQ];
+    }
+    float* xp = p.dx + (((long long)blockIdx.y * (4 * TW) + 4 * ty) * (4 * TW) + 4 * tx) * p.lddx + c4;
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+        for (int c = 0; c < 4; ++c) *reinterpret_cast<f32x4*>(xp + (long long)(u * 4 * TW + c) * p.lddx) = P[u][c];
 }
 
 struct Wg43Plan { bool ok; int T, S; size_t v_f, m_f, u_f, cs_f, gemm_bytes; };
@@ -1124,11 +1235,13 @@ extern "C" size_t vd_conv3x3_wgrad_wino43_ws_bytes(int32_t nimg, int32_t H, int3
  * reduction of wide layers: FUSED_FINISH_MIN); 7 = all */
 static int wgrad43_impl(const float* xin, int64_t ldx, const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cin,
                         int32_t Cout, float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws,
-                        size_t ws_bytes, void* stream, int phases, const float* Vgiven = nullptr) {
+                        size_t ws_bytes, void* stream, int phases, const float* Vgiven = nullptr, const float* dMgiven = nullptr) {
     // Vgiven: the V image of xin that vd_conv3x3_wino43_fwd_planes left behind ([T/16][36][16][Cin], the same kernel's output): the
     // transform pass then runs its dY half alone and xin is not read
-    VD_REQUIRE((xin || Vgiven) && dy && dw_oihw && ws, "vd_conv3x3_wgrad_wino43: null operand");
-    VD_REQUIRE(!Vgiven || vd_aligned16(Vgiven), "vd_conv3x3_wgrad_wino43: V must be 16-byte aligned");
+    // dMgiven (with Vgiven): the image of dy that vd_conv3x3_wino43_dy_image wrote -- no transform pass at all, dy is not read
+    VD_REQUIRE((xin || Vgiven) && (dy || dMgiven) && dw_oihw && ws, "vd_conv3x3_wgrad_wino43: null operand");
+    VD_REQUIRE(!dMgiven || (Vgiven && !(phases & 1)), "vd_conv3x3_wgrad_wino43: a given dM needs a given V and runs no transform pass");
+    VD_REQUIRE((!Vgiven || vd_aligned16(Vgiven)) && (!dMgiven || vd_aligned16(dMgiven)), "vd_conv3x3_wgrad_wino43: V / dM must be 16-byte aligned");
     VD_REQUIRE(vd_conv3x3_wgrad_wino43_supported(nimg, H, W, Cin, Cout, ldx, lddy),
                "vd_conv3x3_wgrad_wino43: unsupported geometry nimg=%d H=%d W=%d Cin=%d Cout=%d", nimg, H, W, Cin, Cout);
     VD_REQUIRE(Cin_w <= Cin && Cout_w <= Cout, "vd_conv3x3_wgrad_wino43: real dims exceed padded dims");
@@ -1153,7 +1266,7 @@ static int wgrad43_impl(const float* xin, int64_t ldx, const float* dy, int64_t 
     if (phases & 2) {
         const float* A[36]; const float* B[36]; float* C[36]; float* colsum[36];
         for (int e = 0; e < 36; ++e) {
-            A[e] = dM + (size_t)e * 16 * Cout; B[e] = V + (size_t)e * 16 * Cin;
+            A[e] = (dMgiven ? dMgiven : dM) + (size_t)e * 16 * Cout; B[e] = V + (size_t)e * 16 * Cin;
             C[e] = dU + (size_t)e * Cout * Cin; colsum[e] = cs + (size_t)e * Cout;
         }
         const int rc = vd_gemm_grouped_wgrad_kblk(A, B, C, colsum, 36, Cout, Cin, g.T, Cout, Cin, Cin, g.S, gws, g.gemm_bytes, stream,
@@ -1283,6 +1396,113 @@ extern "C" int vd_conv3x3_wino43_fwd_planes(const float* xin, int64_t ldx, const
         o.CT = vd_conv3x3_wino43_fwd_chunk_rows(H, W) / 16;
         hipLaunchKernelGGL(wino43_out_transform_kernel, dim3((unsigned)(T / o.CT), (unsigned)((Cout + 63) / 64)), dim3(16, 16), 0, st, o);
         VD_LAUNCH_CHECK("wino43_out_transform_kernel");
+    }
+    return 0;
+}
+
+/* ---- dM = A dY A^T, the weight gradient's image of dy, into a caller's buffer ([T/16][36][16][Cout], vd_conv3x3_wino43_dm_floats floats):
+ * the transform pass's dY half alone -- the same device code and bits the weight gradient's own pass writes into its workspace.  Both
+ * gradients of a convolution read it: vd_conv3x3_wgrad_wino43_vm and vd_conv3x3_wino43_dgrad_planes. */
+extern "C" size_t vd_conv3x3_wino43_dm_floats(int32_t nimg, int32_t H, int32_t W, int32_t Cout) {
+    const size_t T = (size_t)nimg * (H / 4) * (W / 4);
+    return (size_t)36 * ((T + 15) / 16 * 16) * Cout;
+}
+
+extern "C" int vd_conv3x3_wino43_dy_image(const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cout, float* dM,
+                                          void* stream) {
+    VD_REQUIRE(dy && dM, "vd_conv3x3_wino43_dy_image: null operand");
+    VD_REQUIRE(nimg > 0 && H >= 4 && W >= 4 && H % 4 == 0 && W % 4 == 0 && Cout > 0 && Cout % 4 == 0 && lddy % 4 == 0 && lddy >= Cout,
+               "vd_conv3x3_wino43_dy_image: unsupported geometry nimg=%d H=%d W=%d Cout=%d", nimg, H, W, Cout);
+    VD_REQUIRE(vd_aligned16(dy) && vd_aligned16(dM), "vd_conv3x3_wino43_dy_image: operands must be 16-byte aligned");
+    const long long TPI = (long long)(H / 4) * (W / 4), T = nimg * TPI;
+    VD_REQUIRE(T % 4 == 0 && T < (1LL << 31) && (long long)nimg * H * W * lddy < 0x7FFFFFF0LL / 4 && T * Cout * 4 < (1LL << 40),
+               "vd_conv3x3_wino43_dy_image: tile count or tensor size out of range");
+    WgT43 t = {};
+    t.dy = dy; t.lddy = lddy; t.dM = dM;
+    t.nimg = nimg; t.H = H; t.W = W; t.Cin = Cout; t.Cout = Cout; t.TW = W / 4; t.TPI = (int)TPI; t.T = (int)T;
+    t.z0 = 1;
+    hipLaunchKernelGGL(wino43_wgrad_transform_kernel, dim3((unsigned)(T / 4), (unsigned)((Cout + 255) / 256), 1), dim3(64, 4), 0,
+                       (hipStream_t)stream, t);
+    VD_LAUNCH_CHECK("wino43_wgrad_transform_kernel(dM)");
+    return 0;
+}
+
+/* the weight gradient with BOTH images given (V from vd_conv3x3_wino43_fwd_planes, dM from vd_conv3x3_wino43_dy_image): the 36 grouped GEMMs
+ * and the fold alone; bitwise the result of vd_conv3x3_wgrad_wino43_v on the dy that dM was made from.  phase: 7 = both, or 2 / 4. */
+extern "C" int vd_conv3x3_wgrad_wino43_vm(const float* V, const float* dM, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                                          float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws,
+                                          size_t ws_bytes, int32_t phase, void* stream) {
+    VD_REQUIRE(V && dM, "vd_conv3x3_wgrad_wino43_vm: null V or dM");
+    VD_REQUIRE(phase == 7 || phase == 2 || phase == 4, "vd_conv3x3_wgrad_wino43_vm: phase must be 7, 2 or 4");
+    return wgrad43_impl(nullptr, Cin, nullptr, Cout, nimg, H, W, Cin, Cout, dw_oihw, dbias, Cin_w, Cout_w, accumulate, ws, ws_bytes, stream,
+                        phase & 6, V, dM);
+}
+
+/* ---- INPUT GRADIENT through planes: dx[nimg][H][W][:Cin] = d/dx of conv3x3(x, w) for the output gradient whose image dM is given
+ * (vd_conv3x3_wino43_dy_image): pack of Ut = (G w G^T) transposed -> 36 plane GEMMs dV = dM Ut on the split-operand tile engine ->
+ * overlap-add pass (wino43_in_transpose_kernel).  32x32 and 16x16 images (a band of a 64-wide image would need its neighbours' tile
+ * rows), Cin, Cout multiples of 4, dx rows 16-byte aligned; channels >= Cin of a pitched dx are left alone. */
+extern "C" int vd_conv3x3_wino43_dgrad_planes_supported(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int64_t lddx) {
+    if (nimg <= 0 || nimg > 65535 || Cin <= 0 || Cout <= 0 || Cin % 4 || Cout % 4 || lddx % 4 || lddx < Cin) return 0;
+    if (!((W == 32 && H == 32) || (W == 16 && H == 16))) return 0;
+    const long long T = (long long)nimg * (H / 4) * (W / 4);
+    if (T >= (1LL << 22) || 36LL * 16 * Cout * 16 + 16LL * Cout + 256 >= 0x70000000LL / 4) return 0;     // (row tiles of the GEMM, its block pitch)
+    if (128LL * Cin + 128 >= 0x70000000LL / 4 || 128LL * Cout + 128 >= 0x70000000LL / 4) return 0;
+    return 1;
+}
+
+extern "C" size_t vd_conv3x3_wino43_dgrad_planes_ws_bytes(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout) {
+    const size_t T = (size_t)nimg * (H / 4) * (W / 4);
+    return ((size_t)36 * Cout * Cin + (size_t)36 * T * Cin) * sizeof(float);
+}
+
+/* occupancy and measurement rule: 1 where GEMMs + overlap-add beat the fused F(4x4,3x3) input-gradient kernel GIVEN dM, i.e. in a training
+ * step whose weight gradient takes dM too.  The floor of the forward's rule (VD_PLANES_MIN_TILES tiles), Cin a multiple of 256 (N of the
+ * 128 x 256 tile), Cout a multiple of 16 (its K tile).  Same-box measurement (profiles/r09_dgrad_planes_geometries.txt, ms, fused vs planes,
+ * settled clock): K 256 -> N 256 @32x32 B = 128 0.390 vs 0.368, K 256 -> N 512 0.817 vs 0.720; @32x32 B = 64 (4096 tiles) 0.192 vs 0.194 and
+ * 0.376 vs 0.369: a tie.  (@16x16 B = 128 0.099 vs 0.092 and 0.190 vs 0.167, but those forwards keep no V: the caller's condition.) */
+extern "C" int vd_conv3x3_dgrad_planes_preferred(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t training) {
+    if (!training || !vd_conv3x3_wino43_dgrad_planes_supported(nimg, H, W, Cin, Cout, Cin)) return 0;
+    static const long long floor_t = getenv("VD_PLANES_MIN_TILES") ? atoll(getenv("VD_PLANES_MIN_TILES")) : VD_PLANES_MIN_TILES;
+    const long long T = (long long)nimg * (H / 4) * (W / 4);
+    return T >= floor_t && Cin % 256 == 0 && Cout % 16 == 0;
+}
+
+extern "C" int vd_conv3x3_wino43_dgrad_planes(const float* dM, const float* w_oihw, float* dx, int64_t lddx, int32_t nimg, int32_t H, int32_t W,
+                                              int32_t Cin, int32_t Cout, float* ws, size_t ws_bytes, int32_t phase, void* stream) {
+    VD_REQUIRE(dM && w_oihw && dx && ws, "vd_conv3x3_wino43_dgrad_planes: null operand");
+    VD_REQUIRE(vd_conv3x3_wino43_dgrad_planes_supported(nimg, H, W, Cin, Cout, lddx),
+               "vd_conv3x3_wino43_dgrad_planes: unsupported geometry nimg=%d H=%d W=%d Cin=%d Cout=%d", nimg, H, W, Cin, Cout);
+    VD_REQUIRE(vd_aligned16(dM) && vd_aligned16(dx) && vd_aligned16(ws), "vd_conv3x3_wino43_dgrad_planes: operands must be 16-byte aligned");
+    VD_REQUIRE(ws_bytes >= vd_conv3x3_wino43_dgrad_planes_ws_bytes(nimg, H, W, Cin, Cout), "vd_conv3x3_wino43_dgrad_planes: workspace too small");
+    VD_REQUIRE(phase == 7 || phase == 1 || phase == 2 || phase == 4, "vd_conv3x3_wino43_dgrad_planes: phase must be 7, 1, 2 or 4");
+    const int TPI = (H / 4) * (W / 4), T = nimg * TPI;
+    float* Ut = ws;
+    float* dV = ws + (size_t)36 * Cout * Cin;
+    hipStream_t st = (hipStream_t)stream;
+    if (phase & 1) {
+        const long long plane = (long long)Cout * Cin;
+        hipLaunchKernelGGL(wino43_pack_planes_t_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, st, w_oihw, Ut, Cout, Cin);
+        VD_LAUNCH_CHECK("wino43_pack_planes_t_kernel");
+    }
+    if (phase & 2) {
+        vd_gemm_desc d = {};
+        d.A = dM; d.B = Ut; d.C = dV;
+        d.M = T; d.N = Cin; d.K = Cout; d.a_kind = VD_ROW; d.b_kind = VD_ROW;
+        d.lda = Cout; d.ldb = Cout; d.ldc = Cin;
+        d.batch = 36; d.nh = 1; d.alpha = 1.f;
+        d.sAb = 16LL * Cout; d.sBb = (long long)Cout * Cin; d.sCb = (long long)T * Cin;
+        const int rc = vd_gemm_rowblk(&d, 36LL * 16 * Cout, stream);
+        if (rc) return rc;
+    }
+    if (phase & 4) {
+        In43 o = {};
+        o.dV = dV; o.plane = (long long)T * Cin; o.dx = dx; o.lddx = lddx; o.Cin = Cin;
+        if (W == 32)
+            hipLaunchKernelGGL(wino43_in_transpose_kernel<8>, dim3((unsigned)((Cin + 15) / 16), (unsigned)nimg), dim3(256), 0, st, o);
+        else
+            hipLaunchKernelGGL(wino43_in_transpose_kernel<4>, dim3((unsigned)((Cin + 63) / 64), (unsigned)nimg), dim3(256), 0, st, o);
+        VD_LAUNCH_CHECK("wino43_in_transpose_kernel");
     }
     return 0;
 }

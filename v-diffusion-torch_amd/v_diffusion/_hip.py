@@ -73,10 +73,11 @@ def _ctypes_of(name, ret, params):
     return _RETURNS[ret], [arg(q) for q in params]
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} not found: the ctypes binding is read from the C header of the source tree")
-    with open(HEADER_PATH) as f:
+def _header_signatures(path=None):
+    path = path or HEADER_PATH
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes binding is read from the C headers of the source tree")
+    with open(path) as f:
         tables = _parse_header(f.read())
     return [{name: _ctypes_of(name, *decl) for name, decl in t.items()} for t in tables]
 
@@ -86,6 +87,10 @@ def _header_signatures():
 # library
 _SIGNATURES, PROBE_EXPORTS = _header_signatures()
 EXPORTS = tuple(_SIGNATURES)
+# headers that extend vdiff_hip.h, each with a fixture of its own: their entry points are bound like EXPORTS
+EXT_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dgrad_planes.h"),)
+_EXT_SIGNATURES = {name: sig for path in EXT_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
+EXT_EXPORTS = tuple(_EXT_SIGNATURES)
 
 _lib = None
 
@@ -99,7 +104,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES}.items():
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():
@@ -465,6 +470,68 @@ def conv3x3_wino43_fwd_planes(x, ldx, w, bias, y, ldy, nimg, H, W, Cin, Cout, re
         phase(2)
     _note_bytes(PROFILE[-1][0], 4.0 * 36.0 * (T * (Cin + Cout) + Cout * Cin))
     with _TimedBytes("wino43_out_transform_kernel", 4.0 * (36.0 * T * Cout + nimg * H * W * Cout * (2 if res is not None else 1))):
+        phase(4)
+
+
+# input gradients through PLANES (csrc/wino43.hip: dM = A dY A^T, the image the weight gradient makes of dy anyway -> 36 plane GEMMs on the
+# split-operand tile engine -> overlap-add pass) in training steps whose forward kept V: dy is transformed once for both gradients.
+# DGRAD_PLANES (VD_DGRAD_PLANES): "0" never, "1" where vd_conv3x3_dgrad_planes_preferred says it beats the fused kernel, "2" wherever supported
+DGRAD_PLANES = os.environ.get("VD_DGRAD_PLANES", "1")
+
+
+def dgrad_planes_supported(nimg, H, W, Cin, Cout, lddy, lddx):
+    """does the input gradient of this Cin -> Cout call (dy at pitch lddy, dx at pitch lddx) go through planes, GIVEN that its forward kept V?
+    The F(4x4,3x3) weight gradient, the other reader of dM, must serve the geometry too."""
+    if DGRAD_PLANES == "0" or not (WINO and WINO43):
+        return False
+    if lddy % 4 or not lib().vd_conv3x3_wino43_dgrad_planes_supported(nimg, H, W, Cin, Cout, lddx):
+        return False
+    if not wgrad43_supported(nimg, H, W, Cin, Cout, Cin, lddy):
+        return False
+    return DGRAD_PLANES == "2" or bool(lib().vd_conv3x3_dgrad_planes_preferred(nimg, H, W, Cin, Cout, 1))
+
+
+def conv3x3_wino43_dy_image(dy, lddy, nimg, H, W, Cout, dm):
+    """dm = A dY A^T (vd_conv3x3_wino43_dy_image): the image of dy both gradients of a planes layer read"""
+    assert dm.numel() >= lib().vd_conv3x3_wino43_dm_floats(nimg, H, W, Cout)
+    with _TimedBytes("wino43_wgrad_transform_kernel", 4.0 * nimg * H * W * Cout * (1 + 2.25)):
+        _check(lib().vd_conv3x3_wino43_dy_image(ptr(dy), lddy, nimg, H, W, Cout, ptr(dm), stream()), "vd_conv3x3_wino43_dy_image")
+
+
+def conv3x3_wgrad_wino43_vm(v, dm, nimg, H, W, Cin, Cout, dw, Cin_w, Cout_w, accumulate=False, dbias=None):
+    """F(4x4,3x3) weight gradient with both images given (vd_conv3x3_wgrad_wino43_vm): the 36 grouped GEMMs and the fold alone"""
+    assert v.numel() == lib().vd_conv3x3_wino43_v_floats(nimg, H, W, Cin) and dm.numel() >= lib().vd_conv3x3_wino43_dm_floats(nimg, H, W, Cout)
+    ws = workspace(lib().vd_conv3x3_wgrad_wino43_ws_bytes(nimg, H, W, Cin, Cout), dm.device, "wgrad43")
+    args = (ptr(v), ptr(dm), nimg, H, W, Cin, Cout, ptr(dw), ptr(dbias), Cin_w, Cout_w, int(accumulate), ws.data_ptr(), ws.numel() * 4)
+    phase = lambda ph: _check(lib().vd_conv3x3_wgrad_wino43_vm(*args, ph, stream()), "vd_conv3x3_wgrad_wino43_vm")
+    if PROFILE is None:
+        phase(7)
+        return
+    with _TimedTile("gemm_dma_kernel<{tile}, 1, 1, true, {kt}, true> " + W43_WGRAD_TAG, 2.0 * nimg * H * W * Cout * 9 * Cin):
+        phase(2)
+    _note_bytes(PROFILE[-1][0], 4.0 * (36.0 * nimg * (H // 4) * (W // 4) * (Cin + Cout) + 36.0 * Cout * Cin))
+    with _TimedName("wino43_wgrad_finish_kernel", 0.0):
+        phase(4)
+
+
+def conv3x3_wino43_dgrad_planes(dm, w, dx, lddx, nimg, H, W, Cin, Cout):
+    """dx = input gradient of the Cin -> Cout 3x3 convolution through planes (vd_conv3x3_wino43_dgrad_planes); ``dm``: the image of dy from
+    conv3x3_wino43_dy_image, ``w``: the raw [Cout][Cin][3][3] kernel"""
+    assert dm.numel() >= lib().vd_conv3x3_wino43_dm_floats(nimg, H, W, Cout) and w.is_contiguous() and tuple(w.shape) == (Cout, Cin, 3, 3)
+    ws = workspace(lib().vd_conv3x3_wino43_dgrad_planes_ws_bytes(nimg, H, W, Cin, Cout), dm.device, "dgrad_planes")
+    args = (ptr(dm), ptr(w), ptr(dx), lddx, nimg, H, W, Cin, Cout, ws.data_ptr(), ws.numel() * 4)
+    phase = lambda ph: _check(lib().vd_conv3x3_wino43_dgrad_planes(*args, ph, stream()), "vd_conv3x3_wino43_dgrad_planes")
+    if PROFILE is None:
+        phase(7)
+        return
+    T = nimg * (H // 4) * (W // 4)
+    with _TimedBytes("wino43_pack_planes_t_kernel", 4.0 * (9 + 36) * Cout * Cin):
+        phase(1)
+    # the 36 planes as ONE batched launch of the tile engine, under that instantiation's name with the work it EXECUTES
+    with _TimedTile("gemm_dma_kernel<{tile}, 0, 0, false, {kt}>", 2.0 * 36 * T * Cout * Cin):
+        phase(2)
+    _note_bytes(PROFILE[-1][0], 4.0 * 36.0 * (T * (Cin + Cout) + Cout * Cin))
+    with _TimedBytes("wino43_in_transpose_kernel", 4.0 * (36.0 * T * Cin + nimg * H * W * Cin)):
         phase(4)
 
 

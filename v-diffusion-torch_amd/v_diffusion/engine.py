@@ -348,6 +348,26 @@ class UNetEngine:
         with torch.cuda.stream(side):
             H.conv3x3_wgrad(x, ldx, dy, lddy, *args, **kw)
 
+    def _conv_bwd_planes(self, w, v, dy, lddy, dx, lddx, B, Hh, Ww, Cin, Cout, gw, gb):
+        """Both gradients of a Cin -> Cout convolution whose forward kept V, from ONE image of dy: the main stream writes dM = A dY A^T, the
+        side stream runs the weight gradient on (V, dM), the main stream goes on with the input gradient through planes (dM -> dx).  False
+        (nothing launched): no V, or the rule / this call's pitches decline -- the caller takes the fused kernels as before."""
+        if v is None or not H.dgrad_planes_supported(B, Hh, Ww, Cin, Cout, lddy, lddx):
+            return False
+        dm = torch.empty(H.lib().vd_conv3x3_wino43_dm_floats(B, Hh, Ww, Cout), dtype=torch.float32, device=dy.device)
+        H.conv3x3_wino43_dy_image(dy, lddy, B, Hh, Ww, Cout, dm)
+        side = self._side
+        if side is None:
+            H.conv3x3_wgrad_wino43_vm(v, dm, B, Hh, Ww, Cin, Cout, gw, Cin, Cout, dbias=gb)
+        else:
+            side.wait_stream(torch.cuda.current_stream())
+            v.record_stream(side)
+            dm.record_stream(side)
+            with torch.cuda.stream(side):
+                H.conv3x3_wgrad_wino43_vm(v, dm, B, Hh, Ww, Cin, Cout, gw, Cin, Cout, dbias=gb)
+        H.conv3x3_wino43_dgrad_planes(dm, w, dx, lddx, B, Hh, Ww, Cin, Cout)
+        return True
+
     def _side_join(self):
         if self._side is not None:
             torch.cuda.current_stream().wait_stream(self._side)
@@ -692,9 +712,10 @@ class UNetEngine:
         _, Ho, Wo, Cout, lddy = _chk(dy)
         rs = blk.rs
         # conv2
-        self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"], v=ctx["v2"])
         da2 = self._new(x, B, Ho, Wo, Cout)
-        self._conv(dy, lddy, mod.conv2.weight, None, da2, Cout, B, Ho, Wo, Cout, Cout, dgrad=True)
+        if not self._conv_bwd_planes(mod.conv2.weight, ctx["v2"], dy, lddy, da2, Cout, B, Ho, Wo, Cout, Cout, g["conv2.weight"], g["conv2.bias"]):
+            self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"], v=ctx["v2"])
+            self._conv(dy, lddy, mod.conv2.weight, None, da2, Cout, B, Ho, Wo, Cout, Cout, dgrad=True)
         # norm2 + FiLM + SiLU + dropout
         dh1 = self._new(x, B, Ho, Wo, Cout)
         c2, fi = blk.film
@@ -704,9 +725,10 @@ class UNetEngine:
                        pgb_keep=self._pgb(B, Cout, g["norm2.weight"], g["norm2.bias"]))
         del da2
         # conv1
-        self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"], v=ctx["v1"])
         da1 = self._new(x, B, Ho, Wo, Cin)
-        self._conv(dh1, Cout, mod.conv1.weight, None, da1, Cin, B, Ho, Wo, Cout, Cin, dgrad=True)
+        if not self._conv_bwd_planes(mod.conv1.weight, ctx["v1"], dh1, Cout, da1, Cin, B, Ho, Wo, Cin, Cout, g["conv1.weight"], g["conv1.bias"]):
+            self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"], v=ctx["v1"])
+            self._conv(dh1, Cout, mod.conv1.weight, None, da1, Cin, B, Ho, Wo, Cout, Cin, dgrad=True)
         del dh1
         # skip path
         if Cin != Cout:
