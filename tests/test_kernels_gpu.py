@@ -1245,6 +1245,9 @@ WGRAD43_CASES = [  # nimg, H, W, Cin, Cout, Cin_w, Cout_w, ldx_extra, lddy_extra
     # >= 384 x 384 weights per plane: the fold kernel sums the split-K slabs itself (wino43_wgrad_reduce_finish_kernel) -- accumulate mode,
     # real dims below the padded ones on both sides, row pitches above the channel counts
     (32, 16, 16, 384, 388, 381, 386, 8, 4), (8, 32, 32, 512, 384, 512, 384, 0, 0),
+    # T % 16 != 0: V / dM are stored in blocks of 16 tiles and the last block is written in part (8x8 images at a batch that is no multiple of
+    # four; 12x12 images).  T = 516 (4 rows of the last block), 520 (8: T16 = 528 ends a K tile of 32 on half a tile), 524 (12), 540 (12)
+    (129, 8, 8, 32, 32, 32, 32, 0, 0), (130, 8, 8, 64, 96, 64, 96, 0, 0), (131, 8, 8, 32, 64, 32, 64, 0, 0), (60, 12, 12, 48, 36, 48, 36, 0, 0),
 ]
 
 
