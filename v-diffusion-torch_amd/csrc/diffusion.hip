@@ -6,10 +6,12 @@
 //   learned variances (bound terms, hybrid loss, reverse step for outputs with variance channels)  the intent of diffusion.py:320-324
 // Without a counterpart in the reference: progressive distillation; consistency distillation / training and the batched
 // target-network update; the DPM-Solver++(2M) reverse step, its dynamically thresholded form and the UniPC step; the RePaint
-// masked reverse step and the forward jump; the noise-map extraction of DDPM inversion; spherical interpolation.
+// masked reverse step and the forward jump; the noise-map extraction of DDPM inversion; spherical interpolation; the residual and
+// the corrected reverse step of Diffusion Posterior Sampling.
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 // Device side first, then the host helpers (launch, coefficient carrier, the refusals every entry shares), then the C entries.
 #include "common.h"
+#include "../../include/vdiff_hip_dps.h"
 
 namespace {
 
@@ -532,10 +534,11 @@ __device__ __forceinline__ float axpby(float a, float x, float b, float y) {
 // per branch: the x0 prediction a0*z + b0x*o (+ b0e*o_eps), clipped to [-1, 1] when asked
 struct PredX0 {
     float a0, b0x, b0e; bool both, clip;
-    __device__ __forceinline__ float operator()(float z, float o, float oe) const {
-        const float x0h = x0_hat(a0, b0x, b0e, both, z, o, oe);
-        return clip ? fminf(fmaxf(x0h, -1.f), 1.f) : x0h;
-    }
+    __device__ __forceinline__ float raw(float z, float o, float oe) const { return x0_hat(a0, b0x, b0e, both, z, o, oe); }
+    __device__ __forceinline__ float clipped(float x0h) const { return clip ? fminf(fmaxf(x0h, -1.f), 1.f) : x0h; }
+    __device__ __forceinline__ float operator()(float z, float o, float oe) const { return clipped(raw(z, o, oe)); }
+    // 1 where the clip passes the gradient on: no clip, or -1 <= x0h <= 1 (torch.clamp's subgradient, boundary included; a NaN passes none)
+    __device__ __forceinline__ float pass(float x0h) const { return (!clip || (x0h >= -1.f && x0h <= 1.f)) ? 1.f : 0.f; }
 };
 
 // per branch: the step mean c1*z + c2*x0_hat + c3*o in one of its two groupings, or x0_hat itself on the last step
@@ -1274,6 +1277,166 @@ __global__ __launch_bounds__(SLERP_THREADS) void slerp_rows_kernel(const float* 
     }
 }
 
+// ---- Diffusion Posterior Sampling (Chung et al. 2023, Algorithm 1): every reverse step is followed by a gradient step on the
+// measurement residual ||meas - A g(xt)||, g the guided (clipped) x0 prediction of the step.  Two launches around the network's input
+// gradient.  dps_residual_kernel: r = meas - A g, sumsq[b] = sum r^2, and the cotangents of (1/2)||r||^2 with u = -A^T r and m the
+// pass mask of the clip (PredX0::pass) -- unnormalised, the network's VJP is linear:
+//   dout cond row (1 + w) m_c u, uncond row -w m_u u (without guidance m u), times b0x, and times b0e on the second half of "both";
+//   dxt = a0 [(1 + w) m_c - w m_u] u (a0 m u): the path that does not go through the network;   x0hat (optional) = g.
+// A: op 0 = M (.) g, the mask of par = 1 or C channels; op 1 = the mean over par x par blocks; op 2 = the mean over the channels.
+// ONE WORKGROUP OWNS ONE SAMPLE and a thread one measurement element with its preimage (1, par^2 or C elements; the preimages tile the
+// image, so every element of dout and dxt is written once): nothing but the sum crosses threads.  Each thread adds its r^2 in fp64 in
+// element order, block_sum adds lanes and waves in a fixed order: no atomics, no workspace, the same bits on every call.
+enum { DPS_MASK = 0, DPS_DOWN = 1, DPS_GRAY = 2 };
+
+struct DpsResArgs {
+    const float* xt; const float* out; const float* meas; const float* mask; Coefs c; int type, cfg, clip, op, par;
+    float* dout; float* dxt; float* sumsq; float* x0hat; int C, H, W;
+};
+
+__device__ __forceinline__ float dps_apply(int op, float m, float sum, float cnt) {      // (A g) of one measurement element
+#pragma clang fp contract(off)
+    return op == DPS_MASK ? m * sum : sum / cnt;
+}
+
+__device__ __forceinline__ float dps_adjoint(int op, float m, float r, float cnt) {      // u = -(A^T r) of each element of its preimage
+#pragma clang fp contract(off)
+    return op == DPS_MASK ? -(m * r) : -(r / cnt);
+}
+
+struct DpsCot { float c, u, z; };      // the factors of u in the cond row, the uncond row and dxt
+
+__device__ __forceinline__ DpsCot dps_cot(bool cfg, float w, float a0, float mc, float mu) {
+#pragma clang fp contract(off)
+    if (!cfg) return {mc, 0.f, a0 * mc};
+    const float fc = (1.f + w) * mc, fu = -w * mu;
+    return {fc, fu, a0 * (fc + fu)};
+}
+
+__device__ __forceinline__ float dps_mul(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
+__global__ __launch_bounds__(256) void dps_residual_kernel(const DpsResArgs p) {
+    __shared__ double sh[4];
+    const long long b = blockIdx.x, HW = (long long)p.H * p.W, N = p.C * HW;
+    const float* k = p.c.k;
+    const bool both = p.type == OUT_BOTH, cfg = p.cfg != 0;
+    const PredX0 x0 = {k[0], k[1], k[2], both, p.clip != 0};
+    const float a0 = k[0], b0x = k[1], b0e = k[2], w = k[6];
+    const long long row = (both ? 2 : 1) * N;
+    const float* zb = p.xt + b * N;
+    const float* oc = p.out + b * (1 + p.cfg) * row;
+    const float* ou = oc + row;
+    float* dc = p.dout + b * (1 + p.cfg) * row;
+    float* du = dc + row;
+    const int op = p.op, f = op == DPS_DOWN ? p.par : 1, Wo = p.W / f, Ho = p.H / f;
+    const int cnt = op == DPS_MASK ? 1 : (op == DPS_DOWN ? f * f : p.C);
+    const long long M = op == DPS_MASK ? N : (op == DPS_DOWN ? (long long)p.C * Ho * Wo : HW);      // measurement elements of a sample
+    // index in [0, N) of element q of the preimage of measurement element j
+    auto elem = [&](long long j, int q) -> long long {
+        if (op == DPS_MASK) return j;
+        if (op == DPS_GRAY) return q * HW + j;
+        const long long c = j / ((long long)Ho * Wo), r = j % ((long long)Ho * Wo), yo = r / Wo, xo = r % Wo;
+        return c * HW + (yo * f + q / f) * p.W + xo * f + q % f;
+    };
+    // the guided prediction of element i and the pass masks of its two branches
+    auto pred = [&](long long i, float& mc, float& mu) -> float {
+        const float z = zb[i];
+        const float pc = x0.raw(z, oc[i], both ? oc[N + i] : 0.f);
+        mc = x0.pass(pc); mu = 0.f;
+        float g = x0.clipped(pc);
+        if (cfg) {
+            const float pu = x0.raw(z, ou[i], both ? ou[N + i] : 0.f);
+            mu = x0.pass(pu);
+            g = guide(w, g, x0.clipped(pu));
+        }
+        return g;
+    };
+    double acc = 0.0;
+    for (long long j = threadIdx.x; j < M; j += blockDim.x) {
+        // (the up to 64 predictions of a preimage are added in fp64 and rounded once: r is a difference of two numbers of one size, and a
+        // running fp32 sum's error would be most of it)
+        double sum = 0.0;
+        float g = 0.f, mc = 0.f, mu = 0.f;
+        for (int q = 0; q < cnt; ++q) { g = pred(elem(j, q), mc, mu); sum += (double)g; }
+        const float m = op == DPS_MASK ? p.mask[b * p.par * HW + (p.par == 1 ? j % HW : j)] : 1.f;
+        const float r = p.meas[b * M + j] - dps_apply(op, m, (float)sum, (float)cnt);
+        acc += (double)r * (double)r;
+        const float u = dps_adjoint(op, m, r, (float)cnt);
+        for (int q = 0; q < cnt; ++q) {
+            const long long i = elem(j, q);
+            if (cnt > 1) g = pred(i, mc, mu);
+            const DpsCot t = dps_cot(cfg, w, a0, mc, mu);
+            const float cc = dps_mul(t.c, u);
+            dc[i] = dps_mul(cc, b0x);
+            if (both) dc[N + i] = dps_mul(cc, b0e);
+            if (cfg) {
+                const float cu = dps_mul(t.u, u);
+                du[i] = dps_mul(cu, b0x);
+                if (both) du[N + i] = dps_mul(cu, b0e);
+            }
+            p.dxt[b * N + i] = dps_mul(t.z, u);
+            if (p.x0hat) p.x0hat[b * N + i] = g;
+        }
+    }
+    acc = block_sum(acc, sh);
+    if (threadIdx.x == 0) p.sumsq[b] = (float)acc;
+}
+
+// dps_step_kernel: sample_step_kernel's row -- the same helpers: prediction, clip, guided mean_plain, last step, noise -- and then
+//   xn -= zeta / sqrt(sumsq[b]) * (dxt[b] + dxin[2b] + dxin[2b+1])      (dxt[b] + dxin[b] without guidance)
+// with dxin the network's input gradient of dps_residual_kernel's dout: the gradient of ||r|| itself, scaled by zeta.  The term is
+// SELECTED: with zeta = 0 or sumsq[b] = 0 the row is sample_step_kernel's bit for bit and its dxin / dxt are never read; a sumsq[b]
+// that is not finite makes that row NaN and no other.  Each thread reads all it needs of its V elements before it writes them, so xn
+// may alias xt.
+struct DpsStepArgs { StepCommon s; const float* noise; const float* dxin; const float* dxt; const float* sumsq; float zeta; };
+
+__device__ __forceinline__ float dps_scale(float zeta, float ss) {
+#pragma clang fp contract(off)
+    return __builtin_isfinite(ss) ? zeta * (1.f / sqrtf(ss)) : __builtin_nanf("");     // (a negative ss: NaN from the root)
+}
+
+__device__ __forceinline__ float dps_correct(float v, float sc, float dz, float dc, float du, bool cfg) {
+#pragma clang fp contract(off)
+    const float d = cfg ? (dz + dc) + du : dz + dc;
+    return __builtin_fmaf(-sc, d, v);
+}
+
+template <int V>
+__global__ void dps_step_kernel(const DpsStepArgs p) {
+    const StepCommon& s = p.s;
+    const long long N = s.N, total = (long long)s.n * N / V;
+    const float* k = coefs(s.c);
+    const StepMean<false> f = step_mean<false>(s, k);
+    const float k5 = k[5], w = k[6];
+    for (long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (long long)gridDim.x * blockDim.x) {
+        const long long e = idx * V, b = e / N, i = e % N;
+        float z[V], v[V];
+        ldv<V>(s.xt + e, z);
+        guided<V>(s, b, i, w, z, f, v);
+        if (p.noise) {
+            float nz[V];
+            ldv<V>(p.noise + e, nz);
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = axpby(1.f, v[j], k5, nz[j]);
+        }
+        const float ss = p.sumsq[b];
+        if (p.zeta != 0.f && ss != 0.f) {
+            const float sc = dps_scale(p.zeta, ss);
+            const float* dn = p.dxin + b * (1 + s.cfg) * N + i;
+            float dz[V], dc[V], du[V] = {};
+            ldv<V>(p.dxt + e, dz);
+            ldv<V>(dn, dc);
+            if (s.cfg) ldv<V>(dn + N, du);
+#pragma unroll
+            for (int j = 0; j < V; ++j) v[j] = dps_correct(v[j], sc, dz[j], dc[j], du[j], s.cfg != 0);
+        }
+        st_dup<V>(s.xn, s.xdup, b, N, i, v);
+    }
+}
+
 // ---- host side of the entries below
 template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
 
@@ -1674,5 +1837,36 @@ extern "C" int vd_slerp_rows(const float* a, const float* b, const float* frac, 
     launch_rows(slerp_rows_kernel<4>, slerp_rows_kernel<1>, N % 4 == 0 && all_aligned16(a, b, out), n, SLERP_THREADS, stream, a, b, frac_dev, f,
                 out, w_out, (long long)N);
     VD_LAUNCH_CHECK("slerp_rows_kernel");
+    return 0;
+}
+
+// (include/vdiff_hip_dps.h.  No device-resident coefficients: the chain has no captured-graph form)
+extern "C" int vd_dps_residual(const float* xt, const float* out, const float* meas, const float* mask, const float* k, int32_t type,
+                               int32_t cfg, int32_t clip, int32_t op, int32_t par, float* dout, float* dxt, float* sumsq, float* x0hat,
+                               int32_t n, int32_t C, int32_t H, int32_t W, void* stream) {
+    DpsResArgs p = {xt, out, meas, mask, {}, type, cfg ? 1 : 0, clip ? 1 : 0, op, par, dout, dxt, sumsq, x0hat, C, H, W};
+    VD_REQUIRE(k != nullptr, "vd_dps_residual: null pointer");
+    VD_TRY(set_coefs("vd_dps_residual", p.c, k, nullptr, 8));
+    VD_REQUIRE(op >= DPS_MASK && op <= DPS_GRAY, "vd_dps_residual: bad op %d", op);
+    VD_TRY(args_given("vd_dps_residual", type, xt && out && meas && dout && dxt && sumsq && (op != DPS_MASK || mask)));
+    VD_REQUIRE(n > 0 && C > 0 && H > 0 && W > 0, "vd_dps_residual: empty batch or image (n=%d, C=%d, H=%d, W=%d)", n, C, H, W);
+    VD_REQUIRE(op != DPS_MASK || par == 1 || par == C, "vd_dps_residual: the mask has 1 or C = %d channels, got %d", C, par);
+    VD_REQUIRE(op != DPS_DOWN || ((par == 2 || par == 4 || par == 8) && H % par == 0 && W % par == 0),
+               "vd_dps_residual: down-sampling by %d of a %d x %d image (the factor is 2, 4 or 8 and divides both sides)", par, H, W);
+    hipLaunchKernelGGL(dps_residual_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("dps_residual_kernel");
+    return 0;
+}
+
+extern "C" int vd_dps_step(const float* xt, const float* out, const float* noise, const float* dxin, const float* dxt, const float* sumsq,
+                           const float* k, float zeta, int32_t type, int32_t cfg, int32_t last_step, int32_t clip, float* xn, float* xdup,
+                           int32_t n, int32_t C, int32_t HW, void* stream) {
+    DpsStepArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, HW), noise, dxin, dxt, sumsq, zeta};
+    VD_REQUIRE(k != nullptr, "vd_dps_step: null pointer");
+    VD_TRY(step_checks("vd_dps_step", p.s, k, nullptr, 8, xt && out && dxin && dxt && sumsq && xn, C, HW));
+    VD_REQUIRE(noise != nullptr || k[5] == 0.f, "vd_dps_step: noise required when the noise scale is non-zero");
+    launch_elems(dps_step_kernel<4>, dps_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, dxin, dxt, xn, xdup), n * p.s.N, stream,
+                 p);
+    VD_LAUNCH_CHECK("dps_step_kernel");
     return 0;
 }

@@ -9,7 +9,8 @@ The three hot-path names are implemented here, and progressive distillation on t
 timestep resampling (``LossSecondMomentResampler``: v_diffusion/resample.py, likewise) and the UniPC predictor-corrector sampler
 (``GaussianDiffusion.p_sample_unipc``, ``unipc_coefs``: v_diffusion/unipc.py, likewise) and consistency distillation / training with
 multistep consistency sampling (``ConsistencyDiffusion``, ``GaussianDiffusion.p_sample_consistency``, ``consistency_coefs``,
-``consistency_sample_coefs``, ``consistency_schedule``: v_diffusion/consistency.py, likewise).  The other nine names the reference package re-exports (data loading,
+``consistency_sample_coefs``, ``consistency_schedule``: v_diffusion/consistency.py, likewise) and Diffusion Posterior Sampling
+(``GaussianDiffusion.p_sample_dps``, ``dps_measure``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input gradient).  The other nine names the reference package re-exports (data loading,
 config helpers, its Trainer / Evaluator: control plane, out of scope) are NOT re-implemented: when the environment
 variable ``VDIFF_REFERENCE_ROOT`` points at a checkout of the reference they are resolved lazily from it (loaded under
 the alias ``v_diffusion_ref`` so its relative imports stay inside the reference), which lets the reference's
@@ -22,6 +23,7 @@ import sys
 from .consistency import ConsistencyDiffusion, consistency_coefs, consistency_sample_coefs, consistency_schedule
 from .diffusion import GaussianDiffusion, get_logsnr_schedule
 from .distill import DistillationDiffusion, distill_coefs
+from .dps import dps_measure, p_sample_dps
 from .inpaint import jump_coefs, known_coefs, resampling_schedule
 from .invert import encode_coefs, slerp
 from .models.unet import UNet
@@ -31,7 +33,8 @@ from .unipc import p_sample_unipc, unipc_coefs
 
 _HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusion", "distill_coefs", "solver_coefs", "threshold_rank",
         "dynamic_threshold", "resampling_schedule", "known_coefs", "jump_coefs", "encode_coefs", "slerp", "LossSecondMomentResampler",
-        "unipc_coefs", "p_sample_unipc", "ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule"]
+        "unipc_coefs", "p_sample_unipc", "ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule",
+        "dps_measure", "p_sample_dps"]
 _DELEGATED = ["get_dataloader", "DATA_INFO", "dict2str", "seed_all", "update_config", "fill_with_defaults", "Trainer",
               "Evaluator", "DummyScheduler"]
 _ref_pkg = None

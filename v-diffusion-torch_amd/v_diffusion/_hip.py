@@ -91,6 +91,11 @@ EXPORTS = tuple(_SIGNATURES)
 EXT_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dgrad_planes.h"),)
 _EXT_SIGNATURES = {name: sig for path in EXT_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
 EXT_EXPORTS = tuple(_EXT_SIGNATURES)
+# (EXT_HEADER_PATHS / EXT_EXPORTS are held to the planes header's fixture as they stand -- tests/test_dgrad_planes_cpu.py -- so a further
+# extension header is listed beside them: vdiff_hip_dps.h, pinned by tests/golden/c_abi_dps.json)
+DPS_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dps.h"),)
+_DPS_SIGNATURES = {name: sig for path in DPS_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
+DPS_EXPORTS = tuple(_DPS_SIGNATURES)
 
 _lib = None
 
@@ -104,7 +109,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_DPS_SIGNATURES}.items():
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():
@@ -1005,6 +1010,26 @@ def slerp_rows(a, b, frac, out, w_out, n, N, frac_dev=None):
     device tensor of n floats; w_out optional, n x 2 floats"""
     arr = _host_floats(None if frac is None else [frac], 1)
     _check(lib().vd_slerp_rows(ptr(a), ptr(b), arr, ptr(frac_dev), ptr(out), ptr(w_out), n, int(N), stream()), "vd_slerp_rows")
+
+
+DPS_OPS = {"mask": 0, "down": 1, "gray": 2}
+
+
+def dps_residual(xt, out, meas, mask, k8, mot, cfg, clip, op, par, dout, dxt, sumsq, x0hat, n, Cc, H, W):
+    """r = meas - A g of the guided x0 prediction g, sumsq[b] = sum r^2 and the cotangents of (1/2)||r||^2: dout (the shape of out) for the
+    network's VJP, dxt for the direct path (vd_dps_residual).  op: DPS_OPS; par = the mask's channel count (1 or C) / the down-sampling
+    factor / unused; mask only for op 0; x0hat (optional) receives g.  k8: sample_step's 8 host floats"""
+    arr = _host_floats(k8, 8)
+    _check(lib().vd_dps_residual(ptr(xt), ptr(out), ptr(meas), ptr(mask), arr, mot, int(cfg), int(clip), int(op), int(par), ptr(dout),
+                                 ptr(dxt), ptr(sumsq), ptr(x0hat), n, Cc, H, W, stream()), "vd_dps_residual")
+
+
+def dps_step(xt, out, noise, dxin, dxt, sumsq, k8, zeta, mot, cfg, last, clip, xn, xdup, n, Cc, HW):
+    """sample_step, then xn -= zeta / sqrt(sumsq[b]) * (dxt[b] + the rows of dxin of sample b); the term is selected: zeta = 0 or
+    sumsq[b] = 0 leaves sample_step's row (vd_dps_step).  xn may alias xt"""
+    arr = _host_floats(k8, 8)
+    _check(lib().vd_dps_step(ptr(xt), ptr(out), ptr(noise), ptr(dxin), ptr(dxt), ptr(sumsq), arr, float(zeta), mot, int(cfg), int(last),
+                             int(clip), ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_dps_step")
 
 
 def lsm_draw(hist, count, u, cdf, t_out, idx_out, w_out, T, K, B, uniform_prob):

@@ -903,6 +903,26 @@ class GaussianDiffusion:
         return p_sample_inpaint(self, denoise_fn, known, mask, label, device, seed, use_ddim, jump_length, resamplings, start,
                                 clip_denoised).cpu()
 
+    def p_sample_dps(self, denoise_fn, measurement, operator, shape, label=None, device=None, seed=None, zeta=1.0, use_ddim=False,
+                     clip_denoised=True):
+        """Reverse chain conditioned on a measurement y = A x (+ noise) by Diffusion Posterior Sampling (extension, v_diffusion/dps.py;
+        Chung et al. 2023, Algorithm 1): training-free restoration with an existing checkpoint.  ``operator`` names A: ``("mask", mask)``
+        -- soft or noisy inpainting, ``mask`` as in ``p_sample_inpaint`` (1 = measured) -- ``("down", f)`` -- box down-sampling by f in
+        {2, 4, 8}, super-resolution -- or ``("gray",)`` -- the channel mean, colourisation.  ``measurement`` is A's image of ``shape`` =
+        (B, C, H, W) on the GPU (``v_diffusion.dps_measure(x, operator)`` makes one).  Every step is the ordinary posterior step (DDPM, or
+        DDIM with ``use_ddim``) followed by x <- x - zeta * grad_{x_t} ||y - A x0_hat(x_t)||, x0_hat the step's guided, clipped
+        prediction: one network call with tape, one launch for the residual and its cotangents (vd_dps_residual), the network's input
+        gradient with the weights held fixed -- ``UNet.forward_vjp`` for a ``v_diffusion.UNet`` (also behind ``.module``), without
+        autograd and without any weight-gradient work; ``torch.autograd.grad`` for any other callable, which is why this method is not
+        wrapped in ``inference_mode`` -- and one launch for the step (vd_dps_step).  The last step is corrected too.  ``zeta``: a float, or
+        ``sample_timesteps`` floats indexed by the grid index a step lands on; a step with zeta 0 takes no gradient, and ``zeta=0`` is
+        ``p_sample(seed=..., use_ddim=...)`` bit for bit.  Draws, from one generator seeded with ``seed``: x_T, then one per step
+        (``p_sample``'s order).  Refused before any launch: ``model_var_type="learned"``, ``x0eps_coef=True``, an unknown operator, a
+        factor outside {2, 4, 8} or not dividing H and W, a measurement of another shape, a negative or non-finite zeta or a zeta list
+        of the wrong length, CPU tensors.  Returns the result ON THE GPU."""
+        from .dps import p_sample_dps
+        return p_sample_dps(self, denoise_fn, measurement, operator, shape, label, device, seed, zeta, use_ddim, clip_denoised)
+
     @torch.inference_mode()
     def p_invert_noise(self, denoise_fn, x_0, label=None, device=None, seed=None, start=None, clip_denoised=True):
         """DDPM noise-space inversion of a given image batch (extension, v_diffusion/invert.py; Huberman-Spiegelglas et al. 2024):

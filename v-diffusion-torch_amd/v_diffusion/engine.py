@@ -161,6 +161,16 @@ class _Pack(collections.namedtuple("_Pack", "uf ud u43 u43f wf wd", defaults=(No
 _NO_PACK = _Pack()            # a kernel ConvPacks does not hold (in / out convolution, nothing packed yet)
 
 
+class _NoGrads(dict):
+    """the gradient set of the input-only backward pass (``backward(tape, dout, None, need_dx=True)``): every parameter's gradient
+    tensor is None, and whoever would fill it launches nothing"""
+    def __missing__(self, key):
+        return None
+
+
+_NO_GRADS = _NoGrads()
+
+
 class ConvPacks:
     """Everything that belongs to the packed images of ONE weight set's residual-block 3x3 kernels at one (need_d, geometry): the
     persistent buffers (``bufs``), the per-layer views into them (``layers``: id(weight) -> _Pack), the device tables of the batched pack
@@ -351,13 +361,16 @@ class UNetEngine:
     def _conv_bwd_planes(self, w, v, dy, lddy, dx, lddx, B, Hh, Ww, Cin, Cout, gw, gb):
         """Both gradients of a Cin -> Cout convolution whose forward kept V, from ONE image of dy: the main stream writes dM = A dY A^T, the
         side stream runs the weight gradient on (V, dM), the main stream goes on with the input gradient through planes (dM -> dx).  False
-        (nothing launched): no V, or the rule / this call's pitches decline -- the caller takes the fused kernels as before."""
+        (nothing launched): no V, or the rule / this call's pitches decline -- the caller takes the fused kernels as before.  ``gw`` None
+        (the input-only pass): the weight-gradient half is not launched; dM and the input gradient are those of the full pass."""
         if v is None or not H.dgrad_planes_supported(B, Hh, Ww, Cin, Cout, lddy, lddx):
             return False
         dm = torch.empty(H.lib().vd_conv3x3_wino43_dm_floats(B, Hh, Ww, Cout), dtype=torch.float32, device=dy.device)
         H.conv3x3_wino43_dy_image(dy, lddy, B, Hh, Ww, Cout, dm)
         side = self._side
-        if side is None:
+        if gw is None:
+            pass
+        elif side is None:
             H.conv3x3_wgrad_wino43_vm(v, dm, B, Hh, Ww, Cin, Cout, gw, Cin, Cout, dbias=gb)
         else:
             side.wait_stream(torch.cuda.current_stream())
@@ -416,8 +429,11 @@ class UNetEngine:
         self._pgb_rows, self._pgb_off, self._pgb_blk = [], 0, 0
 
     def _pgb(self, B, C, dgamma, dbeta):
+        """the slice of the arena a norm's backward leaves its per-image terms in; ``dgamma`` None (the input-only pass): the slice is
+        scratch that nothing sums"""
         sl = self._pgb_arena[self._pgb_off: self._pgb_off + B * 2 * C]
-        self._pgb_rows.append([sl.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, C, 0, 0, self._pgb_blk])
+        if dgamma is not None:
+            self._pgb_rows.append([sl.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), B, C, 0, 0, self._pgb_blk])
         self._pgb_off += B * 2 * C
         self._pgb_blk += (C + 15) // 16
         return sl
@@ -535,10 +551,15 @@ class UNetEngine:
         p = self._layer(w)
         if p.wd is not None:
             return p.wd
+        cache, key = self._fixed, ("wd", id(w))              # (a chain that takes input gradients packs the input convolution's once)
+        if cache is not None and key in cache:
+            return cache[key]
         co, ci = w.shape[0], w.shape[1]
         cout_p = cout_p or co
         wd = self._new(w, ci, 9, cout_p)
         H.pack_conv3x3(w, co, ci, wd=wd, Cout_p=cout_p)
+        if cache is not None:
+            cache[key] = wd
         return wd
 
     def _pack_thin(self, w, rows):
@@ -705,8 +726,10 @@ class UNetEngine:
         return out_parts
 
     def _res_bwd(self, blk, ctx, dy, dx, dx_accumulate, ta, dfilms, G):
+        """``G`` None: the input-only pass -- the dx chain's launches with their arguments, none of the weight-gradient ones"""
         mod = blk.res
-        g = {s: G[name] for s, name in blk.res_names.items()}          # this block's gradient tensors by parameter-name suffix
+        only_dx = G is None
+        g = _NO_GRADS if only_dx else {s: G[name] for s, name in blk.res_names.items()}      # this block's gradient tensors by parameter-name suffix
         x, a1, h1, a2, film = ctx["x"], ctx["a1"], ctx["h1"], ctx["a2"], ctx["film"]
         B, Hh, Ww, Cin, ldx = _chk(x)
         _, Ho, Wo, Cout, lddy = _chk(dy)
@@ -714,12 +737,13 @@ class UNetEngine:
         # conv2
         da2 = self._new(x, B, Ho, Wo, Cout)
         if not self._conv_bwd_planes(mod.conv2.weight, ctx["v2"], dy, lddy, da2, Cout, B, Ho, Wo, Cout, Cout, g["conv2.weight"], g["conv2.bias"]):
-            self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"], v=ctx["v2"])
+            if not only_dx:
+                self._cwgrad(a2, Cout, dy, lddy, B, Ho, Wo, Cout, Cout, g["conv2.weight"], Cout, Cout, dbias=g["conv2.bias"], v=ctx["v2"])
             self._conv(dy, lddy, mod.conv2.weight, None, da2, Cout, B, Ho, Wo, Cout, Cout, dgrad=True)
         # norm2 + FiLM + SiLU + dropout
         dh1 = self._new(x, B, Ho, Wo, Cout)
         c2, fi = blk.film
-        dfilm = dfilms[c2][fi]
+        dfilm = dfilms[c2][0 if only_dx else fi]          # (input-only: one scratch slot per width, never summed)
         H.gn_apply_bwd(da2, Cout, h1, Cout, ctx["coef2"], mod.norm2.weight, mod.norm2.bias, film, 1, ctx["p"], ctx["seed"],
                        H.RS_NONE, None, 0, dh1, Cout, False, dfilm, None, None, False, B, Ho, Wo, Cout, GROUPS,
                        pgb_keep=self._pgb(B, Cout, g["norm2.weight"], g["norm2.bias"]))
@@ -727,7 +751,8 @@ class UNetEngine:
         # conv1
         da1 = self._new(x, B, Ho, Wo, Cin)
         if not self._conv_bwd_planes(mod.conv1.weight, ctx["v1"], dh1, Cout, da1, Cin, B, Ho, Wo, Cin, Cout, g["conv1.weight"], g["conv1.bias"]):
-            self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"], v=ctx["v1"])
+            if not only_dx:
+                self._cwgrad(a1, Cin, dh1, Cout, B, Ho, Wo, Cin, Cout, g["conv1.weight"], Cin, Cout, dbias=g["conv1.bias"], v=ctx["v1"])
             self._conv(dh1, Cout, mod.conv1.weight, None, da1, Cin, B, Ho, Wo, Cout, Cin, dgrad=True)
         del dh1
         # skip path
@@ -735,7 +760,8 @@ class UNetEngine:
             xs = ctx["xs"]
             P = B * Ho * Wo
             w = mod.skip.weight
-            self._wgrad(dy, xs, g["skip.weight"], g["skip.bias"], Cout, Cin, P, lddy, _ld(xs), Cin)
+            if not only_dx:
+                self._wgrad(dy, xs, g["skip.weight"], g["skip.bias"], Cout, Cin, P, lddy, _ld(xs), Cin)
             dsk = self._new(x, B, Ho, Wo, Cin)
             H.gemm(dy, w, dsk, P, Cin, Cout, a_kind=H.ROW, b_kind=H.COL, lda=lddy, ldb=Cin, ldc=Cin)
         else:
@@ -752,7 +778,8 @@ class UNetEngine:
                        pgb_keep=self._pgb(B, Cin, g["norm1.weight"], g["norm1.bias"]))
         # FiLM projection film = fc(ta): weight/bias gradient here (keeps the gradient-completion order); the embedding
         # gradient of all blocks is one batched GEMM at the end of backward (_film_bwd)
-        self._linear_bwd(ta, mod.fc.weight, dfilm, g["fc.weight"], g["fc.bias"], None)
+        if not only_dx:
+            self._linear_bwd(ta, mod.fc.weight, dfilm, g["fc.weight"], g["fc.bias"], None)
 
     # ------------------------------------------------------------------------------------------ attention block
     def _attn_fwd(self, blk, x, dest, tape, x_parts=None):
@@ -795,7 +822,8 @@ class UNetEngine:
 
     def _attn_bwd(self, blk, ctx, dy, dx, dx_accumulate, G):
         mod = blk.att
-        g = {s: G[name] for s, name in blk.att_names.items()}
+        only_dx = G is None                                   # the input-only pass: see _res_bwd
+        g = _NO_GRADS if only_dx else {s: G[name] for s, name in blk.att_names.items()}
         x, xn, qkv, P, O = ctx["x"], ctx["xn"], ctx["qkv"], ctx["P"], ctx["O"]
         B, Hh, Ww, C, ldx = _chk(x)
         lddy = _ld(dy)
@@ -803,7 +831,8 @@ class UNetEngine:
         hid, ld = nh * hd, 3 * nh * hd
         M = B * L
         # proj_out
-        self._wgrad(dy, O, g["proj_out.weight"], g["proj_out.bias"], C, hid, M, lddy, hid, hid)
+        if not only_dx:
+            self._wgrad(dy, O, g["proj_out.weight"], g["proj_out.bias"], C, hid, M, lddy, hid, hid)
         dO = self._new(x, B, L, hid)
         H.gemm(dy, mod.proj_out.weight, dO, M, hid, C, a_kind=H.ROW, b_kind=H.COL, lda=lddy, ldb=hid, ldc=hid)
         dqkv = self._new(x, B, L, ld)
@@ -827,7 +856,8 @@ class UNetEngine:
             del dP
         del dO
         # proj_in
-        self._wgrad(dqkv, xn, g["proj_in.weight"], g["proj_in.bias"], ld, C, M, ld, C, C)
+        if not only_dx:
+            self._wgrad(dqkv, xn, g["proj_in.weight"], g["proj_in.bias"], ld, C, M, ld, C, C)
         dxn = self._new(x, B, Hh, Ww, C)
         H.gemm(dqkv, mod.proj_in.weight, dxn, M, C, ld, a_kind=H.ROW, b_kind=H.COL, lda=ld, ldb=C, ldc=C)
         # norm (no activation) + the residual branch
@@ -908,8 +938,11 @@ class UNetEngine:
         return out
 
     def _out_conv_bwd(self, o, dout, G):
-        """gradients of the output convolution and its norm; returns the gradient of the last block's output"""
+        """gradients of the output convolution and its norm; returns the gradient of the last block's output.  ``G`` None (the
+        input-only pass): the weight-gradient launches are left out"""
         m = self.m
+        only_dx = G is None
+        G = _NO_GRADS if only_dx else G
         B, H0, W0, cop, _ = _chk(dout)
         gn, conv = m.out_conv[0], m.out_conv[2]
         C0, co, P0 = o["a"].shape[3], m.out_channels, B * H0 * W0
@@ -919,14 +952,16 @@ class UNetEngine:
             nz = wz.shape[0]
             dz = self._new(dout, P0, nz)
             H.tap_spread(dout, cop, dz, nz, B, H0, W0, co)                   # dz[q][co*9+tap] = dout[q - off(tap)][co]
-            gz, cs = self._new(dout, nz, C0), self._new(dout, nz)
-            H.gemm(dz, o["a"], gz, nz, C0, P0, a_kind=H.COL, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0, splitk=_splitk(nz, C0, P0),
-                   colsum=cs)
-            H.thin_wgrad_finish(gz, co, C0, C0, G["out_conv.2.weight"], colsum=cs, cs_stride=9, cs_off=4, dbias=G["out_conv.2.bias"])
+            if not only_dx:
+                gz, cs = self._new(dout, nz, C0), self._new(dout, nz)
+                H.gemm(dz, o["a"], gz, nz, C0, P0, a_kind=H.COL, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0, splitk=_splitk(nz, C0, P0),
+                       colsum=cs)
+                H.thin_wgrad_finish(gz, co, C0, C0, G["out_conv.2.weight"], colsum=cs, cs_stride=9, cs_off=4, dbias=G["out_conv.2.bias"])
             H.gemm(dz, wz, da, P0, C0, nz, a_kind=H.ROW, b_kind=H.COL, lda=nz, ldb=C0, ldc=C0)
             del dz
         else:
-            H.conv3x3_wgrad(o["a"], C0, dout, cop, B, H0, W0, C0, cop, G["out_conv.2.weight"], C0, co, dbias=G["out_conv.2.bias"])
+            if not only_dx:
+                H.conv3x3_wgrad(o["a"], C0, dout, cop, B, H0, W0, C0, cop, G["out_conv.2.weight"], C0, co, dbias=G["out_conv.2.bias"])
             H.conv3x3(dout, cop, self._pack_d(conv.weight, cop), None, da, C0, B, H0, W0, cop, C0)
         dh = self._new(dout, B, H0, W0, C0)
         H.gn_apply_bwd(da, C0, o["h"], _ld(o["h"]), o["coef"], gn.weight, gn.bias, None, 1, 0.0, 0, H.RS_NONE, None, 0, dh, C0,
@@ -943,12 +978,14 @@ class UNetEngine:
         tape = {} if save else None
         x_nchw = x_nchw.to(torch.float32).contiguous()
         fixed = self._fixed
-        if fixed is not None and "packs" in fixed:
+        if fixed is not None and "packs" in fixed and (fixed["packs_d"] or not save):
             self._packs = fixed["packs"]                 # a sampler holds the weights fixed: packed once per chain
         else:
+            # (a chain that takes input gradients -- p_sample_dps -- saves: the first saving forward of the context packs the
+            # input-gradient images too, once, and every later forward uses that set)
             self._pack_all(need_d=save, geom=(B, H0, W0))
             if fixed is not None:
-                fixed["packs"] = self._packs
+                fixed["packs"], fixed["packs_d"] = self._packs, bool(save)
         ta = self._embed_fwd(t, y, tape)
         films = self._film_fwd(ta, tape)
         p_drop = float(m.drop_rate) if training else 0.0
@@ -1000,7 +1037,23 @@ class UNetEngine:
     def backward(self, tape, dout, G, need_dx=False, progress=None):
         """Fills ``G`` (name -> tensor, every entry overwritten) and returns d/dx (NCHW) when asked.  ``progress(name)`` is called whenever
         the gradient of ``name`` and of everything before it in completion_order() is final (gradient-bucket overlap).  The deferred
-        weight-gradient queue and the side stream never outlive the call, whatever it raises (backward_steps' ``finally``)."""
+        weight-gradient queue and the side stream never outlive the call, whatever it raises (backward_steps' ``finally``).
+        ``G`` None with ``need_dx``: the INPUT-ONLY pass, for a network whose weights are held fixed (guidance, posterior sampling, any loss
+        on the prediction).  It runs what d/dx depends on -- the input-gradient convolutions, the GroupNorm and attention backward, the
+        skip-path GEMMs, the resample backward: the launches of the full pass with their arguments, so d/dx is that pass's bit for bit
+        -- and none of the weight-gradient, GroupNorm-parameter, FiLM or embedding work; it opens no side stream and allocates no
+        parameter-shaped tensor.  There is no gradient to report: a ``progress`` listener is refused."""
+        if G is None:
+            self._refuse_no_grads(need_dx, progress is not None)
+            steps = self._backward(tape, dout, None, True, False)
+            try:
+                while True:
+                    next(steps)
+            except StopIteration as fin:
+                return fin.value
+            finally:
+                self._wq = None
+                self._side = None
         steps = self.backward_steps(tape, dout, G, need_dx, join=progress is not None)
         try:
             while True:
@@ -1009,6 +1062,14 @@ class UNetEngine:
                     progress(name)
         except StopIteration as fin:
             return fin.value
+
+    @staticmethod
+    def _refuse_no_grads(need_dx, listening):
+        if not need_dx:
+            raise ValueError("backward without a gradient set (G=None) computes d/dx only: need_dx=True is required")
+        if listening:
+            raise ValueError("backward without a gradient set (G=None) finishes no parameter gradient: there is nothing to report to a "
+                             "progress listener / backward_steps")
 
     def progress_points(self):
         """The names ``backward_steps`` yields, in order (static: a function of the plan): the output convolution, the last block of every
@@ -1049,7 +1110,13 @@ class UNetEngine:
         """Generator form of the backward pass: runs up to the next point at which a prefix of completion_order() is final, yields the
         last finished name (progress_points() lists them), and returns d/dx through StopIteration.  ``join``: a listener consumes the
         gradients at every yield (a gradient reducer, or autograd handing a segment's gradients to DDP's hooks: models/unet.py), so the
-        weight-gradient side stream is joined there; without one it is joined once, at the end."""
+        weight-gradient side stream is joined there; without one it is joined once, at the end.  ``G`` None (the input-only pass of
+        ``backward``) is refused: it has nothing to report."""
+        if G is None:
+            self._refuse_no_grads(need_dx, True)               # (at the call, not at the first next())
+        return self._steps(tape, dout, G, need_dx, join)
+
+    def _steps(self, tape, dout, G, need_dx, join):
         try:
             dx = yield from self._backward(tape, dout, G, need_dx, join)
             return dx
@@ -1058,17 +1125,20 @@ class UNetEngine:
             self._side = None
 
     def _backward(self, tape, dout, G, need_dx=False, join=False):
-        """dout: NHWC ``[B,H,W,Cp]`` gradient of the padded output (padding channels zero)."""
+        """dout: NHWC ``[B,H,W,Cp]`` gradient of the padded output (padding channels zero).  ``G`` None: the input-only pass."""
+        only_dx = G is None
         self._join_at_progress = bool(join)                    # a listener consumes gradients at every yield: finished means finished on every stream
         B = dout.shape[0]
         self._packs = tape["packs"]                            # the images THIS forward packed (another forward may have run since)
         ta = tape["ta"]
-        dta = torch.zeros_like(ta)
-        dfilms = {c2: self._new(ta, len(mods), B, c2) for c2, mods in self.film_groups.items()}
+        dta = None if only_dx else torch.zeros_like(ta)
+        # (input-only: vd_gn_apply_bwd wants a dfilm wherever it is given a film -- one scratch slot per width, as the per-image GroupNorm
+        # parameter terms go to the arena and are never summed)
+        dfilms = {c2: self._new(ta, 1 if only_dx else len(mods), B, c2) for c2, mods in self.film_groups.items()}
         self._pgb_begin(dout, B)
-        self._wq = {}
+        self._wq = None if only_dx else {}
         self._side = None
-        if H.WGRAD_STREAM and H.PROFILE is None:
+        if not only_dx and H.WGRAD_STREAM and H.PROFILE is None:
             if self._side_stream is None or self._side_stream.device != dout.device:
                 self._side_stream = torch.cuda.Stream(device=dout.device)
             self._side = self._side_stream
@@ -1106,6 +1176,8 @@ class UNetEngine:
                 dh_cur = dxbuf
         dy0 = dskip.pop(0)
         assert not dskip
+        if only_dx:
+            return self._in_conv_dgrad(tape["in"], dy0)
         self._in_conv_bwd(tape["in"], dy0, G)
         yield "in_conv.bias"
         dx = self._in_conv_dgrad(tape["in"], dy0) if need_dx else None

@@ -65,7 +65,7 @@ class _UNetFn(torch.autograd.Function):
     def backward(ctx, dout):
         model, tape = ctx.model, ctx.tape
         if tape is None:
-            raise RuntimeError("UNet backward called twice (the tape is freed after the first backward)")
+            raise RuntimeError(_TWICE)
         ctx.tape = None
         eng = model.engine()
         flat = model._flat_grad_views is not None
@@ -84,6 +84,32 @@ class _UNetFn(torch.autograd.Function):
                                               for k, _ in model.named_parameters())
 
 
+_TWICE = "UNet backward called twice (the tape is freed after the first backward)"
+
+
+class _UNetInputFn(torch.autograd.Function):
+    """One autograd node for a network that is held fixed: no parameter requires a gradient and the input does (guidance, posterior
+    sampling, any loss on the prediction of a frozen checkpoint).  Forward runs the engine and keeps its tape; backward is the engine's
+    INPUT-ONLY pass (``UNetEngine.backward(tape, dout, None, need_dx=True)``): none of the weight-gradient work, no gradient slot or flat
+    store touched, and d/dx bit for bit that of the full pass."""
+
+    @staticmethod
+    def forward(ctx, model, x, t, y):
+        with torch.cuda.device(x.device):
+            out, tape = model.engine().forward(x, t, y, model.training, save=True)
+            ctx.model, ctx.tape = model, tape
+            return model._to_nchw(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        model, tape = ctx.model, ctx.tape
+        if tape is None:
+            raise RuntimeError(_TWICE)
+        ctx.tape = None
+        return None, model._input_grad(tape, dout), None, None
+
+
 class _BackwardRun:
     """What one forward shares with its chain of ``_SegFn`` nodes: the tape, then the running backward pass (the engine's generator),
     the gradient tensors not yet handed to autograd, and d/dx."""
@@ -98,7 +124,7 @@ class _BackwardRun:
 
     def start(self, dout):
         if self.tape is None:
-            raise RuntimeError("UNet backward called twice (the tape is freed after the first backward)")
+            raise RuntimeError(_TWICE)
         tape, self.tape = self.tape, None
         self.task_id = torch._C._current_graph_task_id()
         self.gen, self.G, self.no_labels = self.model._chain_begin(self, tape, dout, self.need_dx)
@@ -338,22 +364,65 @@ class UNet(nn.Module):
     # ---- chain of autograd nodes (see _SegFn)
     def _chain_begin(self, run, tape, dout, need_dx):
         eng = self.engine()
-        # the pass in flight is held through a weak reference (round-5 advice): a run whose graph is gone -- backward stopped between nodes
-        # because a hook raised, or autograd.grad over a subset pruned the upstream nodes -- must not be kept alive (its tape is GBs of
-        # activations) nor be run to completion here; a run that still has live nodes (two forwards, one backward) is drained first
-        other = eng._active_run() if eng._active_run is not None else None
-        if other is not None and other is not run and not other.finished:
-            if other.task_id == run.task_id:
-                other.drain()               # two forwards inside ONE backward call: finish the first pass, its remaining nodes find their gradients
-            else:
-                other.stop_early()          # left over from an EARLIER backward call (it raised, or it never reached the pass's last nodes): its
-                                            # nodes can no longer run -- PyTorch keeps a failed call's graph alive until the next call starts
+        self._settle_active_run(run, run.task_id)
         G = self._grad_targets()
         no_labels = bool(self.num_classes) and tape["embed"]["yn"] is None
         gen = eng.backward_steps(tape, self._dout_nhwc(dout), G, need_dx=need_dx, join=True)
         import weakref
         eng._active_run = weakref.ref(run)
         return gen, G, no_labels
+
+    def _settle_active_run(self, run, task_id):
+        """before a backward pass of this engine starts: the engine's queue / side-stream / arena state belongs to one pass at a time"""
+        eng = self.engine()
+        # the pass in flight is held through a weak reference (round-5 advice): a run whose graph is gone -- backward stopped between nodes
+        # because a hook raised, or autograd.grad over a subset pruned the upstream nodes -- must not be kept alive (its tape is GBs of
+        # activations) nor be run to completion here; a run that still has live nodes (two forwards, one backward) is drained first
+        other = eng._active_run() if eng._active_run is not None else None
+        if other is not None and other is not run and not other.finished:
+            if other.task_id == task_id:
+                other.drain()               # two forwards inside ONE backward call: finish the first pass, its remaining nodes find their gradients
+            else:
+                other.stop_early()          # left over from an EARLIER backward call (it raised, or it never reached the pass's last nodes): its
+                                            # nodes can no longer run -- PyTorch keeps a failed call's graph alive until the next call starts
+
+    def _input_grad(self, tape, dout):
+        """d/dx (NCHW fp32) of ``dout`` through the engine's input-only backward pass of ``tape``"""
+        self._settle_active_run(None, torch._C._current_graph_task_id())
+        with torch.no_grad(), torch.cuda.device(dout.device):
+            return self.engine().backward(tape, self._dout_nhwc(dout), None, need_dx=True)
+
+    def forward_vjp(self, x, t, y=None):
+        """``(out, vjp)``: ``out`` is what ``forward(x, t, y)`` returns and ``vjp(dout)`` -- ``dout`` of ``out``'s shape -- returns d/dx of
+        ``x``'s shape, fp32 on the device: the vector-Jacobian product of the network with its weights held fixed, through the engine's
+        input-only backward pass (``UNetEngine.backward`` with ``G=None``).  No autograd: it works under ``no_grad`` and ``inference_mode``
+        and touches no ``.grad``, no gradient slot and no flat store.  ``vjp`` runs once -- the tape is freed on the first call, a second
+        raises.  ``self.training`` is honoured (dropout as the module is set)."""
+        if not x.is_cuda:
+            raise RuntimeError("v_diffusion.UNet runs on an MI355X through libvdiff_hip.so only; there is no CPU path "
+                               "(the CPU restatement lives under oracle/ and is test infrastructure)")
+        out_shape = (x.shape[0], self.out_channels) + tuple(x.shape[2:])
+        if x.shape[0] == 0:                                   # empty batch: nothing to launch
+            tape = ()
+            out = x.new_zeros(out_shape, dtype=torch.float32)
+        else:
+            with torch.no_grad(), torch.cuda.device(x.device):
+                out, tape = self.engine().forward(x.detach(), t, y, self.training, save=True)
+                out = self._to_nchw(out)
+        state = [tape]
+
+        def vjp(dout):
+            if state[0] is None:
+                raise RuntimeError(_TWICE)
+            tape, state[0] = state[0], None
+            if not torch.is_tensor(dout) or tuple(dout.shape) != out_shape:
+                raise ValueError(f"dout must have the output's shape {out_shape}, got {tuple(getattr(dout, 'shape', ()))}")
+            if not tape:
+                return x.new_zeros(tuple(x.shape), dtype=torch.float32)
+            if not dout.is_cuda:
+                raise RuntimeError("v_diffusion.UNet.forward_vjp: dout must be on the device of the forward")
+            return self._input_grad(tape, dout.detach())
+        return out, vjp
 
     def _chain_end(self, run):
         eng = self._engine
@@ -395,6 +464,8 @@ class UNet(nn.Module):
             return x.new_zeros((0, self.out_channels) + tuple(x.shape[2:]), dtype=torch.float32)
         params = list(self.parameters())
         if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in params)):
+            if x.requires_grad and not any(p.requires_grad for p in params):
+                return _UNetInputFn.apply(self, x, t, y)      # a frozen network: d/dx without the weight-gradient work
             if self._flat_grad_views is None and _hip.AUTOGRAD_CHAIN:
                 return self._forward_chain(x, t, y)
             return _UNetFn.apply(self, x, t, y, *params)
