@@ -10,7 +10,13 @@ The second run must reproduce the first BIT FOR BIT in the real part of every ou
 is read and multiplied by zero, a split-K slab summed without having been written, a row of the last 16-tile block of V / dM past T, a
 destination accumulated into where it should be overwritten -- each turns a finite leftover into a NaN here.  Every case asserts that the
 scratch tag of its entry was among the poisoned ones and that both runs took the same kernel form (the intended one where the entry's own
-test names it).  Needs an MI355X."""
+test names it).
+
+And the memory AROUND the tensors ("Memory a kernel may not read", the write side): every destination and every source is a view
+into the middle of a larger allocation (poison.Banded: a band of an image / 256 rows / 64 Ki floats on either side, sentinel around
+destinations, the run's pad value -- NaN in the second run -- around sources, so the halo rows above the first image and below the last are
+poisoned too), and the second run gets scratch of EXACTLY the bytes asked for, between sentinel bands (poison.ExactWorkspace).  No band
+of a destination or of a scratch buffer may change.  Needs an MI355X."""
 import functools
 import math
 import os
@@ -40,10 +46,18 @@ def H():
     return _hip
 
 
+@pytest.fixture(autouse=True)
+def _drop_bands():
+    """the ledger of poison.Banded records keeps their allocations alive: emptied after every test"""
+    yield
+    P.forget_bands()
+
+
 def dest(shape, cols=None, poison=False, init=None):
     """a destination: real part (columns [0, cols) of the last axis; cols None: everything) NaN in the poisoned run, CLEAN_FILL in the clean
-    one -- or `init` (a CPU tensor of the real part's shape) for an accumulating call --, pitch columns the sentinel"""
-    t = torch.full(shape, P.SENTINEL, device=DEV)
+    one -- or `init` (a CPU tensor of the real part's shape) for an accumulating call --, pitch columns the sentinel; banded: the tensor
+    is a view between two sentinel bands of poison.band_elems(shape) floats, which twice() checks after each run"""
+    t = P.banded(shape, P.SENTINEL, P.SENTINEL, device=DEV)
     real = t if cols is None else t[..., :cols]
     if init is not None:
         real.copy_(init)
@@ -62,14 +76,33 @@ def _sync():
 
 def twice(H, tags, run, verify):
     """run(pad, poison) -> (kernel form, {name: (tensor, real columns or None)}).  Clean run, `verify(outputs)` against fp64, poison, the same
-    call again, bitwise comparison.  Returns both forms' common value."""
+    call again, bitwise comparison.  Returns both forms' common value.
+
+    Memory AROUND the tensors: every destination of dest() and every source of poison.pitched() / pitched_rows() lies between two bands
+    (sentinel / the run's pad value), and the poisoned pass runs on poison.ExactWorkspace -- scratch of exactly the bytes the wrapper
+    asked for, NaN-filled, between sentinel bands.  After each pass no band of a destination, after the poisoned pass no band of a
+    scratch buffer may have changed, and the entry's tag must have been requested."""
+    _sync()
+    damage = P.bands_damage()                                   # (packed weight images made for this case before it runs)
+    assert not damage, f"written outside a destination before the runs: {damage}"
     form_c, clean = run(CLEAN_PAD, False)
     _sync()
+    damage = P.bands_damage()
+    assert not damage, f"written outside a destination (clean run): {damage}"
     verify(clean)
     found = P.poison_workspaces(H, P.FLOAT_TAGS)
     assert set(tags) <= found, f"scratch of this entry not poisoned: wanted {tags}, cached {sorted(found)}"
-    form_p, pois = run(NAN, True)
-    _sync()
+    damage = P.bands_damage()                                   # (statistics that verify() finalised into banded tensors)
+    assert not damage, f"written outside a destination while verifying: {damage}"
+    exact = P.ExactWorkspace()
+    with pytest.MonkeyPatch.context() as mp:
+        mp.setattr(H, "workspace", exact)
+        form_p, pois = run(NAN, True)
+        _sync()
+    damage = P.bands_damage()
+    assert not damage, f"written outside a destination (poisoned run): {damage}"
+    assert exact.intact(), f"written outside the scratch the entry was given {exact.requests}: {exact.damage()}"
+    assert set(tags) <= exact.tags(), f"scratch of this entry not requested: wanted {tags}, requested {exact.requests}"
     assert form_c == form_p, f"the two runs took different kernel forms: {form_c} / {form_p}"
     assert clean.keys() == pois.keys()
     for name, (tc, cols) in clean.items():
@@ -112,7 +145,7 @@ def test_gemm_kinds(H, a_kind, b_kind, M, N, K, tile):
         Bd = P.pitched_rows(B if b_kind == 0 else B.T.contiguous(), (K if b_kind == 0 else N) + 4, pad)
         Rd = P.pitched_rows(R, N + 4, pad)
         Cd = dest((M, N + 4), N, poison)
-        H.gemm(Ad, Bd, Cd, M, N, K, a_kind=a_kind, b_kind=b_kind, lda=Ad.shape[1], ldb=Bd.shape[1], ldc=N + 4, bias=bias.to(DEV), R=Rd,
+        H.gemm(Ad, Bd, Cd, M, N, K, a_kind=a_kind, b_kind=b_kind, lda=Ad.shape[1], ldb=Bd.shape[1], ldc=N + 4, bias=P.on_device(bias), R=Rd,
                ldr=N + 4, alpha=0.5, tile=tile)
         return H.lib().vd_gemm_last_tile(), {"C": (Cd, N)}
     twice(H, (), run, lambda o: close(o["C"][0][:, :N], ref64, ref32, name=f"gemm{a_kind}{b_kind}"))
@@ -177,7 +210,7 @@ def test_gemm_grouped_wgrad(H, count, M, N, K, splitk, pad):
     def run(padv, poison):
         ents = []
         for dy, x in data:
-            dyp, xp = torch.full((K, M + pad), padv, device=DEV), torch.full((K, N + pad), padv, device=DEV)
+            dyp, xp = (P.banded((K, c + pad), padv, padv, device=DEV, check=False) for c in (M, N))
             dyp[:, :M], xp[:, :N] = dy, x
             ents.append((dyp, xp, dest((M, N + pad), N, poison), dest((M,), None, poison)))
         H.gemm_grouped_wgrad(ents, M, N, K, M + pad, N + pad, N + pad, splitk)
@@ -264,29 +297,32 @@ def _wgrad_twice(H, case, accumulate, tags, entry, bound, form):
 
 # ------------------------------------------------------------------------------------------------ direct 3x3 (implicit GEMM)
 DIRECT_CASES = [(3, 16, 16, 64, 32, 32, 64), (5, 8, 8, 36, 68, 4, 4)]       # nimg, H, W, Cin, Cout, ldx - Cin, ldy - Cout
+# a single 2x2 image (every tap but the centre is a halo: the rows above and below the tensor are the source's bands); three output
+# channels at pitch 4 (forward only: the input gradient's K is a multiple of 4)
+DIRECT_SMALL, DIRECT_THIN = (1, 2, 2, 8, 8, 0, 0), (2, 8, 8, 32, 3, 0, 1)
 
 
-@pytest.mark.parametrize("case", DIRECT_CASES)
+@pytest.mark.parametrize("case", DIRECT_CASES + [DIRECT_SMALL, DIRECT_THIN])
 def test_conv3x3_direct_forward(H, case):
     nimg, Hh, Ww, Cin, Cout, ex, ey = case
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    wf = torch.empty(Cout, 9, Cin, device=DEV)
-    H.pack_conv3x3(d["w"].to(DEV), Cout, Cin, wf=wf, Cin_p=Cin)
+    wf = dest((Cout, 9, Cin))
+    H.pack_conv3x3(P.on_device(d["w"]), Cout, Cin, wf=wf, Cin_p=Cin)
 
     def run(pad, poison):
         y = dest((nimg, Hh, Ww, Cout + ey), Cout, poison)
-        H.conv3x3(P.pitched(d["x"], Cin + ex, pad), Cin + ex, wf, d["b"].to(DEV), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
+        H.conv3x3(P.pitched(d["x"], Cin + ex, pad), Cin + ex, wf, P.on_device(d["b"]), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
                   res=P.pitched(d["res"], Cout + ey, pad), ldres=Cout + ey)
         return H.lib().vd_gemm_last_tile(), {"y": (y, Cout)}
     twice(H, (), run, lambda o: close(from_nhwc(o["y"][0], Cout), d["y64"], d["y32"], name="conv fwd"))
 
 
-@pytest.mark.parametrize("case", DIRECT_CASES)
+@pytest.mark.parametrize("case", DIRECT_CASES + [DIRECT_SMALL])
 def test_conv3x3_direct_dgrad(H, case):
     nimg, Hh, Ww, Cin, Cout, ex, ey = case
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    wd = torch.empty(Cin, 9, Cout, device=DEV)
-    H.pack_conv3x3(d["w"].to(DEV), Cout, Cin, wd=wd, Cout_p=Cout)
+    wd = dest((Cin, 9, Cout))
+    H.pack_conv3x3(P.on_device(d["w"]), Cout, Cin, wd=wd, Cout_p=Cout)
 
     def run(pad, poison):
         dx = dest((nimg, Hh, Ww, Cin + ex), Cin, poison)
@@ -306,21 +342,22 @@ def test_conv3x3_direct_wgrad(H, case, accumulate):
 
 
 # ------------------------------------------------------------------------------------------------ Winograd F(2x2,3x3)
-# the pitched rows of WINO_CASES / WINO_WGRAD_CASES: ld > C on both sides with a partial channel block; four images per workgroup, Cout % 32 != 0
-@pytest.mark.parametrize("case", [(3, 16, 16, 32, 96, 32, 64), (5, 8, 8, 48, 36, 0, 4)])
+# the pitched rows of WINO_CASES / WINO_WGRAD_CASES: ld > C on both sides with a partial channel block; four images per workgroup (the last
+# workgroup holds 1 of 4), Cout % 32 != 0; 64 tiles per row (the largest patch image); 120 work items (a ragged persistent round)
+@pytest.mark.parametrize("case", [(3, 16, 16, 32, 96, 32, 64), (5, 8, 8, 48, 36, 0, 4), (1, 8, 128, 16, 20, 0, 0), (10, 32, 32, 32, 96, 0, 0)])
 def test_conv3x3_wino_forward_stats_dgrad(H, case):
     nimg, Hh, Ww, Cin, Cout, ex, ey = case
     HW = Hh * Ww
     assert H.lib().vd_conv3x3_wino_supported(nimg, Hh, Ww, Cin, Cout, Cin + ex, Cout + ey, Cout + ey) == 1
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    uf, ud = torch.empty(16, Cout, Cin, device=DEV), torch.empty(16, Cin, Cout, device=DEV)
-    H.wino_pack(d["w"].to(DEV), Cout, Cin, uf=uf, ud=ud)
+    uf, ud = dest((16, Cout, Cin)), dest((16, Cin, Cout))
+    H.wino_pack(P.on_device(d["w"]), Cout, Cin, uf=uf, ud=ud)
     used = nimg * (HW // 64) * 2 * Cout                        # [img][H*W/64][2][Cout]
 
     def run(pad, poison):
         y = dest((nimg, Hh, Ww, Cout + ey), Cout, poison)
         part = dest((H.stats_part_numel(nimg, HW, Cout),), used, poison)
-        H.conv3x3_wino(P.pitched(d["x"], Cin + ex, pad), Cin + ex, uf, d["b"].to(DEV), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
+        H.conv3x3_wino(P.pitched(d["x"], Cin + ex, pad), Cin + ex, uf, P.on_device(d["b"]), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
                        res=P.pitched(d["res"], Cout + ey, pad), ldres=Cout + ey, stats_part=part)
         assert H.last_row_tile() == 128
         return H.lib().vd_wino_last_kernel(), {"y": (y, Cout), "stats_part": (part, used)}
@@ -328,7 +365,7 @@ def test_conv3x3_wino_forward_stats_dgrad(H, case):
     def verify(o):
         close(from_nhwc(o["y"][0], Cout), d["y64"], d["y32"], slack=8.0, floor=4e-6, name="wino fwd")
         if Cout % 32 == 0:
-            stats = torch.empty(nimg, 32, 2, device=DEV)
+            stats = dest((nimg, 32, 2))
             H.gn_stats_from_partials([(o["stats_part"][0], Cout, HW // 64)], nimg, HW, stats)
             g = d["y64"].reshape(nimg, 32, -1)
             close(stats[..., 0], g.mean(-1), None, floor=4e-6, name="wino stats mean")
@@ -356,7 +393,9 @@ def test_conv3x3_wgrad_wino(H, case, accumulate):
 
 
 # ------------------------------------------------------------------------------------------------ Winograd F(4x4,3x3), fused kernels
-W43_CASES = [(3, 32, 32, 96, 24, 8, 32), (12, 16, 16, 96, 40, 8, 32)]        # rows of WINO43_CASES with ld > C on both sides
+# rows of WINO43_CASES: ld > C on both sides (three images x three channel blocks; three image quads); one quad of 16x16 images in one
+# item; a 64-wide image of one 16-row part
+W43_CASES = [(3, 32, 32, 96, 24, 8, 32), (12, 16, 16, 96, 40, 8, 32), (4, 16, 16, 32, 8, 0, 0), (1, 16, 64, 32, 16, 0, 0)]
 
 
 @pytest.mark.parametrize("case", W43_CASES)
@@ -365,22 +404,22 @@ def test_conv3x3_wino43_fwd(H, case):
     HW = Hh * Ww
     assert H.lib().vd_conv3x3_wino43_fwd_supported(nimg, Hh, Ww, Cin, Cout, Cin + ex, Cout + ey, Cout + ey) == 1
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    u43f = torch.empty(H.lib().vd_wino43_u_floats(Cout, Cin), device=DEV)
-    H.wino43_pack_fwd(d["w"].to(DEV), Cout, Cin, u43f)
+    u43f = dest((H.lib().vd_wino43_u_floats(Cout, Cin),))
+    H.wino43_pack_fwd(P.on_device(d["w"]), Cout, Cin, u43f)
     chunks = HW // H.wino43_fwd_chunk_rows(Hh, Ww)
     used = nimg * chunks * 2 * Cout
 
     def run(pad, poison):
         y = dest((nimg, Hh, Ww, Cout + ey), Cout, poison)
         part = dest((H.stats_part_numel(nimg, HW, Cout),), used, poison)
-        H.conv3x3_wino43_fwd(P.pitched(d["x"], Cin + ex, pad), Cin + ex, u43f, d["b"].to(DEV), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
+        H.conv3x3_wino43_fwd(P.pitched(d["x"], Cin + ex, pad), Cin + ex, u43f, P.on_device(d["b"]), y, Cout + ey, nimg, Hh, Ww, Cin, Cout,
                              res=P.pitched(d["res"], Cout + ey, pad), ldres=Cout + ey, stats_part=part)
         return H.lib().vd_wino43_last_kernel(), {"y": (y, Cout), "stats_part": (part, used)}
 
     def verify(o):
         y = o["y"][0]
         close(from_nhwc(y, Cout), d["y64"], d["y32"], slack=8.0, floor=4e-6, name="wino43 forward")
-        stats = torch.empty(nimg, 32, 2, device=DEV)
+        stats = dest((nimg, 32, 2))
         H.gn_stats_from_partials([(o["stats_part"][0], Cout, chunks)], nimg, HW, stats)
         g = from_nhwc(y, Cout).double().reshape(nimg, 32, -1)               # statistics of what was WRITTEN
         close(stats[..., 0], g.mean(-1), None, floor=2e-6, name="mean")
@@ -393,8 +432,8 @@ def test_conv3x3_dgrad_wino43(H, case):
     nimg, Hh, Ww, Cin, Cout, ey, ex = case
     assert H.lib().vd_conv3x3_dgrad_wino43_supported(nimg, Hh, Ww, Cin, Cout, Cout + ey, Cin + ex) == 1
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    u43 = torch.empty(H.lib().vd_wino43_u_floats(Cout, Cin), device=DEV)
-    H.wino43_pack(d["w"].to(DEV), Cout, Cin, u43)
+    u43 = dest((H.lib().vd_wino43_u_floats(Cout, Cin),))
+    H.wino43_pack(P.on_device(d["w"]), Cout, Cin, u43)
 
     def run(pad, poison):
         dx = dest((nimg, Hh, Ww, Cin + ex), Cin, poison)
@@ -451,7 +490,7 @@ def test_forward_planes(H, case):
     ldres = Cout + 8
     assert lib.vd_conv3x3_wino43_fwd_planes_supported(nimg, Hh, Ww, Cin, Cout, Cin + ex, Cout + ey, ldres) == 1
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    wd, bd = d["w"].to(DEV), d["b"].to(DEV)
+    wd, bd = P.on_device(d["w"]), P.on_device(d["b"])
     chunks = HW // H.wino43_fwd_chunk_rows(Hh, Ww)
     used = nimg * chunks * 2 * Cout
 
@@ -477,7 +516,7 @@ def test_forward_planes(H, case):
         else:
             assert nimg % 4 != 0
             close(from_nhwc(y, Cout), d["y64"], d["y32"], slack=8.0, floor=4e-6, name="planes forward")
-        stats = torch.empty(nimg, 32, 2, device=DEV)
+        stats = dest((nimg, 32, 2))
         H.gn_stats_from_partials([(o["stats_part"][0], Cout, chunks)], nimg, HW, stats)
         g = from_nhwc(y, Cout).double().reshape(nimg, 32, -1)               # statistics of what was WRITTEN
         mean, rstd = g.mean(-1), 1 / torch.sqrt(g.var(-1, unbiased=False) + 1e-6)
@@ -498,10 +537,10 @@ def test_weight_gradient_from_given_images(H, both, accumulate):
     assert H.wgrad43_supported(nimg, Hh, Ww, Cin, Cout, Cin, Cout)
     d = _wgrad_data(nimg, Hh, Ww, Cin, Cout, Cin, Cout)
     xd, dyd = P.pitched(d["x"], Cin, CLEAN_PAD), P.pitched(d["dy"], Cout, CLEAN_PAD)
-    v = torch.empty(lib.vd_conv3x3_wino43_v_floats(nimg, Hh, Ww, Cin), device=DEV)
-    H.conv3x3_wino43_fwd_planes(xd, Cin, rnd(Cout, Cin, 3, 3, seed=2, scale=(9 * Cin) ** -0.5).to(DEV), None,
+    v = dest((lib.vd_conv3x3_wino43_v_floats(nimg, Hh, Ww, Cin),))
+    H.conv3x3_wino43_fwd_planes(xd, Cin, P.on_device(rnd(Cout, Cin, 3, 3, seed=2, scale=(9 * Cin) ** -0.5)), None,
                                 torch.empty(nimg, Hh, Ww, Cout, device=DEV), Cout, nimg, Hh, Ww, Cin, Cout, v=v)
-    dm = torch.empty(lib.vd_conv3x3_wino43_dm_floats(nimg, Hh, Ww, Cout), device=DEV)
+    dm = dest((lib.vd_conv3x3_wino43_dm_floats(nimg, Hh, Ww, Cout),))
     H.conv3x3_wino43_dy_image(dyd, Cout, nimg, Hh, Ww, Cout, dm)
 
     def run(pad, poison):
@@ -527,7 +566,7 @@ def test_dy_image_and_dgrad_planes(H, case):
     assert lib.vd_conv3x3_wino43_dgrad_planes_supported(nimg, Hh, Ww, Cin, Cout, Cin + ex) == 1
     assert lib.vd_conv3x3_dgrad_wino43_supported(nimg, Hh, Ww, Cin, Cout, Cout + ey, Cin) == 0
     d = _conv_data(nimg, Hh, Ww, Cin, Cout)
-    wd = d["w"].to(DEV).contiguous()
+    wd = P.on_device(d["w"]).contiguous()
     nm = lib.vd_conv3x3_wino43_dm_floats(nimg, Hh, Ww, Cout)
 
     def run(pad, poison):
@@ -550,21 +589,24 @@ def test_dy_image_and_dgrad_planes(H, case):
 # ------------------------------------------------------------------------------------------------ GroupNorm
 # nimg, C, H, W, film -> form of the backward (vd_gn_bwd_last_kernel): plain single-pass; two-pass (24-channel slabs: 96-byte rows);
 # SPLIT with 4 sibling workgroups per (image, slab)
-GN_POISON_CASES = [((2, 64, 8, 8, False), "plain"), ((3, 96, 8, 8, True), "plain"), ((2, 192, 64, 64, False), "two-pass"),
-                   ((2, 256, 64, 64, False), "split4")]
+# act and resample (0 none, 1 down, 2 up: apply and backward index a second resolution) as in GN_CASES
+GN_POISON_CASES = [((2, 64, 8, 8, False, True, 0), "plain"), ((3, 96, 8, 8, True, True, 0), "plain"),
+                   ((2, 192, 64, 64, False, True, 0), "two-pass"), ((2, 256, 64, 64, False, True, 0), "split4"),
+                   ((2, 128, 4, 4, False, False, 0), "any"), ((2, 64, 8, 8, False, True, 1), "any"), ((2, 64, 8, 8, False, True, 2), "any")]
 
 
 @functools.lru_cache(maxsize=None)
-def _gn_data(nimg, Cc, Hh, Ww, use_film):
+def _gn_data(nimg, Cc, Hh, Ww, use_film, act, rs):
     x = rnd(nimg, Cc, Hh, Ww, seed=1) * 1.5 + 0.3
     gamma, beta = 1 + 0.1 * rnd(Cc, seed=2), 0.1 * rnd(Cc, seed=3)
     film = 0.3 * rnd(nimg, 2 * Cc, seed=4) if use_film else None
-    dy, add = rnd(nimg, Cc, Hh, Ww, seed=5), rnd(nimg, Cc, Hh, Ww, seed=6)
+    Ho, Wo = (Hh // 2, Ww // 2) if rs == 1 else ((Hh * 2, Ww * 2) if rs == 2 else (Hh, Ww))
+    dy, add = rnd(nimg, Cc, Ho, Wo, seed=5), rnd(nimg, Cc, Hh, Ww, seed=6)
 
     def ref(dt):
         xs, g, b_ = x.to(dt).requires_grad_(True), gamma.to(dt).requires_grad_(True), beta.to(dt).requires_grad_(True)
         fl = None if film is None else film.to(dt).requires_grad_(True)
-        out = ref_gn_block(xs, g, b_, fl, True, 0)
+        out = ref_gn_block(xs, g, b_, fl, act, rs)
         out.backward(dy.to(dt))
         return out.detach(), xs.grad + add.to(dt), g.grad, b_.grad, (None if fl is None else fl.grad)
     return dict(x=x, gamma=gamma, beta=beta, film=film, dy=dy, add=add, r64=ref(torch.float64), r32=ref(torch.float32))
@@ -574,22 +616,23 @@ def _gn_data(nimg, Cc, Hh, Ww, use_film):
 def test_gn_stats_apply_backward(H, case, form):
     """vd_gn_stats -> vd_gn_apply -> vd_gn_apply_bwd as test_kernels_gpu.py::test_gn_forward_backward runs them, every tensor at pitch C + 8,
     nothing accumulated: statistics, coefficient table, y, dx, dfilm, dgamma, dbeta all start as NaN in the second run"""
-    nimg, Cc, Hh, Ww, use_film = case
+    nimg, Cc, Hh, Ww, use_film, act, rs = case
     d = _gn_data(*case)
     ld = Cc + 8
-    gd, bd = d["gamma"].to(DEV), d["beta"].to(DEV)
-    fd = None if d["film"] is None else d["film"].to(DEV)
+    Ho, Wo = d["dy"].shape[2:]
+    gd, bd = P.on_device(d["gamma"]), P.on_device(d["beta"])
+    fd = None if d["film"] is None else P.on_device(d["film"])
 
     def run(pad, poison):
         xd = P.pitched(d["x"], ld, pad)
         stats = dest((nimg, 32, 2), None, poison)
         H.gn_stats(xd, ld, nimg, Hh * Ww, Cc, stats)
-        coef, y = dest((nimg, 4, Cc), None, poison), dest((nimg, Hh, Ww, ld), Cc, poison)
-        H.gn_apply(xd, ld, stats, gd, bd, fd, True, 0.0, 0, 0, y, ld, nimg, Hh, Ww, Cc, coef)
+        coef, y = dest((nimg, 4, Cc), None, poison), dest((nimg, Ho, Wo, ld), Cc, poison)
+        H.gn_apply(xd, ld, stats, gd, bd, fd, act, 0.0, 0, rs, y, ld, nimg, Hh, Ww, Cc, coef)
         dx = dest((nimg, Hh, Ww, ld), Cc, poison)
         dfilm = None if fd is None else dest((nimg, 2 * Cc), None, poison)
         dgam, dbet = dest((Cc,), None, poison), dest((Cc,), None, poison)
-        H.gn_apply_bwd(P.pitched(d["dy"], ld, pad), ld, xd, ld, coef, gd, bd, fd, True, 0.0, 0, 0, P.pitched(d["add"], ld, pad), ld, dx, ld,
+        H.gn_apply_bwd(P.pitched(d["dy"], ld, pad), ld, xd, ld, coef, gd, bd, fd, act, 0.0, 0, rs, P.pitched(d["add"], ld, pad), ld, dx, ld,
                        False, dfilm, dgam, dbet, False, nimg, Hh, Ww, Cc)
         out = {"stats": (stats, None), "coef": (coef, None), "y": (y, Cc), "dx": (dx, Cc), "dgamma": (dgam, None), "dbeta": (dbet, None)}
         if dfilm is not None:
@@ -610,7 +653,7 @@ def test_gn_stats_apply_backward(H, case, form):
         assert k == -1, k
     elif form == "split4":
         assert k // 100000000 == 4 and k % 10000 == 1024, k
-    else:
+    elif form == "plain":
         assert 0 < k < 100000000, k
 
 
@@ -621,16 +664,16 @@ def test_gn_apply_from_partials(H):
     nimg, Hh, Ww, Cin, C1 = 3, 8, 8, 64, 96
     HW, ldb = Hh * Ww, C1 + 8
     d = _conv_data(nimg, Hh, Ww, Cin, C1)
-    wf = torch.empty(C1, 9, Cin, device=DEV)
-    H.pack_conv3x3(d["w"].to(DEV), C1, Cin, wf=wf, Cin_p=Cin)
-    gamma, beta, film = rnd(C1, seed=7).to(DEV), rnd(C1, seed=8).to(DEV), (rnd(nimg, 2 * C1, seed=9) * 0.1).to(DEV)
+    wf = dest((C1, 9, Cin))
+    H.pack_conv3x3(P.on_device(d["w"]), C1, Cin, wf=wf, Cin_p=Cin)
+    gamma, beta, film = P.on_device(rnd(C1, seed=7)), P.on_device(rnd(C1, seed=8)), P.on_device(rnd(nimg, 2 * C1, seed=9) * 0.1)
     npart = H.stats_part_numel(nimg, HW, C1)
     keep = {}
 
     def run(pad, poison):
         buf = dest((nimg, Hh, Ww, ldb), C1, poison)
-        part = torch.full((npart,), NAN if poison else CLEAN_FILL, device=DEV)
-        H.conv3x3(P.pitched(d["x"], Cin + 4, pad), Cin + 4, wf, d["b"].to(DEV), buf, ldb, nimg, Hh, Ww, Cin, C1,
+        part = P.banded((npart,), NAN if poison else CLEAN_FILL, P.SENTINEL, device=DEV)
+        H.conv3x3(P.pitched(d["x"], Cin + 4, pad), Cin + 4, wf, P.on_device(d["b"]), buf, ldb, nimg, Hh, Ww, Cin, C1,
                   res=P.pitched(d["res"], C1 + 4, pad), ldres=C1 + 4, stats_part=part)
         code = H.lib().vd_gemm_last_tile()
         chunks = HW // (H.last_row_tile() // 2)
@@ -649,7 +692,7 @@ def test_gn_apply_from_partials(H):
     def verify(o):
         close(from_nhwc(o["conv y"][0], C1), d["y64"], d["y32"], name="conv fwd")
         buf, parts = keep["buf"], [(keep["part"], C1, keep["chunks"])]
-        stats = torch.empty(nimg, 32, 2, device=DEV)
+        stats = dest((nimg, 32, 2))
         H.gn_stats_from_partials(parts, nimg, HW, stats)
         g = d["y64"].reshape(nimg, 32, -1)
         close(stats[..., 0], g.mean(-1), None, floor=2e-6, name="mean")
@@ -683,9 +726,8 @@ def test_sumsq(H, n):
     ref = (g.double() ** 2).sum().reshape(1)
 
     def run(pad, poison):
-        whole = torch.full((n + 64,), pad, device=DEV)          # what lies behind the n floats is not the kernel's to read
-        whole[:n] = g.to(DEV)
+        gd = P.banded_like(g, pad, DEV)                         # what lies before and behind the n floats is not the kernel's to read
         ss = dest((1,), None, poison)
-        H.sumsq(whole[:n], ss)
+        H.sumsq(gd, ss)
         return 0, {"sumsq": (ss, None)}
     twice(H, ("sumsq",), run, lambda o: close(o["sumsq"][0], ref, None, floor=1e-6, name="sumsq"))
