@@ -7,11 +7,12 @@
 // Without a counterpart in the reference: progressive distillation; consistency distillation / training and the batched
 // target-network update; the DPM-Solver++(2M) reverse step, its dynamically thresholded form and the UniPC step; the RePaint
 // masked reverse step and the forward jump; the noise-map extraction of DDPM inversion; spherical interpolation; the residual and
-// the corrected reverse step of Diffusion Posterior Sampling.
+// the corrected reverse step of Diffusion Posterior Sampling; the null-space reverse step of DDNM.
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 // Device side first, then the host helpers (launch, coefficient carrier, the refusals every entry shares), then the C entries.
 #include "common.h"
 #include "../../include/vdiff_hip_dps.h"
+#include "../../include/vdiff_hip_ddnm.h"
 
 namespace {
 
@@ -449,14 +450,16 @@ inline int grid_for(long long total) {
 }
 
 // V = floats per lane and access: 4 (dwordx4) when C*HW is a multiple of 4 and every base is 16-byte aligned -- a vector then never
-// straddles two samples or the two halves of a "both" output -- else 1.
+// straddles two samples or the two halves of a "both" output -- else 1.  (2, dwordx2: the two-float rows of ddnm_step_kernel.)
 template <int V> __device__ __forceinline__ void ldv(const float* p, float (&r)[V]) {
     if constexpr (V == 4) { const float4 t = *reinterpret_cast<const float4*>(p); r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
+    else if constexpr (V == 2) { const float2 t = *reinterpret_cast<const float2*>(p); r[0] = t.x; r[1] = t.y; }
     else r[0] = *p;
 }
 
 template <int V> __device__ __forceinline__ void stv(float* p, const float (&r)[V]) {
     if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(r[0], r[1], r[2], r[3]);
+    else if constexpr (V == 2) *reinterpret_cast<float2*>(p) = make_float2(r[0], r[1]);
     else *p = r[0];
 }
 
@@ -546,8 +549,9 @@ struct PredX0 {
 // reference takes the output itself as eps, diffusion.py:338-347 -- rebuilding it as (xt - alpha*x0_hat)/sigma cancels)
 template <bool FUSED> struct StepMean {
     PredX0 x0; float c1, c2, c3; bool last;
-    __device__ __forceinline__ float operator()(float z, float o, float oe) const {
-        const float x0h = x0(z, o, oe);
+    __device__ __forceinline__ float operator()(float z, float o, float oe) const { return of(z, x0(z, o, oe), o); }
+    // ... from a prediction already formed (a kernel that needs the prediction too forms it once)
+    __device__ __forceinline__ float of(float z, float x0h, float o) const {
         if (last) return x0h;
         return FUSED ? mean_fused(c1, c2, c3, z, x0h, o) : mean_plain(c1, c2, c3, z, x0h, o);
     }
@@ -1437,6 +1441,163 @@ __global__ void dps_step_kernel(const DpsStepArgs p) {
     }
 }
 
+// ---- Denoising Diffusion Null-space Model (Wang, Yu, Zhang 2023): the three operators of the DPS section have a closed-form
+// pseudo-inverse, so the step's x0 prediction is corrected without a gradient: g_hat = g + lam * A^+(meas - A g) keeps the network's
+// null-space part and takes the range-space part from the measurement.  ONE launch per reverse step: sample_step_kernel's value v (the
+// same helpers: prediction, clip, guided mean_plain, last step, noise) and
+//   xn = fma(cw, d, v),   d = A^+ r on the preimage,  r = meas_j - A g,  cw = lam on the last step and c2 * lam otherwise (host, rounded once)
+// since v holds c2 * g.  A g is dps_apply's (the preimage summed in fp64, rounded once); d = r for the two means (A^+ spreads r over the
+// preimage) and r / M for a mask element with M > 0.  SELECTED, not multiplied: with lam = 0 the row is sample_step_kernel's bit for bit
+// (and without sumsq meas and mask are never read); a mask element with M = 0 has no measurement -- no correction, no share of sumsq,
+// whatever meas holds there; with `exact` (mask, last step, lam = 1, no noise term) an element with M = 1 IS meas.
+// The work split is dps_residual_kernel's: one workgroup owns one sample, a thread G adjacent measurement elements with their preimages
+// (rows x LEN floats each: 1 x 1 mask, f x f blocks with LEN = f, C x 1 grey), so nothing but the optional sum crosses threads and a
+// thread has read its whole preimage before it writes any of it (xn may alias xt; rows > 1 are read again, element by element, each
+// before its own store).  G and LEN follow from the SHAPES alone -- G = 4 where the measurement rows are whole multiples of 4 -- and fix
+// which thread adds which r^2 in which order; WIDE (every base 16-byte aligned) only turns the G * LEN floats of a row into dwordx2 /
+// dwordx4 accesses: the same bits, sumsq included.
+struct DdnmArgs {
+    StepCommon s; const float* noise; const float* meas; const float* mask; float* sumsq; float lam, cw; int exact, op, par, C, H, W;
+};
+
+// VW = 1, 2 or 4 floats of a row: one access (ldv / stv) when WIDE, else element by element
+template <int VW, bool WIDE> __device__ __forceinline__ void ld_row(const float* p, float (&r)[VW]) {
+    if constexpr (WIDE) ldv<VW>(p, r);
+    else {
+#pragma unroll
+        for (int j = 0; j < VW; ++j) r[j] = p[j];
+    }
+}
+
+template <int VW, bool WIDE> __device__ __forceinline__ void st_row(float* p, const float (&r)[VW]) {
+    if constexpr (WIDE) stv<VW>(p, r);
+    else {
+#pragma unroll
+        for (int j = 0; j < VW; ++j) p[j] = r[j];
+    }
+}
+
+// one sample's rows of the step's operands
+struct DdnmRows { const float* z; const float* oc; const float* ou; int N; bool both, cfg; };
+
+// elements [i, i + VW) of the sample: g = the guided clipped prediction (dps_residual_kernel's pred), v = sample_step_kernel's guided mean
+template <int VW, bool WIDE>
+__device__ __forceinline__ void ddnm_row(const DdnmRows& t, const StepMean<false>& f, float w, int i, float (&g)[VW], float (&v)[VW]) {
+    float z[VW], o[VW], oe[VW] = {};
+    ld_row<VW, WIDE>(t.z + i, z);
+    ld_row<VW, WIDE>(t.oc + i, o);
+    if (t.both) ld_row<VW, WIDE>(t.oc + t.N + i, oe);
+#pragma unroll
+    for (int j = 0; j < VW; ++j) { g[j] = f.x0(z[j], o[j], oe[j]); v[j] = f.of(z[j], g[j], o[j]); }
+    if (t.cfg) {
+        ld_row<VW, WIDE>(t.ou + i, o);
+        if (t.both) ld_row<VW, WIDE>(t.ou + t.N + i, oe);
+#pragma unroll
+        for (int j = 0; j < VW; ++j) {
+            const float pu = f.x0(z[j], o[j], oe[j]);
+            v[j] = guide(w, v[j], f.of(z[j], pu, o[j]));
+            g[j] = guide(w, g[j], pu);
+        }
+    }
+}
+
+__device__ __forceinline__ float ddnm_pinv(int op, float m, float r) {      // (A^+ r) of each element of the preimage; m > 0
+#pragma clang fp contract(off)
+    return op == DPS_MASK ? r / m : r;
+}
+
+__device__ __forceinline__ float ddnm_sub(float y, float ag) {
+#pragma clang fp contract(off)
+    return y - ag;
+}
+
+template <int OP, int G, int LEN, bool WIDE>
+__global__ __launch_bounds__(256) void ddnm_step_kernel(const DdnmArgs p) {
+    // a thread's row of G * LEN floats goes in pieces of at most 4 (LEN = 8: two), left to right: the order of the fp64 sum
+    constexpr int VW = G * LEN > 4 ? 4 : G * LEN, PIECES = G * LEN / VW;
+    __shared__ double sh[4];
+    const StepCommon& s = p.s;
+    const float* k = s.c.k;
+    const StepMean<false> f = step_mean<false>(s, k);
+    const float k5 = k[5], w = k[6];
+    // (offsets inside one sample are 32-bit -- the entry refuses C*H*W >= 2^31 -- and only the sample's bases 64-bit)
+    const long long b = blockIdx.x;
+    const int N = (int)s.N, HW = p.H * p.W;
+    const int Wo = p.W / LEN, HoWo = p.H / LEN * Wo;                                          // (LEN > 1: down-sampling by LEN)
+    const int rows = OP == DPS_MASK ? 1 : (OP == DPS_DOWN ? LEN : p.C);
+    const int stride = OP == DPS_DOWN ? p.W : HW;
+    const float cnt = (float)(rows * LEN);
+    const int M = OP == DPS_MASK ? N : (OP == DPS_DOWN ? p.C * HoWo : HW);        // measurement elements of a sample
+    const bool corr = p.lam != 0.f, need = corr || p.sumsq != nullptr, once = need && rows == 1;
+    const bool mask_wide = WIDE && (p.par != 1 || HW % G == 0);              // (a one-channel mask: a group may straddle two channels)
+    const DdnmRows in = {s.xt + b * s.N, s.out + b * (1 + s.cfg) * s.row, s.out + (b * (1 + s.cfg) + 1) * s.row, N, s.type == OUT_BOTH,
+                         s.cfg != 0};
+    const float* nb = p.noise ? p.noise + b * s.N : nullptr;
+    const float* yb = p.meas + b * M;
+    const float* mb = OP == DPS_MASK ? p.mask + b * p.par * (long long)HW : nullptr;
+    float* xb = s.xn + b * s.N;
+    float* db = s.xdup ? s.xdup + 2 * b * s.N : nullptr;
+    double acc = 0.0;
+    for (int t = threadIdx.x; t < M / G; t += blockDim.x) {
+        const int j0 = t * G;
+        int i0 = j0;
+        if constexpr (OP == DPS_DOWN) {
+            const int c = j0 / HoWo, r = j0 % HoWo, yo = r / Wo, xo = r % Wo;
+            i0 = c * HW + yo * LEN * p.W + xo * LEN;
+        }
+        float g[VW], v[VW], y[G] = {}, m[G] = {}, d[G] = {};                  // (m stays 0 where nothing is taken: no lane mask kept)
+        if (need) {
+            double sum[G] = {};
+#pragma unroll 1
+            for (int q = 0; q < rows * PIECES; ++q) {
+                ddnm_row<VW, WIDE>(in, f, w, i0 + q / PIECES * stride + q % PIECES * VW, g, v);
+#pragma unroll
+                for (int e = 0; e < VW; ++e) sum[G == 1 ? 0 : e / LEN] += (double)g[e];
+            }
+            ld_row<G, WIDE>(yb + j0, y);
+#pragma unroll
+            for (int e = 0; e < G; ++e) m[e] = 1.f;
+            if constexpr (OP == DPS_MASK) {
+                if (mask_wide) ld_row<G, WIDE>(mb + (p.par == 1 ? j0 % HW : j0), m);
+                else {
+#pragma unroll
+                    for (int e = 0; e < G; ++e) m[e] = mb[p.par == 1 ? (j0 + e) % HW : j0 + e];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < G; ++e) {
+                if (m[e] > 0.f) {
+                    const float r = ddnm_sub(y[e], dps_apply(OP, m[e], (float)sum[e], cnt));
+                    acc += (double)r * (double)r;
+                    d[e] = ddnm_pinv(OP, m[e], r);
+                }
+            }
+        }
+#pragma unroll 1
+        for (int q = 0; q < rows * PIECES; ++q) {
+            const int i = i0 + q / PIECES * stride + q % PIECES * VW;
+            if (!once) ddnm_row<VW, WIDE>(in, f, w, i, g, v);
+            if (nb) {
+                float nz[VW];
+                ld_row<VW, WIDE>(nb + i, nz);
+#pragma unroll
+                for (int e = 0; e < VW; ++e) v[e] = axpby(1.f, v[e], k5, nz[e]);
+            }
+#pragma unroll
+            for (int e = 0; e < VW; ++e) {
+                const int u = G == 1 ? 0 : e / LEN;
+                if (corr && m[u] > 0.f) v[e] = (p.exact && m[u] == 1.f) ? y[u] : __builtin_fmaf(p.cw, d[u], v[e]);
+            }
+            st_row<VW, WIDE>(xb + i, v);
+            if (db) { st_row<VW, WIDE>(db + i, v); st_row<VW, WIDE>(db + N + i, v); }
+        }
+    }
+    if (p.sumsq) {                                                           // (uniform over the workgroup)
+        acc = block_sum(acc, sh);
+        if (threadIdx.x == 0) p.sumsq[b] = (float)acc;
+    }
+}
+
 // ---- host side of the entries below
 template <typename... P> inline bool all_aligned16(P... ps) { return (vd_aligned16(ps) && ...); }
 
@@ -1868,5 +2029,40 @@ extern "C" int vd_dps_step(const float* xt, const float* out, const float* noise
     launch_elems(dps_step_kernel<4>, dps_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, dxin, dxt, xn, xdup), n * p.s.N, stream,
                  p);
     VD_LAUNCH_CHECK("dps_step_kernel");
+    return 0;
+}
+
+// (include/vdiff_hip_ddnm.h.  Host coefficients only, as the DPS entries: the chain has no captured-graph form)
+extern "C" int vd_ddnm_step(const float* xt, const float* out, const float* noise, const float* meas, const float* mask, const float* k,
+                            float lam, int32_t type, int32_t cfg, int32_t last_step, int32_t clip, int32_t op, int32_t par, float* xn,
+                            float* xdup, float* sumsq, int32_t n, int32_t C, int32_t H, int32_t W, void* stream) {
+    VD_REQUIRE(k != nullptr, "vd_ddnm_step: null pointer");
+    VD_REQUIRE(op >= DPS_MASK && op <= DPS_GRAY, "vd_ddnm_step: bad op %d", op);
+    VD_TRY(args_given("vd_ddnm_step", type, xt && out && meas && xn && (op != DPS_MASK || mask)));
+    VD_REQUIRE(n > 0 && C > 0 && H > 0 && W > 0, "vd_ddnm_step: empty batch or image (n=%d, C=%d, H=%d, W=%d)", n, C, H, W);
+    VD_REQUIRE(op != DPS_MASK || par == 1 || par == C, "vd_ddnm_step: the mask has 1 or C = %d channels, got %d", C, par);
+    VD_REQUIRE(op != DPS_DOWN || ((par == 2 || par == 4 || par == 8) && H % par == 0 && W % par == 0),
+               "vd_ddnm_step: down-sampling by %d of a %d x %d image (the factor is 2, 4 or 8 and divides both sides)", par, H, W);
+    VD_REQUIRE((long long)C * H * W * (type == OUT_BOTH ? 2 : 1) <= 0x7fffffffLL, "vd_ddnm_step: a sample of %d x %d x %d is too large", C, H, W);
+    VD_REQUIRE(noise != nullptr || k[5] == 0.f, "vd_ddnm_step: noise required when the noise scale is non-zero");
+    const bool last = last_step != 0;
+    DdnmArgs p = {step_common(xt, out, type, cfg, last_step, clip, xn, xdup, n, C, H * W), noise, meas, mask, sumsq, lam,
+                  last ? lam : k[4] * lam, op == DPS_MASK && last && lam == 1.f && (!noise || k[5] == 0.f), op, par, C, H, W};
+    VD_TRY(set_coefs("vd_ddnm_step", p.s.c, k, nullptr, 8));
+    const bool wide = all_aligned16(xt, out, noise, meas, mask, xn, xdup);
+    // the form follows from the shapes (G = 4 where a sample's measurement rows are whole multiples of 4), the access width from the bases
+    const bool four = (op == DPS_MASK ? p.s.N : (long long)H * W) % 4 == 0;
+    if (op == DPS_DOWN) {
+        if (par == 2) launch_rows(ddnm_step_kernel<DPS_DOWN, 1, 2, true>, ddnm_step_kernel<DPS_DOWN, 1, 2, false>, wide, n, 256, stream, p);
+        else if (par == 4) launch_rows(ddnm_step_kernel<DPS_DOWN, 1, 4, true>, ddnm_step_kernel<DPS_DOWN, 1, 4, false>, wide, n, 256, stream, p);
+        else launch_rows(ddnm_step_kernel<DPS_DOWN, 1, 8, true>, ddnm_step_kernel<DPS_DOWN, 1, 8, false>, wide, n, 256, stream, p);
+    } else if (op == DPS_MASK) {
+        if (four) launch_rows(ddnm_step_kernel<DPS_MASK, 4, 1, true>, ddnm_step_kernel<DPS_MASK, 4, 1, false>, wide, n, 256, stream, p);
+        else launch_rows(ddnm_step_kernel<DPS_MASK, 1, 1, false>, ddnm_step_kernel<DPS_MASK, 1, 1, false>, false, n, 256, stream, p);
+    } else {
+        if (four) launch_rows(ddnm_step_kernel<DPS_GRAY, 4, 1, true>, ddnm_step_kernel<DPS_GRAY, 4, 1, false>, wide, n, 256, stream, p);
+        else launch_rows(ddnm_step_kernel<DPS_GRAY, 1, 1, false>, ddnm_step_kernel<DPS_GRAY, 1, 1, false>, false, n, 256, stream, p);
+    }
+    VD_LAUNCH_CHECK("ddnm_step_kernel");
     return 0;
 }

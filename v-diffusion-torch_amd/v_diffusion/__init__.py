@@ -10,7 +10,8 @@ timestep resampling (``LossSecondMomentResampler``: v_diffusion/resample.py, lik
 (``GaussianDiffusion.p_sample_unipc``, ``unipc_coefs``: v_diffusion/unipc.py, likewise) and consistency distillation / training with
 multistep consistency sampling (``ConsistencyDiffusion``, ``GaussianDiffusion.p_sample_consistency``, ``consistency_coefs``,
 ``consistency_sample_coefs``, ``consistency_schedule``: v_diffusion/consistency.py, likewise) and Diffusion Posterior Sampling
-(``GaussianDiffusion.p_sample_dps``, ``dps_measure``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input gradient).  The other nine names the reference package re-exports (data loading,
+(``GaussianDiffusion.p_sample_dps``, ``dps_measure``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input gradient) and
+DDNM null-space restoration (``GaussianDiffusion.p_sample_ddnm``, ``ddnm_rule``, ``ddnm_pinv``: v_diffusion/ddnm.py, likewise).  The other nine names the reference package re-exports (data loading,
 config helpers, its Trainer / Evaluator: control plane, out of scope) are NOT re-implemented: when the environment
 variable ``VDIFF_REFERENCE_ROOT`` points at a checkout of the reference they are resolved lazily from it (loaded under
 the alias ``v_diffusion_ref`` so its relative imports stay inside the reference), which lets the reference's
@@ -21,6 +22,7 @@ import os
 import sys
 
 from .consistency import ConsistencyDiffusion, consistency_coefs, consistency_sample_coefs, consistency_schedule
+from .ddnm import ddnm_pinv, ddnm_rule
 from .diffusion import GaussianDiffusion, get_logsnr_schedule
 from .distill import DistillationDiffusion, distill_coefs
 from .dps import dps_measure, p_sample_dps
@@ -34,7 +36,7 @@ from .unipc import p_sample_unipc, unipc_coefs
 _HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusion", "distill_coefs", "solver_coefs", "threshold_rank",
         "dynamic_threshold", "resampling_schedule", "known_coefs", "jump_coefs", "encode_coefs", "slerp", "LossSecondMomentResampler",
         "unipc_coefs", "p_sample_unipc", "ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule",
-        "dps_measure", "p_sample_dps"]
+        "dps_measure", "p_sample_dps", "ddnm_rule", "ddnm_pinv"]
 _DELEGATED = ["get_dataloader", "DATA_INFO", "dict2str", "seed_all", "update_config", "fill_with_defaults", "Trainer",
               "Evaluator", "DummyScheduler"]
 _ref_pkg = None

@@ -96,6 +96,10 @@ EXT_EXPORTS = tuple(_EXT_SIGNATURES)
 DPS_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dps.h"),)
 _DPS_SIGNATURES = {name: sig for path in DPS_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
 DPS_EXPORTS = tuple(_DPS_SIGNATURES)
+# (... and each of those tables is held to its own fixture as it stands: vdiff_hip_ddnm.h, pinned by tests/golden/c_abi_ddnm.json)
+DDNM_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_ddnm.h"),)
+_DDNM_SIGNATURES = {name: sig for path in DDNM_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
+DDNM_EXPORTS = tuple(_DDNM_SIGNATURES)
 
 _lib = None
 
@@ -109,7 +113,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_DPS_SIGNATURES}.items():
+        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_DPS_SIGNATURES, **_DDNM_SIGNATURES}.items():
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():
@@ -1030,6 +1034,15 @@ def dps_step(xt, out, noise, dxin, dxt, sumsq, k8, zeta, mot, cfg, last, clip, x
     arr = _host_floats(k8, 8)
     _check(lib().vd_dps_step(ptr(xt), ptr(out), ptr(noise), ptr(dxin), ptr(dxt), ptr(sumsq), arr, float(zeta), mot, int(cfg), int(last),
                              int(clip), ptr(xn), ptr(xdup), n, Cc, HW, stream()), "vd_dps_step")
+
+
+def ddnm_step(xt, out, noise, meas, mask, k8, lam, mot, cfg, last, clip, op, par, xn, xdup, sumsq, n, Cc, H, W):
+    """sample_step, then xn += cw * A^+(meas - A g) on every preimage, g the guided x0 prediction and cw = lam on the last step, else
+    c2 * lam (vd_ddnm_step).  Selected: lam = 0 leaves sample_step's row, a mask element 0 has no measurement.  op, par, mask, meas:
+    dps_residual's; sumsq (optional, n floats) receives sum r^2 over the measured elements of each sample.  xn may alias xt"""
+    arr = _host_floats(k8, 8)
+    _check(lib().vd_ddnm_step(ptr(xt), ptr(out), ptr(noise), ptr(meas), ptr(mask), arr, float(lam), mot, int(cfg), int(last), int(clip),
+                              int(op), int(par), ptr(xn), ptr(xdup), ptr(sumsq), n, Cc, H, W, stream()), "vd_ddnm_step")
 
 
 def lsm_draw(hist, count, u, cdf, t_out, idx_out, w_out, T, K, B, uniform_prob):

@@ -924,6 +924,30 @@ class GaussianDiffusion:
         return p_sample_dps(self, denoise_fn, measurement, operator, shape, label, device, seed, zeta, use_ddim, clip_denoised)
 
     @torch.inference_mode()
+    def p_sample_ddnm(self, denoise_fn, measurement, operator, shape, label=None, device=None, seed=None, sigma_y=0.0, lam=None,
+                      use_ddim=False, jump_length=1, resamplings=1, clip_denoised=True, return_residuals=False):
+        """Reverse chain conditioned on a measurement y = A x (+ noise) by the Denoising Diffusion Null-space Model (extension,
+        v_diffusion/ddnm.py; Wang, Yu, Zhang 2023): training-free restoration with an existing checkpoint and WITHOUT a gradient.
+        ``operator``, ``measurement`` and ``shape`` are ``p_sample_dps``'s: ``("mask", mask)``, ``("down", f)`` or ``("gray",)``, each
+        with a closed-form pseudo-inverse A^+ (``v_diffusion.ddnm_pinv``).  Every step is the ordinary posterior step (DDPM, or DDIM with
+        ``use_ddim``) on the corrected prediction g + lam * A^+(y - A g), g the step's guided, clipped x0 prediction: one ordinary
+        network call and ONE launch (vd_ddnm_step); the last step returns the corrected prediction, so with ``sigma_y=0`` the result
+        satisfies A x = y to rounding, and exactly where a mask is 1.  ``sigma_y`` > 0 (the measurement's noise, DDNM+): lam and the
+        step's noise scale follow ``v_diffusion.ddnm_rule``.  ``lam``: None (the rule), a float in [0, 1] or ``sample_timesteps`` floats
+        indexed by the grid index a step lands on; ``lam=0.0`` is ``p_sample(seed=..., use_ddim=...)`` bit for bit.  With ``resamplings``
+        > 1 the chain jumps forward by ``jump_length`` grid steps at every resampling point and denoises again (the paper's time travel;
+        ``resampling_schedule``, as ``p_sample_inpaint``).  Draws, from one generator seeded with ``seed``: x_T, then one per transition
+        -- the step's noise or the jump's.  ``return_residuals=True`` returns ``(x, res)``, res the (reverse steps, B) fp32 device tensor
+        of ||y - A g|| per step and sample, written without a host synchronisation.  Refused before any launch:
+        ``model_var_type="learned"``, ``x0eps_coef=True``, an unknown operator, a factor outside {2, 4, 8} or not dividing H and W, a
+        measurement of another shape, a negative or non-finite ``sigma_y``, ``sigma_y`` > 0 with ``use_ddim`` (no step noise is left to
+        absorb the measurement's), a ``lam`` outside [0, 1] or a list of the wrong length, a bad ``jump_length`` / ``resamplings``, CPU
+        tensors.  Returns the result ON THE GPU."""
+        from .ddnm import p_sample_ddnm
+        return p_sample_ddnm(self, denoise_fn, measurement, operator, shape, label, device, seed, sigma_y, lam, use_ddim, jump_length,
+                             resamplings, clip_denoised, return_residuals)
+
+    @torch.inference_mode()
     def p_invert_noise(self, denoise_fn, x_0, label=None, device=None, seed=None, start=None, clip_denoised=True):
         """DDPM noise-space inversion of a given image batch (extension, v_diffusion/invert.py; Huberman-Spiegelglas et al. 2024):
         ``(x_start, maps)`` such that ``p_sample_replay(denoise_fn, x_start, maps, label)`` returns ``x_0``, for any network.  With
