@@ -242,6 +242,28 @@ int vd_conv3x3_wgrad_wino43_v(const float* V, const float* dy, int64_t lddy, int
                               float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws, size_t ws_bytes,
                               int32_t phase, void* stream);
 
+/* Input gradient of the 3x3 convolution through PLANES (csrc/wino43.hip), the exact adjoint of vd_conv3x3_wino43_fwd_planes: with
+ * dM = A dY A^T ([T/16][36][16][Cout], vd_conv3x3_wino43_dm_floats floats: the image the weight gradient's transform pass makes of dy, written
+ * into the caller's buffer by vd_conv3x3_wino43_dy_image -- same device code, same bits), the 36 products dV[xi] = dM[xi] Ut[xi] run as one
+ * batched launch of the split-operand tile engine (Ut = the forward's plane image transposed, packed from the raw kernel w_oihw) and an
+ * HBM-bound pass overlap-adds the 6x6 patches B dV B^T into dx[nimg][H][W][:Cin] (every element written once, fixed summation order,
+ * channels >= Cin of a pitched dx untouched).  32x32 and 16x16 images.  ws: vd_conv3x3_wino43_dgrad_planes_ws_bytes.  phase: 7 = everything,
+ * or 1 (pack), 2 (GEMMs), 4 (overlap-add) for per-kernel timing.
+ * vd_conv3x3_wgrad_wino43_vm: the weight gradient with BOTH images given (no transform pass; phase 7, 2 or 4), bitwise the result of
+ * vd_conv3x3_wgrad_wino43_v -- so a training step transforms dy once for both gradients.
+ * vd_conv3x3_dgrad_planes_preferred: host rule (occupancy floor + same-box measurement) for where this form, given dM, beats the fused
+ * F(4x4,3x3) input-gradient kernel; training steps only. */
+size_t vd_conv3x3_wino43_dm_floats(int32_t nimg, int32_t H, int32_t W, int32_t Cout);
+int vd_conv3x3_wino43_dy_image(const float* dy, int64_t lddy, int32_t nimg, int32_t H, int32_t W, int32_t Cout, float* dM, void* stream);
+int vd_conv3x3_wgrad_wino43_vm(const float* V, const float* dM, int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout,
+                               float* dw_oihw, float* dbias, int32_t Cin_w, int32_t Cout_w, int32_t accumulate, float* ws, size_t ws_bytes,
+                               int32_t phase, void* stream);
+int vd_conv3x3_wino43_dgrad_planes_supported(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int64_t lddx);
+size_t vd_conv3x3_wino43_dgrad_planes_ws_bytes(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout);
+int vd_conv3x3_dgrad_planes_preferred(int32_t nimg, int32_t H, int32_t W, int32_t Cin, int32_t Cout, int32_t training);
+int vd_conv3x3_wino43_dgrad_planes(const float* dM, const float* w_oihw, float* dx, int64_t lddx, int32_t nimg, int32_t H, int32_t W,
+                                   int32_t Cin, int32_t Cout, float* ws, size_t ws_bytes, int32_t phase, void* stream);
+
 /* all 3x3 kernels of a network in one launch: items_dev = [n][8] int64 {w, uf, ud, Cout, Cin, tiled, 0, first 256-thread block};
  * tiled = 1 (Cout, Cin multiples of 16): the tensor takes (Cout/16)*(Cin/16) blocks of one 16x16 tile, else ceil(Cout*Cin/256) */
 int vd_wino_pack_batched(const int64_t* items_dev, int32_t n, int64_t total_blocks, void* stream);
@@ -675,6 +697,67 @@ int vd_noise_extract(const float* xt, const float* out, const float* x0, const f
  * aligned, scalar otherwise (the two forms add in different orders and may differ in the last bit of a weight). */
 int vd_slerp_rows(const float* a, const float* b, const float* frac, const float* frac_dev, float* out, float* w_out, int32_t n, int64_t N,
                   void* stream);
+/* Diffusion Posterior Sampling (Chung et al. 2023, Algorithm 1; csrc/diffusion.hip): the two launches of one reverse step, either side
+ * of the network's input gradient.  Conventions of the reverse steps above: images NCHW fp32; k = the 8 host floats of
+ * vd_sample_step {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3}; out = n*(1+cfg) rows, cond and uncond interleaved, of C channels
+ * (2C for "both", model_out_type 3).  Both return 1 before any launch on a bad model_out_type or op, a null required buffer or
+ * n, C, H, W (HW) < 1.
+ *
+ * The measurement operator A acts per sample on the guided prediction g (C, H, W):
+ *   op 0  mask      A g = M (.) g, M = mask[n][par][H][W] with par = 1 or C channels, values in [0, 1];   A^T r = M (.) r
+ *   op 1  box down-sampling by par in {2, 4, 8} (H, W multiples of it, refused otherwise): the mean over par x par blocks,
+ *         (C, H/par, W/par);   A^T r = r / par^2 on every element of the block
+ *   op 2  grey      the mean over the channels, (1, H, W);   A^T r = r / C on every channel
+ *
+ * vd_dps_residual: per branch p = a0*xt + b0x*out (+ b0e*out_eps), xhat = clip ? clamp(p, -1, 1) : p, and the pass mask m = 1 where
+ *   -1 <= p <= 1 or clip is off (torch.clamp's subgradient, boundary included).  g = xhat_c + w (xhat_c - xhat_u) with cfg, else xhat;
+ *   r = meas - A g (meas: n samples of A's image);  sumsq[b] = sum r^2 over the sample, in a fixed order (one workgroup per sample, no
+ *   atomics, no workspace: the same call gives the same bits);  u = -A^T r.  Cotangents of (1/2)||r||^2, unnormalised:
+ *     dout (the shape of out)  cond rows (1 + w) m_c u, uncond rows -w m_u u (without cfg: m u), times b0x on the first C channels and
+ *                              b0e on the second C of "both"
+ *     dxt[n][C][H][W]          a0 [(1 + w) m_c - w m_u] u   (a0 m u without cfg)
+ *     x0hat (optional)         g
+ * vd_dps_step: vd_sample_step's row (same device helpers: prediction, clip, guided mean, last_step, noise), then
+ *     xn -= zeta / sqrt(sumsq[b]) * (dxt[b] + dxin[2b] + dxin[2b+1])      (dxt[b] + dxin[b] without cfg)
+ *   with dxin (n*(1+cfg) rows of C*HW) the network's input gradient of dout.  The term is selected, not multiplied: with zeta = 0 or
+ *   sumsq[b] = 0 row b is vd_sample_step's bit for bit and a NaN in its dxin / dxt reaches nothing; a sumsq[b] that is not finite makes
+ *   that row NaN and leaves the others alone.  Writes xn and the optional xdup (rows 2b, 2b+1); xn may alias xt.  dwordx4 accesses when
+ *   C*HW is a multiple of 4 and every base is 16-byte aligned, scalar otherwise: the same bits. */
+int vd_dps_residual(const float* xt, const float* out, const float* meas, const float* mask, const float* k, int32_t model_out_type,
+                    int32_t cfg, int32_t clip, int32_t op, int32_t par, float* dout, float* dxt, float* sumsq, float* x0hat, int32_t n,
+                    int32_t C, int32_t H, int32_t W, void* stream);
+int vd_dps_step(const float* xt, const float* out, const float* noise, const float* dxin, const float* dxt, const float* sumsq,
+                const float* k, float zeta, int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip, float* xn, float* xdup,
+                int32_t n, int32_t C, int32_t HW, void* stream);
+/* Denoising Diffusion Null-space Model (Wang, Yu, Zhang 2023; csrc/diffusion.hip): one reverse step whose x0 prediction takes its
+ * range-space part from a measurement meas = A x and keeps the network's null-space part, g_hat = g + lam * A^+(meas - A g) -- ONE launch,
+ * no gradient.  Conventions of the reverse steps above and of the DPS entries: images NCHW fp32; k = the 8 host floats of
+ * vd_sample_step {a0, b0x, b0e, c1, c2, noise_scale, w_guide, c3}; out = n*(1+cfg) rows, cond and uncond interleaved, of C channels (2C
+ * for "both", model_out_type 3); op, par, mask, meas as vd_dps_residual takes them:
+ *   op 0  mask      A g = M (.) g, M = mask[n][par][H][W] with par = 1 or C channels, values in [0, 1];   A^+ r = r / M where M > 0
+ *   op 1  box down-sampling by par in {2, 4, 8}: the mean over par x par blocks, (C, H/par, W/par);   A^+ r = r on every element of the block
+ *   op 2  grey      the mean over the channels, (1, H, W);   A^+ r = r on every channel
+ *
+ * Per element of the preimage of measurement element j (1, par^2 or C elements; the preimages tile the image):
+ *   v  = vd_sample_step's value, the same device helpers: the clipped prediction per branch, the mean c1*xt + c2*x0_hat (x0_hat itself on
+ *        the last step), the guided mean, + k[5]*noise when noise is given
+ *   g  = the guided clipped prediction (vd_dps_residual's);  A g = the preimage summed in fp64 and rounded once (vd_dps_residual's rule)
+ *   r  = meas_j - A g;   d = A^+ r;   xn = fma(cw, d, v) with cw = lam on the last step, else c2*lam rounded once per launch
+ * Selected, not multiplied:
+ *   lam == 0              the row is vd_sample_step's bit for bit; without sumsq, meas and mask are not read
+ *   mask, M == 0          no correction and no share of sumsq: a NaN in meas there reaches nothing
+ *   mask, M == 1, last step, lam == 1 and no noise term (noise null or k[5] == 0):  xn = meas bit for bit
+ * sumsq (optional, n floats): sumsq[b] = sum of r^2 over the measured elements of sample b (mask: those with M > 0), added in fp64 in a
+ * fixed order (one workgroup per sample, no atomics, no workspace: the same call gives the same bits), stored as fp32; null skips it.
+ * Writes xn and the optional xdup (rows 2b, 2b+1); xn may alias xt.  dwordx2 / dwordx4 row accesses when every base is 16-byte aligned,
+ * scalar otherwise: the same bits, sumsq included.
+ * Returns 1 before any launch on what vd_dps_residual refuses -- a bad model_out_type or op, a null required buffer (xt, out, meas, k, xn,
+ * the mask of op 0), n, C, H, W < 1, a mask of neither 1 nor C channels, a factor outside {2, 4, 8} or not dividing H and W -- and on
+ * noise == null with k[5] != 0, and on a sample whose output row (C*H*W floats, twice that for "both") does not fit 2^31 - 1: offsets
+ * inside a sample are 32-bit. */
+int vd_ddnm_step(const float* xt, const float* out, const float* noise, const float* meas, const float* mask, const float* k, float lam,
+                 int32_t model_out_type, int32_t cfg, int32_t last_step, int32_t clip, int32_t op, int32_t par, float* xn, float* xdup,
+                 float* sumsq, int32_t n, int32_t C, int32_t H, int32_t W, void* stream);
 
 /* ------------------------------------------------------------------ loss-aware timestep resampling (resample.hip)
  * Nichol & Dhariwal 2021, section 3.3: timesteps drawn in proportion to sqrt(E[L_t^2]) and the loss reweighted by 1/(T p_t), with the

@@ -3,7 +3,7 @@ tests/test_dps_cpu.py and tests/test_dps_gpu.py.  Written from the formulas, not
 
     operators         A g = M (.) g  |  the mean over f x f blocks  |  the mean over the channels;   A^T their adjoints
     residual          g = the guided, clipped x0 prediction of the step;  r = meas - A g;  sumsq = sum r^2 per sample;  u = -A^T r
-    cotangents        of (1/2)||r||^2:  dout = d/d out,  dxt = d/d x_t with out held fixed (the closed forms of include/vdiff_hip_dps.h)
+    cotangents        of (1/2)||r||^2:  dout = d/d out,  dxt = d/d x_t with out held fixed (the closed forms at vd_dps_residual in include/vdiff_hip.h)
     step              x_s = [the ordinary reverse step] - zeta / sqrt(sumsq) (dxt + the rows of dxin of the sample),  dxin = the
                       network's VJP of dout;  the term is selected: zeta = 0 or sumsq = 0 leave the ordinary step
 

@@ -4,9 +4,8 @@
     and the variance identity (c2 lam sigma_y)^2 + noise_scale'^2 = noise_scale^2 wherever lam = 1;
   * the pseudo-inverses: A A^+ y = y on the range of A and A^+ A A^+ = A^+ for the three operators, fp64 on CPU tensors, hard masks,
     ``v_diffusion.ddnm_pinv`` against the restatement tests/ddnm_ref.py;
-  * every refusal that needs no device, the exported names, the C ABI fixture of include/vdiff_hip_ddnm.h."""
+  * every refusal that needs no device, the exported names."""
 import ctypes
-import json
 import math
 import os
 import sys
@@ -15,15 +14,12 @@ import pytest
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-if __name__ == "__main__":
-    sys.path[:0] = [os.path.dirname(_HERE), os.path.join(os.path.dirname(_HERE), "v-diffusion-torch_amd")]
 sys.path.insert(0, _HERE)
 import ddnm_ref as R                                              # noqa: E402
 import dps_ref as DR                                              # noqa: E402
 from v_diffusion import _hip                                      # noqa: E402
 
 F64 = torch.float64
-DDNM_ABI = os.path.join(_HERE, "golden", "c_abi_ddnm.json")
 
 
 def rnd(shape, seed, scale=1.0):
@@ -206,36 +202,7 @@ def test_the_names_are_exported_and_inherited():
     assert callable(_hip.ddnm_step)
 
 
-# ------------------------------------------------------------------------------------------------ 4. the C ABI of the new header
-def _parsed_ddnm_abi():
-    """the declarations of include/vdiff_hip_ddnm.h as _hip reads them: [[name, return type, [parameter, ...]], ...] in header order"""
-    (path,) = _hip.DDNM_HEADER_PATHS
-    with open(path) as f:
-        product, probe = _hip._parse_header(f.read())
-    assert not probe
-    return [[name, ret, params] for name, (ret, params) in product.items()]
-
-
-def test_the_new_entry_is_as_recorded_and_exported():
-    """name, return type and each parameter's type and name of the entry of include/vdiff_hip_ddnm.h against its fixture
-    (python tests/test_ddnm_cpu.py --record rewrites it, for a change that is MEANT to alter it); it shadows no entry of the other
-    headers, is bound with the types the declaration states and exported by the library"""
-    lib = _hip.lib()
-    with open(DDNM_ABI) as f:
-        want = json.load(f)
-    got = _parsed_ddnm_abi()
-    assert [e[0] for e in got] == [e[0] for e in want] == ["vd_ddnm_step"], "entry points: names or order moved"
-    for g, w in zip(got, want):
-        assert g == w, f"{w[0]} moved: recorded {w[1]} ({', '.join(w[2])}), the header now says {g[1]} ({', '.join(g[2])})"
-    assert list(_hip.DDNM_EXPORTS) == [e[0] for e in want]
-    assert not set(_hip.DDNM_EXPORTS) & (set(_hip.EXPORTS) | set(_hip.EXT_EXPORTS) | set(_hip.DPS_EXPORTS))
-    by_value = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
-    for name, ret, params in want:
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and ret == "int"
-        assert list(fn.argtypes) == [ctypes.c_void_p if "*" in q else by_value[q.rpartition(" ")[0]] for q in params], name
-
-
+# ------------------------------------------------------------------------------------------------ 4. the C entry
 def test_the_entry_refuses_before_any_launch():
     """what vd_dps_residual refuses -- a bad model_out_type or op, a null required buffer, n, C, H, W < 1, a mask width that is neither 1
     nor C, a factor outside {2, 4, 8} or not dividing the image -- and a missing noise with a noise scale: 1, with the reason, and
@@ -259,11 +226,3 @@ def test_the_entry_refuses_before_any_launch():
     for f, H, W in ((3, 6, 6), (16, 16, 16), (1, 4, 4), (2, 5, 4), (4, 8, 6), (8, 8, 12)):
         assert r(op=1, par=f, H=H, W=W) == 1 and "down-sampling" in err(), (f, H, W)
     assert r(noise=None) == 1 and "noise" in err()
-
-
-if __name__ == "__main__":
-    assert sys.argv[1:] == ["--record"], __doc__
-    with open(DDNM_ABI, "w") as _f:
-        json.dump(_parsed_ddnm_abi(), _f, indent=1)
-        _f.write("\n")
-    print(f"{len(_parsed_ddnm_abi())} entry points -> {DDNM_ABI}")

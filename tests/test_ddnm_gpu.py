@@ -328,7 +328,7 @@ def test_noisy_measurement_follows_the_rule(vd, monkeypatch, op, par):
 def test_time_travel_draw_order_and_call_count(vd, monkeypatch):
     """(jump_length, resamplings) = (2, 2): one generator seeded on the device; the initial state, then one image-shaped draw per
     transition and nothing else; T + (r - 1) j P network calls; the chain against fp64 over the replayed draws"""
-    import v_diffusion.ddnm as ddnm
+    import v_diffusion.restore as restore          # (the chain is opened, and every draw made, there)
     T, shape, seed, j, r = T_CHAIN, CHAIN_SHAPE, 13, 2, 2
     gd, y, mask, operator, meas = chain_setup(vd, "down", 2, False)
     sched = vd.resampling_schedule(T, j, r)
@@ -347,7 +347,7 @@ def test_time_travel_draw_order_and_call_count(vd, monkeypatch):
             t = real(*a, **kw)
             seen.append((kw.get("generator"), t.clone()))
             return t
-    monkeypatch.setattr(ddnm, "torch", Recording())
+    monkeypatch.setattr(restore, "torch", Recording())
     got, res = gd.p_sample_ddnm(D.Stub(calls=calls), meas, operator, shape, seed=seed, jump_length=j, resamplings=r, return_residuals=True)
     monkeypatch.undo()
     want = D.replay(seed, shape, len(sched))

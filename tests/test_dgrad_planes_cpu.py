@@ -3,15 +3,10 @@ vd_conv3x3_dgrad_planes_preferred, the refusals of the new entry points (every o
 tile engine each case of tests/test_dgrad_planes_gpu.py plans to."""
 import ctypes
 import importlib.util
-import json
 import os
-import sys
 
 import pytest
 
-if __name__ == "__main__":
-    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path[:0] = [_root, os.path.join(_root, "v-diffusion-torch_amd")]
 from v_diffusion import _hip
 
 
@@ -22,36 +17,6 @@ def lib():
 
 def _err(lib):
     return lib.vd_last_error().decode(errors="replace")
-
-
-EXT_ABI = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "c_abi_dgrad_planes.json")
-
-
-def _parsed_ext_abi():
-    """the declarations of include/vdiff_hip_dgrad_planes.h as _hip reads them: [[name, return type, [parameter, ...]], ...] in header order"""
-    (path,) = _hip.EXT_HEADER_PATHS
-    with open(path) as f:
-        product, probe = _hip._parse_header(f.read())
-    assert not probe
-    return [[name, ret, params] for name, (ret, params) in product.items()]
-
-
-def test_the_new_entries_are_as_recorded_and_exported(lib):
-    """name, position, return type and each parameter's type and name of every entry of the extension header against its fixture
-    (python tests/test_dgrad_planes_cpu.py --record rewrites it, for a change that is MEANT to alter one); none of them shadows an entry of
-    vdiff_hip.h, all are bound with the types the declaration states and exported by the library"""
-    with open(EXT_ABI) as f:
-        want = json.load(f)
-    got = _parsed_ext_abi()
-    assert [e[0] for e in got] == [e[0] for e in want], "entry points: names or order moved"
-    for g, w in zip(got, want):
-        assert g == w, f"{w[0]} moved: recorded {w[1]} ({', '.join(w[2])}), the header now says {g[1]} ({', '.join(g[2])})"
-    assert list(_hip.EXT_EXPORTS) == [e[0] for e in want] and not set(_hip.EXT_EXPORTS) & set(_hip.EXPORTS)
-    by_value = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t}
-    for name, ret, params in want:
-        fn = getattr(lib, name)
-        assert fn.restype is {"int": ctypes.c_int, "size_t": ctypes.c_size_t}[ret]
-        assert list(fn.argtypes) == [ctypes.c_void_p if "*" in q else by_value[q.rpartition(" ")[0]] for q in params], name
 
 
 def test_supported_truth_table(lib):
@@ -147,11 +112,3 @@ def test_plans_of_the_gpu_cases(lib):
     # the step's own shapes: the 128 x 256 form
     for ci in (256, 512):
         assert _hip.tile_fields(lib.vd_gemm_plan_tile(8192, ci, 256, _hip.ROW, _hip.ROW, 36, 0, 0))[1:] == gpu.WIDE
-
-
-if __name__ == "__main__":
-    assert sys.argv[1:] == ["--record"], __doc__
-    with open(EXT_ABI, "w") as _f:
-        json.dump(_parsed_ext_abi(), _f, indent=1)
-        _f.write("\n")
-    print(f"{len(_parsed_ext_abi())} entry points -> {EXT_ABI}")

@@ -4,10 +4,9 @@
     none of the weight-gradient, GroupNorm-parameter, FiLM or embedding launches, and the d/dx chain of the full pass launch for launch;
   * the fp64 restatement tests/dps_ref.py against itself: <A x, r> = <x, A^T r>, the closed-form cotangents against torch autograd, and
     a chain that does reduce the measurement residual;
-  * every refusal that needs no device, the C ABI fixture of include/vdiff_hip_dps.h, the exported names."""
+  * every refusal that needs no device, the exported names."""
 import collections
 import ctypes
-import json
 import os
 import sys
 
@@ -15,15 +14,12 @@ import pytest
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-if __name__ == "__main__":
-    sys.path[:0] = [os.path.dirname(_HERE), os.path.join(os.path.dirname(_HERE), "v-diffusion-torch_amd")]
 sys.path.insert(0, _HERE)
 import dps_ref as R                                               # noqa: E402
 import test_engine_trace_cpu as TR                                # noqa: E402  (the Recorder and the model table: imported, not copied)
 from v_diffusion import _hip                                      # noqa: E402
 
 F64 = torch.float64
-DPS_ABI = os.path.join(_HERE, "golden", "c_abi_dps.json")
 MOTS = ("v", "eps", "x0", "both")
 # the wrappers of the d/dx chain other than the GEMMs (which the weight gradients share): each must run exactly as often as in the full pass
 DX_CHAIN = ("gn_apply_bwd", "attn_bwd", "softmax_rows_bwd", "conv3x3_wino43_dgrad_planes", "conv3x3_wino43_dy_image",
@@ -295,35 +291,7 @@ def test_the_names_are_exported_and_inherited():
     assert _hip.DPS_OPS == {"mask": 0, "down": 1, "gray": 2}
 
 
-# ------------------------------------------------------------------------------------------------ 4. the C ABI of the new header
-def _parsed_dps_abi():
-    """the declarations of include/vdiff_hip_dps.h as _hip reads them: [[name, return type, [parameter, ...]], ...] in header order"""
-    (path,) = _hip.DPS_HEADER_PATHS
-    with open(path) as f:
-        product, probe = _hip._parse_header(f.read())
-    assert not probe
-    return [[name, ret, params] for name, (ret, params) in product.items()]
-
-
-def test_the_new_entries_are_as_recorded_and_exported():
-    """name, position, return type and each parameter's type and name of every entry of include/vdiff_hip_dps.h against its fixture
-    (python tests/test_dps_cpu.py --record rewrites it, for a change that is MEANT to alter one); none shadows an entry of the other
-    headers, all are bound with the types the declaration states and exported by the library"""
-    lib = _hip.lib()
-    with open(DPS_ABI) as f:
-        want = json.load(f)
-    got = _parsed_dps_abi()
-    assert [e[0] for e in got] == [e[0] for e in want] == ["vd_dps_residual", "vd_dps_step"], "entry points: names or order moved"
-    for g, w in zip(got, want):
-        assert g == w, f"{w[0]} moved: recorded {w[1]} ({', '.join(w[2])}), the header now says {g[1]} ({', '.join(g[2])})"
-    assert list(_hip.DPS_EXPORTS) == [e[0] for e in want] and not set(_hip.DPS_EXPORTS) & (set(_hip.EXPORTS) | set(_hip.EXT_EXPORTS))
-    by_value = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float}
-    for name, ret, params in want:
-        fn = getattr(lib, name)
-        assert fn.restype is ctypes.c_int and ret == "int"
-        assert list(fn.argtypes) == [ctypes.c_void_p if "*" in q else by_value[q.rpartition(" ")[0]] for q in params], name
-
-
+# ------------------------------------------------------------------------------------------------ 4. the C entries
 def test_the_entries_refuse_before_any_launch():
     """bad model_out_type or op, a null required buffer, n, C, H, W < 1, a mask width that is neither 1 nor C, a factor outside
     {2, 4, 8} or not dividing the image: 1, with the reason, and nothing launched (the addresses are never dereferenced)"""
@@ -356,11 +324,3 @@ def test_the_entries_refuse_before_any_launch():
     for name in ("n", "C", "HW"):
         assert s(**{name: 0}) == 1 and "empty" in err(), name
     assert s(noise=None) == 1 and "noise" in err()
-
-
-if __name__ == "__main__":
-    assert sys.argv[1:] == ["--record"], __doc__
-    with open(DPS_ABI, "w") as _f:
-        json.dump(_parsed_dps_abi(), _f, indent=1)
-        _f.write("\n")
-    print(f"{len(_parsed_dps_abi())} entry points -> {DPS_ABI}")

@@ -503,7 +503,7 @@ def test_zeta_zero_is_p_sample(vd, ddim):
 
 def test_draw_order(vd, monkeypatch):
     """one generator, seeded on the device; the initial state, then one image-shaped draw per step and nothing else"""
-    import v_diffusion.dps as dps
+    import v_diffusion.restore as restore          # (the chain is opened, and every draw made, there)
     T, shape, seed = 5, (2, 3, 8, 8), 13
     gd = make_gd(vd, T)
     seen = []
@@ -518,7 +518,7 @@ def test_draw_order(vd, monkeypatch):
             t = real(*a, **kw)
             seen.append((kw.get("generator"), t.clone()))
             return t
-    monkeypatch.setattr(dps, "torch", Recording())
+    monkeypatch.setattr(restore, "torch", Recording())
     meas = torch.zeros((2, 1, 8, 8), device=DEV)
     gd.p_sample_dps(Stub(), meas, ("gray",), shape, seed=seed, zeta=0.3)
     monkeypatch.undo()

@@ -95,6 +95,10 @@ def test_every_entry_binds_by_the_type_rule():
                 assert a is params[ctype], f"{name}: parameter `{p}` bound as {a}"
     assert seen == set(params)
     assert _hip.EXPORTS == tuple(_hip._SIGNATURES) and _hip._SIGNATURES["vd_gemm"][1][0] is C.POINTER(_hip.GemmDesc)
+    lib = _hip.lib()                                                        # ... and the loaded library carries exactly the table's types
+    for name, (res, args) in _hip._SIGNATURES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == args, f"{name}: bound as {fn.restype} {fn.argtypes}"
 
 
 def test_the_header_parser_refuses_what_it_cannot_bind(monkeypatch):
@@ -112,6 +116,10 @@ def test_the_header_parser_refuses_what_it_cannot_bind(monkeypatch):
         _hip._ctypes_of("vd_ret", *bad["vd_ret"])
     with pytest.raises(RuntimeError, match="declaration"):                   # a declaration the pattern cannot read is not dropped silently
         _hip._parse_header("int vd_ok(void);\nint vd_callback(void (*fn)(int), void* stream);\n")
+    for twice in ("int vd_ok(void);\nint vd_dup(int32_t n);\nsize_t vd_dup(void);\n",              # a name declared twice is named, not collapsed:
+                  "int vd_dup(void);\n#ifdef VD_PROBES\nint vd_dup(void);\n#endif\n"):           # in one table, or once in each
+        with pytest.raises(RuntimeError, match="vd_dup is declared twice"):
+            _hip._parse_header(twice)
     monkeypatch.setattr(_hip, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
     with pytest.raises(RuntimeError, match="no_such_header.h not found"):
         _hip._header_signatures()

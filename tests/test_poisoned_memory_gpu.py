@@ -1,6 +1,6 @@
 """Every kernel entry that takes pitched operands, a scratch buffer or a non-accumulating destination, run twice: once as its own parity
 test runs it (pitch columns 3.0, scratch as the previous launch left it) and checked against fp64 with that test's bound, then again with
-NaN in everything the contract of include/vdiff_hip.h / vdiff_hip_dgrad_planes.h says is not read:
+NaN in everything the contract of include/vdiff_hip.h says is not read:
 
   pitch columns of the sources (from the padded channel count up to the pitch), every cached scratch buffer of v_diffusion._hip (whole,
   all streams: tests/poison.py), the real part of every destination of a non-accumulating call, every statistics-partial / colsum side

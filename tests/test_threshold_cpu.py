@@ -114,7 +114,7 @@ def test_restated_step_and_chain_agree_with_the_solver_restatement():
     assert torch.equal(gp, g) and torch.equal(xn, R.step(x, g, hist, table[3].double())) and bool((s == 1.0).all())
 
 
-def test_c_abi_declares_the_two_entries():
+def test_the_two_entries_have_public_names_and_wrappers():
     """(declarations and ctypes signatures of the entry points: tests/test_host_cpu.py pins the whole C ABI)"""
     import v_diffusion as vd
     from v_diffusion import _hip

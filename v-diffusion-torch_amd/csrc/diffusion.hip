@@ -11,8 +11,6 @@
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 // Device side first, then the host helpers (launch, coefficient carrier, the refusals every entry shares), then the C entries.
 #include "common.h"
-#include "../../include/vdiff_hip_dps.h"
-#include "../../include/vdiff_hip_ddnm.h"
 
 namespace {
 
@@ -2001,7 +1999,7 @@ extern "C" int vd_slerp_rows(const float* a, const float* b, const float* frac, 
     return 0;
 }
 
-// (include/vdiff_hip_dps.h.  No device-resident coefficients: the chain has no captured-graph form)
+// (Diffusion Posterior Sampling.  No device-resident coefficients: the chain has no captured-graph form)
 extern "C" int vd_dps_residual(const float* xt, const float* out, const float* meas, const float* mask, const float* k, int32_t type,
                                int32_t cfg, int32_t clip, int32_t op, int32_t par, float* dout, float* dxt, float* sumsq, float* x0hat,
                                int32_t n, int32_t C, int32_t H, int32_t W, void* stream) {
@@ -2032,7 +2030,7 @@ extern "C" int vd_dps_step(const float* xt, const float* out, const float* noise
     return 0;
 }
 
-// (include/vdiff_hip_ddnm.h.  Host coefficients only, as the DPS entries: the chain has no captured-graph form)
+// (DDNM.  Host coefficients only, as the DPS entries: the chain has no captured-graph form)
 extern "C" int vd_ddnm_step(const float* xt, const float* out, const float* noise, const float* meas, const float* mask, const float* k,
                             float lam, int32_t type, int32_t cfg, int32_t last_step, int32_t clip, int32_t op, int32_t par, float* xn,
                             float* xdup, float* sumsq, int32_t n, int32_t C, int32_t H, int32_t W, void* stream) {

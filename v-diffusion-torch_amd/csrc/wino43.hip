@@ -35,7 +35,6 @@
 //     memory (36 linear DMA pieces) and a lane's fragment for both 16-channel blocks
 //     and both k-steps is one conflict-free ds_read_b128.
 #include "common.h"
-#include "../../include/vdiff_hip_dgrad_planes.h"
 #include <stdlib.h>
 #include <type_traits>
 

@@ -53,6 +53,8 @@ def _parse_header(text):
         if len(decls) != len(re.findall(r"\bvd_\w+\s*\(", part)):
             raise RuntimeError(f"{HEADER_PATH}: a vd_* declaration is not of the form `type vd_name(parameters);`")
         for ret, name, params in decls:
+            if name in tables[0] or name in tables[1]:
+                raise RuntimeError(f"{HEADER_PATH}: {name} is declared twice")
             params = [" ".join(q.split()) for q in params.split(",")]
             tables[i % 2][name] = (" ".join(ret.split()), [] if params == ["void"] else params)
     return tables
@@ -73,11 +75,10 @@ def _ctypes_of(name, ret, params):
     return _RETURNS[ret], [arg(q) for q in params]
 
 
-def _header_signatures(path=None):
-    path = path or HEADER_PATH
-    if not os.path.exists(path):
-        raise RuntimeError(f"{path} not found: the ctypes binding is read from the C headers of the source tree")
-    with open(path) as f:
+def _header_signatures():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} not found: the ctypes binding is read from the C header of the source tree")
+    with open(HEADER_PATH) as f:
         tables = _parse_header(f.read())
     return [{name: _ctypes_of(name, *decl) for name, decl in t.items()} for t in tables]
 
@@ -87,19 +88,6 @@ def _header_signatures(path=None):
 # library
 _SIGNATURES, PROBE_EXPORTS = _header_signatures()
 EXPORTS = tuple(_SIGNATURES)
-# headers that extend vdiff_hip.h, each with a fixture of its own: their entry points are bound like EXPORTS
-EXT_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dgrad_planes.h"),)
-_EXT_SIGNATURES = {name: sig for path in EXT_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
-EXT_EXPORTS = tuple(_EXT_SIGNATURES)
-# (EXT_HEADER_PATHS / EXT_EXPORTS are held to the planes header's fixture as they stand -- tests/test_dgrad_planes_cpu.py -- so a further
-# extension header is listed beside them: vdiff_hip_dps.h, pinned by tests/golden/c_abi_dps.json)
-DPS_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_dps.h"),)
-_DPS_SIGNATURES = {name: sig for path in DPS_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
-DPS_EXPORTS = tuple(_DPS_SIGNATURES)
-# (... and each of those tables is held to its own fixture as it stands: vdiff_hip_ddnm.h, pinned by tests/golden/c_abi_ddnm.json)
-DDNM_HEADER_PATHS = (os.path.join(os.path.dirname(HEADER_PATH), "vdiff_hip_ddnm.h"),)
-_DDNM_SIGNATURES = {name: sig for path in DDNM_HEADER_PATHS for name, sig in _header_signatures(path)[0].items()}
-DDNM_EXPORTS = tuple(_DDNM_SIGNATURES)
 
 _lib = None
 
@@ -113,7 +101,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in {**_SIGNATURES, **_EXT_SIGNATURES, **_DPS_SIGNATURES, **_DDNM_SIGNATURES}.items():
+        for name, (res, args) in _SIGNATURES.items():
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():

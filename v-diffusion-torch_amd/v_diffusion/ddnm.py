@@ -27,10 +27,10 @@ import numbers
 import torch
 
 from . import _hip
-from .chain import Chain, refuse_variants
-from .diffusion import _device_ctx, _need_cuda
-from .dps import _operator
+from .chain import refuse_variants
+from .diffusion import _need_cuda
 from .inpaint import jump_coefs, resampling_schedule
+from .restore import ddnm_pinv, open_chain, parse_operator, per_index      # noqa: F401  (ddnm_pinv: v_diffusion.ddnm.ddnm_pinv)
 
 
 def ddnm_rule(c2, noise_scale, sigma_y, last, lam=None):
@@ -53,54 +53,15 @@ def ddnm_rule(c2, noise_scale, sigma_y, last, lam=None):
     return lam, math.sqrt(max(0.0, ns * ns - carried * carried))
 
 
-def ddnm_pinv(y, operator, shape):
-    """A^+ y for a measurement batch ``y`` of images of ``shape`` = (B, C, H, W), with plain torch operations on ``y``'s device: y / M
-    where M > 0 and 0 elsewhere for ``("mask", mask)``, every measurement element spread over its f x f block for ``("down", f)`` and
-    over the C channels for ``("gray",)`` (both means: A^+ copies).  The companion of ``dps_measure``: A A^+ y = y on the range of A.
-    Not hot path."""
-    kind, par, mask, mshape = _operator(operator, tuple(shape))
-    if not torch.is_tensor(y) or tuple(y.shape) != mshape:
-        raise ValueError(f"y must have shape {mshape}, the image of shape {tuple(shape)} under {kind!r}, got "
-                         f"{tuple(getattr(y, 'shape', ()))}")
-    if kind == "mask":
-        m = mask.to(device=y.device, dtype=y.dtype).expand(mshape)
-        return torch.where(m > 0, y / torch.where(m > 0, m, torch.ones_like(m)), torch.zeros_like(y))
-    if kind == "down":
-        return y.repeat_interleave(par, dim=2).repeat_interleave(par, dim=3)
-    return y.expand(tuple(int(v) for v in shape)).clone()
-
-
-def _lams(lam, T):
-    """None (``ddnm_rule``'s) or the lam of every destination grid index 0 ... T-1 as python floats"""
-    if lam is None:
-        return None
-    if isinstance(lam, numbers.Real) and not isinstance(lam, bool):
-        ls = [float(lam)] * T
-    else:
-        if torch.is_tensor(lam):
-            lam = lam.detach().reshape(-1).tolist() if lam.dim() <= 1 else None
-        if not isinstance(lam, (list, tuple)) or len(lam) != T or any(isinstance(v, bool) or not isinstance(v, numbers.Real) for v in lam):
-            raise ValueError(f"lam must be None, a float or {T} floats (one per destination grid index), got "
-                             f"{len(lam) if isinstance(lam, (list, tuple)) else lam!r}")
-        ls = [float(v) for v in lam]
-    bad = [v for v in ls if not 0.0 <= v <= 1.0]                       # (a NaN fails both)
-    if bad:
-        raise ValueError(f"lam must lie in [0, 1], got {bad[0]!r}")
-    return ls
-
-
 def _check_inputs(gd, measurement, operator, shape, sigma_y, lam, use_ddim, jump_length, resamplings):
     """everything that can be refused before a launch; returns (kind, par, mask, sigma_y, the lams or None, the schedule)"""
     refuse_variants(gd, "p_sample_ddnm")
-    kind, par, mask, mshape = _operator(operator, tuple(shape))
-    if not torch.is_tensor(measurement) or tuple(measurement.shape) != mshape:
-        raise ValueError(f"measurement must have shape {mshape}, the image of shape {tuple(shape)} under {kind!r}, got "
-                         f"{tuple(getattr(measurement, 'shape', ()))}")
+    kind, par, mask, _ = parse_operator(operator, tuple(shape), measurement, "measurement")
     if isinstance(sigma_y, bool) or not isinstance(sigma_y, numbers.Real) or not (math.isfinite(sigma_y) and sigma_y >= 0.0):
         raise ValueError(f"sigma_y must be finite and >= 0, got {sigma_y!r}")
     if sigma_y > 0.0 and use_ddim:
         raise ValueError("sigma_y > 0 with use_ddim=True: a DDIM step adds no noise that could absorb the measurement's")
-    ls = _lams(lam, gd.sample_timesteps)
+    ls = per_index("lam", lam, gd.sample_timesteps, lambda v: 0.0 <= v <= 1.0, "lie in [0, 1]", allow_none=True)    # (a NaN: outside)
     sched = resampling_schedule(gd.sample_timesteps, jump_length, resamplings)      # validates the two counts
     _need_cuda(measurement, "p_sample_ddnm")
     return kind, par, mask, float(sigma_y), ls, sched
@@ -111,17 +72,10 @@ def p_sample_ddnm(gd, denoise_fn, measurement, operator, shape, label=None, devi
     """the chain of ``GaussianDiffusion.p_sample_ddnm`` (see there); returns the final image batch on the device, and with
     ``return_residuals`` the (reverse steps, B) norms ||y - A g|| too"""
     kind, par, mask, sigma_y, ls, sched = _check_inputs(gd, measurement, operator, shape, sigma_y, lam, use_ddim, jump_length, resamplings)
-    device = torch.device(gd._default_device(denoise_fn) if device is None else device)
-    ctx = _device_ctx(device)
     T, fn, clip, op = gd.sample_timesteps, gd.logsnr_fn, bool(clip_denoised), _hip.DPS_OPS[kind]
-    shape = tuple(int(v) for v in shape)
-    B, C, Hh, Ww = shape
+    ctx, draw, meas, m, ch = open_chain(gd, denoise_fn, measurement, mask, par, shape, label, device, seed)
+    (B, C, Hh, Ww), device = ch.x.shape, ch.device
     with ctx, torch.no_grad():
-        generator = None if seed is None else torch.Generator(device).manual_seed(seed)
-        draw = lambda: torch.randn(shape, device=device, generator=generator)
-        meas = measurement.to(device=device, dtype=torch.float32).contiguous()
-        m = None if mask is None else mask.to(device=device, dtype=torch.float32).expand(B, par, Hh, Ww).contiguous()
-        ch = Chain(gd, denoise_fn, draw(), label, device)
         res = torch.zeros((sum(b < a for a, b in zip(sched, sched[1:])), B), dtype=torch.float32, device=device) if return_residuals else None
         n = 0
         with ch.fixed_weights():

@@ -20,93 +20,20 @@ Random draws, from one ``torch.Generator(device).manual_seed(seed)``, each of th
 one per step -- ``p_sample``'s order.
 """
 import math
-import numbers
 
 import torch
-import torch.nn.functional as F
 
 from . import _hip
-from .chain import Chain, F64, refuse_variants
-from .diffusion import _device_ctx, _need_cuda
-
-OPERATORS = ("mask", "down", "gray")
-DOWN_FACTORS = (2, 4, 8)
-
-
-def _operator(operator, shape):
-    """``(kind, par, mask or None, the shape of A's image)`` of an operator on images of ``shape`` = (B, C, H, W); everything about it
-    that can be refused without a device.  par: the mask's channel count / the down-sampling factor / 0."""
-    if not isinstance(operator, (tuple, list)) or not operator or operator[0] not in OPERATORS:
-        raise ValueError(f"operator must be ('mask', mask), ('down', f) or ('gray',), got {operator!r}")
-    if len(shape) != 4 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in shape):
-        raise ValueError(f"shape must be (B, C, H, W) of positive integers, got {tuple(shape)!r}")
-    B, C, H, W = (int(v) for v in shape)
-    kind = operator[0]
-    if len(operator) != (1 if kind == "gray" else 2):
-        raise ValueError(f"operator {kind!r} takes {'no argument' if kind == 'gray' else 'one argument'}, got {len(operator) - 1}")
-    if kind == "gray":
-        return kind, 0, None, (B, 1, H, W)
-    if kind == "down":
-        f = operator[1]
-        if isinstance(f, bool) or not isinstance(f, numbers.Integral) or f not in DOWN_FACTORS:
-            raise ValueError(f"the down-sampling factor must be one of {DOWN_FACTORS}, got {f!r}")
-        if H % f or W % f:
-            raise ValueError(f"the down-sampling factor {f} must divide H = {H} and W = {W}")
-        return kind, int(f), None, (B, C, H // f, W // f)
-    mask = operator[1]                                                 # p_sample_inpaint's rules
-    if not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) \
-            or tuple(mask.shape[2:]) != (H, W):
-        raise ValueError(f"mask must have shape (B or 1, 1 or C, H, W) for images of shape {(B, C, H, W)}, got "
-                         f"{tuple(getattr(mask, 'shape', ()))}")
-    if mask.dtype != torch.bool:
-        if not mask.dtype.is_floating_point:
-            raise ValueError(f"mask must be float or bool, got {mask.dtype}")
-        lo, hi = float(mask.min()), float(mask.max())
-        if not (lo >= 0.0 and hi <= 1.0):                              # (a NaN fails both)
-            raise ValueError(f"mask values must lie in [0, 1], got [{lo}, {hi}]")
-    return kind, int(mask.shape[1]), mask, (B, C, H, W)
-
-
-def dps_measure(x, operator):
-    """A x of an image batch ``x`` (B, C, H, W) with plain torch operations on ``x``'s device: M (.) x for ``("mask", mask)``, the mean
-    over f x f blocks for ``("down", f)``, the channel mean (B, 1, H, W) for ``("gray",)``.  Not hot path: it makes the measurement a
-    caller hands to ``p_sample_dps`` (adding the measurement noise is the caller's)."""
-    if not torch.is_tensor(x) or x.dim() != 4:
-        raise ValueError(f"x must be a (B, C, H, W) tensor, got shape {tuple(getattr(x, 'shape', ()))}")
-    kind, par, mask, _ = _operator(operator, tuple(x.shape))
-    if kind == "mask":
-        return mask.to(device=x.device, dtype=x.dtype) * x
-    if kind == "down":
-        return F.avg_pool2d(x, par)
-    return x.mean(dim=1, keepdim=True)
-
-
-def _zetas(zeta, T):
-    """the step size of every destination grid index 0 ... T-1 as python floats"""
-    if isinstance(zeta, numbers.Real) and not isinstance(zeta, bool):
-        zs = [float(zeta)] * T
-    else:
-        if torch.is_tensor(zeta):
-            zeta = zeta.detach().reshape(-1).tolist() if zeta.dim() <= 1 else None
-        if not isinstance(zeta, (list, tuple)) or len(zeta) != T or \
-                any(isinstance(z, bool) or not isinstance(z, numbers.Real) for z in zeta):
-            raise ValueError(f"zeta must be a float or {T} floats (one per destination grid index), got "
-                             f"{len(zeta) if isinstance(zeta, (list, tuple)) else zeta!r}")
-        zs = [float(z) for z in zeta]
-    bad = [z for z in zs if not (math.isfinite(z) and z >= 0.0)]
-    if bad:
-        raise ValueError(f"zeta must be finite and >= 0, got {bad[0]!r}")
-    return zs
+from .chain import F64, refuse_variants
+from .diffusion import _need_cuda
+from .restore import dps_measure, open_chain, parse_operator, per_index      # noqa: F401  (dps_measure: v_diffusion.dps.dps_measure)
 
 
 def _check_inputs(gd, measurement, operator, shape, zeta):
     """everything that can be refused before a launch; returns (kind, par, mask, the step sizes)"""
     refuse_variants(gd, "p_sample_dps")
-    kind, par, mask, mshape = _operator(operator, tuple(shape))
-    if not torch.is_tensor(measurement) or tuple(measurement.shape) != mshape:
-        raise ValueError(f"measurement must have shape {mshape}, the image of shape {tuple(shape)} under {kind!r}, got "
-                         f"{tuple(getattr(measurement, 'shape', ()))}")
-    zs = _zetas(zeta, gd.sample_timesteps)
+    kind, par, mask, _ = parse_operator(operator, tuple(shape), measurement, "measurement")
+    zs = per_index("zeta", zeta, gd.sample_timesteps, lambda z: math.isfinite(z) and z >= 0.0, "be finite and >= 0")
     _need_cuda(measurement, "p_sample_dps")
     return kind, par, mask, zs
 
@@ -135,17 +62,11 @@ def p_sample_dps(gd, denoise_fn, measurement, operator, shape, label=None, devic
                  clip_denoised=True):
     """the chain of ``GaussianDiffusion.p_sample_dps`` (see there); returns the final image batch on the device"""
     kind, par, mask, zs = _check_inputs(gd, measurement, operator, shape, zeta)
-    device = torch.device(gd._default_device(denoise_fn) if device is None else device)
-    ctx = _device_ctx(device)
     clip, op = bool(clip_denoised), _hip.DPS_OPS[kind]
-    shape = tuple(int(v) for v in shape)
+    ctx, draw, meas, m, ch = open_chain(gd, denoise_fn, measurement, mask, par, shape, label, device, seed)
+    shape, device = tuple(ch.x.shape), ch.device
     B, C, Hh, Ww = shape
     with ctx, torch.no_grad():
-        generator = None if seed is None else torch.Generator(device).manual_seed(seed)
-        draw = lambda: torch.randn(shape, device=device, generator=generator)
-        meas = measurement.to(device=device, dtype=torch.float32).contiguous()
-        m = None if mask is None else mask.to(device=device, dtype=torch.float32).expand(B, par, Hh, Ww).contiguous()
-        ch = Chain(gd, denoise_fn, draw(), label, device)
         co = C * (2 if gd.model_out_type == "both" else 1)
         dout = torch.empty((ch.rows, co, Hh, Ww), dtype=torch.float32, device=device)
         dxt = torch.empty(shape, dtype=torch.float32, device=device)

@@ -1037,7 +1037,7 @@ class UNetEngine:
     def backward(self, tape, dout, G, need_dx=False, progress=None):
         """Fills ``G`` (name -> tensor, every entry overwritten) and returns d/dx (NCHW) when asked.  ``progress(name)`` is called whenever
         the gradient of ``name`` and of everything before it in completion_order() is final (gradient-bucket overlap).  The deferred
-        weight-gradient queue and the side stream never outlive the call, whatever it raises (backward_steps' ``finally``).
+        weight-gradient queue and the side stream never outlive the call, whatever it raises (``_steps``' ``finally``, both passes).
         ``G`` None with ``need_dx``: the INPUT-ONLY pass, for a network whose weights are held fixed (guidance, posterior sampling, any loss
         on the prediction).  It runs what d/dx depends on -- the input-gradient convolutions, the GroupNorm and attention backward, the
         skip-path GEMMs, the resample backward: the launches of the full pass with their arguments, so d/dx is that pass's bit for bit
@@ -1045,16 +1045,9 @@ class UNetEngine:
         parameter-shaped tensor.  There is no gradient to report: a ``progress`` listener is refused."""
         if G is None:
             self._refuse_no_grads(need_dx, progress is not None)
-            steps = self._backward(tape, dout, None, True, False)
-            try:
-                while True:
-                    next(steps)
-            except StopIteration as fin:
-                return fin.value
-            finally:
-                self._wq = None
-                self._side = None
-        steps = self.backward_steps(tape, dout, G, need_dx, join=progress is not None)
+            steps = self._steps(tape, dout, None, True, False)
+        else:
+            steps = self.backward_steps(tape, dout, G, need_dx, join=progress is not None)
         try:
             while True:
                 name = next(steps)

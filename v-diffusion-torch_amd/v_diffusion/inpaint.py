@@ -24,8 +24,9 @@ import torch
 import torch.nn.functional as F
 
 from . import _hip
-from .chain import Chain, chain_length, image_batch
-from .diffusion import F64, _device_ctx, _need_cuda
+from .chain import chain_length, image_batch
+from .diffusion import F64, _need_cuda
+from .restore import mask_channels, open_chain
 
 
 def _positive_int(name, v):
@@ -97,20 +98,10 @@ def _check_inputs(gd, known, mask, jump_length, resamplings, start):
     if gd.model_var_type == "learned":
         raise NotImplementedError("model_var_type='learned'")
     image_batch("known", known)
-    B, C, H, W = known.shape
-    if not torch.is_tensor(mask) or mask.dim() != 4 or mask.shape[0] not in (1, B) or mask.shape[1] not in (1, C) \
-            or tuple(mask.shape[2:]) != (H, W):
-        raise ValueError(f"mask must have shape (B or 1, 1 or C, H, W) for known of shape {tuple(known.shape)}, got "
-                         f"{tuple(getattr(mask, 'shape', ()))}")
-    if mask.dtype != torch.bool:
-        if not mask.dtype.is_floating_point:
-            raise ValueError(f"mask must be float or bool, got {mask.dtype}")
-        lo, hi = float(mask.min()), float(mask.max())
-        if not (lo >= 0.0 and hi <= 1.0):                          # (a NaN fails both)
-            raise ValueError(f"mask values must lie in [0, 1], got [{lo}, {hi}]")
+    mask_c = mask_channels(mask, tuple(known.shape), "known")
     Tc = chain_length(gd, start)
     resampling_schedule(Tc, jump_length, resamplings)              # validates the two counts
-    return Tc, int(mask.shape[1])
+    return Tc, mask_c
 
 
 def p_sample_inpaint(gd, denoise_fn, known, mask, label=None, device=None, seed=None, use_ddim=False, jump_length=1, resamplings=1,
@@ -118,17 +109,11 @@ def p_sample_inpaint(gd, denoise_fn, known, mask, label=None, device=None, seed=
     """the chain of ``GaussianDiffusion.p_sample_inpaint`` (see there); returns the final image batch on the device"""
     Tc, mask_c = _check_inputs(gd, known, mask, jump_length, resamplings, start)
     _need_cuda(known, "p_sample_inpaint")
-    device = torch.device(gd._default_device(denoise_fn) if device is None else device)
-    ctx = _device_ctx(device)
     T, fn, clip = gd.sample_timesteps, gd.logsnr_fn, bool(clip_denoised)
     sched = resampling_schedule(Tc, jump_length, resamplings)
+    # (the chain's first state: x_T, or the eps of the noised start; its x_in is filled below)
+    ctx, draw, known, m, ch = open_chain(gd, denoise_fn, known, mask, mask_c, known.shape, label, device, seed, dup=False)
     with ctx:
-        generator = None if seed is None else torch.Generator(device).manual_seed(seed)
-        known = known.to(device=device, dtype=torch.float32).contiguous()
-        shape = tuple(known.shape)
-        draw = lambda: torch.randn(shape, device=device, generator=generator)
-        m = mask.to(device=device, dtype=torch.float32).expand(shape[0], mask_c, shape[2], shape[3]).contiguous()
-        ch = Chain(gd, denoise_fn, draw(), label, device, dup=False)           # x_T, or the eps of the noised start
         B, C, HW = ch.B, ch.C, ch.HW
         if start is not None:                                                  # SDEdit: x_start = alpha known + sigma eps, everywhere
             _hip.forward_jump(known, ch.x, known_coefs(fn, T, Tc), *ch.dst, B, C * HW)
