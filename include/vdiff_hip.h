@@ -794,10 +794,13 @@ int vd_sumsq(const float* g, int64_t n, float* out1, float* ws, size_t ws_bytes,
 /* [r_lo, r_hi) with r_mode != 0 is an index range treated apart this step (the class-embedding tensors, unet.py:207-215):
  * r_mode 1 = the range received no gradient (class-conditional net called with y = None; the reference leaves .grad None and
  * torch.optim.AdamW skips it: p, m, v untouched, per-parameter step not advanced; the EMA shadow still follows p);
- * r_mode 2 = the range is updated with its own bias corrections r_bc1, r_bc2 (its step count lags). r_mode 0: ignored. */
+ * r_mode 2 = the range is updated with its own bias corrections r_bc1, r_bc2 (its step count lags). r_mode 0: ignored.
+ * beta1, beta2 and ema_decay are doubles: the rates 1 - beta1, 1 - beta2, 1 - ema_decay are formed in double on the host and rounded
+ * to fp32 once, which is what torch.optim.AdamW and utils.py:149 hand to their fp32 operators (1.f - 0.9999f is 1.66e-4 off 1e-4,
+ * 1.f - 0.999f is 1.29e-5 off 1e-3; as vd_ema_track_batched's decay). */
 int vd_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
-                 const float* gnorm_sq, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
-                 float bc1, float bc2, float ema_decay, int64_t r_lo, int64_t r_hi, int32_t r_mode, float r_bc1, float r_bc2,
+                 const float* gnorm_sq, float max_norm, float lr, double beta1, double beta2, float eps, float wd,
+                 float bc1, float bc2, double ema_decay, int64_t r_lo, int64_t r_hi, int32_t r_mode, float r_bc1, float r_bc2,
                  void* stream);
 /* the same update with the decision about [r_lo, r_hi) made ON THE DEVICE: r_flag[0] > 0 (device float: "some rank's micro-batch of
  * this update carried labels" -- one slot behind the flat gradient buffer, summed over ranks by the last gradient bucket's
@@ -806,8 +809,8 @@ int vd_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64
  * per-update host all-reduce the reference's DDP + torch.optim.AdamW pair needs no equivalent of (train_utils.py:159-163:
  * optimizer.step() skips parameters whose .grad is None; under DDP that is the same on every rank by construction). */
 int vd_adamw_ema_flagged(float* p, const float* g, float* m, float* v, float* ema, int64_t n,
-                         const float* gnorm_sq, float max_norm, float lr, float beta1, float beta2, float eps, float wd,
-                         float bc1, float bc2, float ema_decay, int64_t r_lo, int64_t r_hi, const float* r_flag, int32_t* r_steps,
+                         const float* gnorm_sq, float max_norm, float lr, double beta1, double beta2, float eps, float wd,
+                         float bc1, float bc2, double ema_decay, int64_t r_lo, int64_t r_hi, const float* r_flag, int32_t* r_steps,
                          double r_beta1, double r_beta2, void* stream);
 
 /* ------------------------------------------------------------------ k-NN precision / recall (metrics.hip)

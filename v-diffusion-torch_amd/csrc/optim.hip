@@ -59,8 +59,8 @@ __device__ __forceinline__ void st1(float* p, float v) {
 #endif
 }
 __global__ void adamw_ema_kernel(float* p, const float* g, float* m, float* v, float* ema, long long n, const float* gnorm_sq,
-                                 float max_norm, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2,
-                                 float ema_decay, long long r_lo, long long r_hi, int r_mode, float r_bc1, float r_bc2,
+                                 float max_norm, float lr, float b1, float b2, float omb1, float omb2, float eps, float wd, float bc1,
+                                 float bc2, float omd, long long r_lo, long long r_hi, int r_mode, float r_bc1, float r_bc2,
                                  const float* r_flag, const int* r_steps, double r_beta1, double r_beta2) {
     if (r_mode == 3) {
         if (r_flag[0] > 0.f) {
@@ -85,12 +85,12 @@ __global__ void adamw_ema_kernel(float* p, const float* g, float* m, float* v, f
         if (!(in_r && r_mode == 1)) {
             const float gi = ld1(g + i) * clip;
             pi *= 1.f - lr * wd;
-            const float mi = b1 * ld1(m + i) + (1.f - b1) * gi;
-            const float vi = b2 * ld1(v + i) + (1.f - b2) * gi * gi;
+            const float mi = b1 * ld1(m + i) + omb1 * gi;
+            const float vi = b2 * ld1(v + i) + omb2 * gi * gi;
             pi -= (in_r ? r_step : step) * mi / (sqrtf(vi) * (in_r ? r_rs2 : rs2) + eps);
             st1(p + i, pi); st1(m + i, mi); st1(v + i, vi);
         }
-        if (ema) { const float e = ld1(ema + i); st1(ema + i, e + (1.f - ema_decay) * (pi - e)); }
+        if (ema) { const float e = ld1(ema + i); st1(ema + i, e + omd * (pi - e)); }
     }
 }
 
@@ -114,23 +114,24 @@ extern "C" int vd_sumsq(const float* g, int64_t n, float* out1, float* ws, size_
 }
 
 extern "C" int vd_adamw_ema(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* gnorm_sq,
-                            float max_norm, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                            float ema_decay, int64_t r_lo, int64_t r_hi, int32_t r_mode, float r_bc1, float r_bc2, void* stream) {
+                            float max_norm, float lr, double beta1, double beta2, float eps, float wd, float bc1, float bc2,
+                            double ema_decay, int64_t r_lo, int64_t r_hi, int32_t r_mode, float r_bc1, float r_bc2, void* stream) {
     VD_REQUIRE(r_mode >= 0 && r_mode <= 2, "vd_adamw_ema: r_mode must be 0, 1 or 2");
     VD_REQUIRE(r_mode == 0 || (0 <= r_lo && r_lo <= r_hi && r_hi <= n), "vd_adamw_ema: bad range [%lld, %lld)", (long long)r_lo, (long long)r_hi);
     VD_REQUIRE(r_mode != 2 || (r_bc1 > 0.f && r_bc2 > 0.f), "vd_adamw_ema: r_mode 2 needs positive bias corrections");
     long long grid = (n + 255) / 256;
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(adamw_ema_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, (long long)n,
-                       gnorm_sq, max_norm, lr, beta1, beta2, eps, wd, bc1, bc2, ema_decay, (long long)r_lo, (long long)r_hi, (int)r_mode,
+                       gnorm_sq, max_norm, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bc1, bc2,
+                       (float)(1.0 - ema_decay), (long long)r_lo, (long long)r_hi, (int)r_mode,
                        r_mode == 2 ? r_bc1 : 1.f, r_mode == 2 ? r_bc2 : 1.f, (const float*)nullptr, (const int*)nullptr, 0.0, 0.0);
     VD_LAUNCH_CHECK("adamw_ema_kernel");
     return 0;
 }
 
 extern "C" int vd_adamw_ema_flagged(float* p, const float* g, float* m, float* v, float* ema, int64_t n, const float* gnorm_sq,
-                                    float max_norm, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2,
-                                    float ema_decay, int64_t r_lo, int64_t r_hi, const float* r_flag, int32_t* r_steps,
+                                    float max_norm, float lr, double beta1, double beta2, float eps, float wd, float bc1, float bc2,
+                                    double ema_decay, int64_t r_lo, int64_t r_hi, const float* r_flag, int32_t* r_steps,
                                     double r_beta1, double r_beta2, void* stream) {
     VD_REQUIRE(r_flag && r_steps, "vd_adamw_ema_flagged: needs the device flag and the device step counter");
     VD_REQUIRE(0 <= r_lo && r_lo <= r_hi && r_hi <= n, "vd_adamw_ema_flagged: bad range [%lld, %lld)", (long long)r_lo, (long long)r_hi);
@@ -138,7 +139,8 @@ extern "C" int vd_adamw_ema_flagged(float* p, const float* g, float* m, float* v
     long long grid = (n + 255) / 256;
     if (grid > 8192) grid = 8192;
     hipLaunchKernelGGL(adamw_ema_kernel, dim3((int)grid), dim3(256), 0, (hipStream_t)stream, p, g, m, v, ema, (long long)n,
-                       gnorm_sq, max_norm, lr, beta1, beta2, eps, wd, bc1, bc2, ema_decay, (long long)r_lo, (long long)r_hi, 3,
+                       gnorm_sq, max_norm, lr, (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2), eps, wd, bc1, bc2,
+                       (float)(1.0 - ema_decay), (long long)r_lo, (long long)r_hi, 3,
                        1.f, 1.f, r_flag, (const int*)r_steps, r_beta1, r_beta2);
     VD_LAUNCH_CHECK("adamw_ema_kernel");
     hipLaunchKernelGGL(cls_step_advance_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, r_flag, (int*)r_steps);
