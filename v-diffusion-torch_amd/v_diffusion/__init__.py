@@ -11,7 +11,9 @@ timestep resampling (``LossSecondMomentResampler``: v_diffusion/resample.py, lik
 multistep consistency sampling (``ConsistencyDiffusion``, ``GaussianDiffusion.p_sample_consistency``, ``consistency_coefs``,
 ``consistency_sample_coefs``, ``consistency_schedule``: v_diffusion/consistency.py, likewise) and Diffusion Posterior Sampling
 (``GaussianDiffusion.p_sample_dps``, ``dps_measure``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input gradient) and
-DDNM null-space restoration (``GaussianDiffusion.p_sample_ddnm``, ``ddnm_rule``, ``ddnm_pinv``: v_diffusion/ddnm.py, likewise).  The other nine names the reference package re-exports (data loading,
+DDNM null-space restoration (``GaussianDiffusion.p_sample_ddnm``, ``ddnm_rule``, ``ddnm_pinv``: v_diffusion/ddnm.py, likewise) and post-hoc EMA
+(``posthoc_ema``, ``solve_weights``, ``profile_dot``, ``power_ema_rate``, ``sigma_rel_to_gamma``, ``gamma_to_sigma_rel``: v_diffusion/phema.py, likewise;
+``HotPathTrainer(ema_sigma_rels=...)`` and ``optim.PowerEMA`` track its profiles).  The other nine names the reference package re-exports (data loading,
 config helpers, its Trainer / Evaluator: control plane, out of scope) are NOT re-implemented: when the environment
 variable ``VDIFF_REFERENCE_ROOT`` points at a checkout of the reference they are resolved lazily from it (loaded under
 the alias ``v_diffusion_ref`` so its relative imports stay inside the reference), which lets the reference's
@@ -29,6 +31,7 @@ from .dps import dps_measure, p_sample_dps
 from .inpaint import jump_coefs, known_coefs, resampling_schedule
 from .invert import encode_coefs, slerp
 from .models.unet import UNet
+from .phema import gamma_to_sigma_rel, posthoc_ema, power_ema_rate, profile_dot, sigma_rel_to_gamma, solve_weights
 from .resample import LossSecondMomentResampler
 from .solver import dynamic_threshold, solver_coefs, threshold_rank
 from .unipc import p_sample_unipc, unipc_coefs
@@ -36,7 +39,8 @@ from .unipc import p_sample_unipc, unipc_coefs
 _HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusion", "distill_coefs", "solver_coefs", "threshold_rank",
         "dynamic_threshold", "resampling_schedule", "known_coefs", "jump_coefs", "encode_coefs", "slerp", "LossSecondMomentResampler",
         "unipc_coefs", "p_sample_unipc", "ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule",
-        "dps_measure", "p_sample_dps", "ddnm_rule", "ddnm_pinv"]
+        "dps_measure", "p_sample_dps", "ddnm_rule", "ddnm_pinv", "sigma_rel_to_gamma", "gamma_to_sigma_rel", "power_ema_rate", "profile_dot",
+        "solve_weights", "posthoc_ema"]
 _DELEGATED = ["get_dataloader", "DATA_INFO", "dict2str", "seed_all", "update_config", "fill_with_defaults", "Trainer",
               "Evaluator", "DummyScheduler"]
 _ref_pkg = None

@@ -1,4 +1,4 @@
-"""ctypes binding of libvdiff_hip.so (C ABI: include/vdiff_hip.h).
+"""ctypes binding of libvdiff_hip.so (C ABI: include/vdiff_hip.h, and include/vdiff_phema.h for the post-hoc EMA entries).
 
 PyTorch is used only for device memory and streams: every function here takes torch CUDA(HIP) tensors,
 passes raw pointers + the current stream to the HIP library and returns nothing the library allocated.
@@ -13,6 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vdiff_hip.h")
+PHEMA_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "vdiff_phema.h")      # the post-hoc EMA entries: a table of their own
 LIB_PATH = os.environ.get("VDIFF_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvdiff_hip.so")   # (override: A/B builds)
 
 ROW, COL, IM2COL = 0, 1, 2
@@ -75,10 +76,11 @@ def _ctypes_of(name, ret, params):
     return _RETURNS[ret], [arg(q) for q in params]
 
 
-def _header_signatures():
-    if not os.path.exists(HEADER_PATH):
-        raise RuntimeError(f"{HEADER_PATH} not found: the ctypes binding is read from the C header of the source tree")
-    with open(HEADER_PATH) as f:
+def _header_signatures(path=None):
+    path = path or HEADER_PATH
+    if not os.path.exists(path):
+        raise RuntimeError(f"{path} not found: the ctypes binding is read from the C header of the source tree")
+    with open(path) as f:
         tables = _parse_header(f.read())
     return [{name: _ctypes_of(name, *decl) for name, decl in t.items()} for t in tables]
 
@@ -88,6 +90,18 @@ def _header_signatures():
 # library
 _SIGNATURES, PROBE_EXPORTS = _header_signatures()
 EXPORTS = tuple(_SIGNATURES)
+# the same for include/vdiff_phema.h (vd_adamw_emas, vd_ema_combine): bound by the same rule, required of the library like the rest
+def _phema_signatures(path=None):
+    """the product table of include/vdiff_phema.h; a name vdiff_hip.h declares too is named, not bound twice (_parse_header sees one header)"""
+    path = path or PHEMA_HEADER_PATH
+    table, probe = _header_signatures(path)
+    twice = sorted((set(table) | set(probe)) & (set(_SIGNATURES) | set(PROBE_EXPORTS)))
+    if twice or probe:
+        raise RuntimeError(f"{path}: {twice or sorted(probe)} also declared in {HEADER_PATH}" if twice else f"{path}: probe entries belong in {HEADER_PATH}")
+    return table
+
+
+PHEMA_SIGNATURES = _phema_signatures()
 
 _lib = None
 
@@ -101,7 +115,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in (*_SIGNATURES.items(), *PHEMA_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():
@@ -1064,6 +1078,34 @@ def adamw_ema_flagged(p, g, m, v, ema, gnorm_sq, max_norm, lr, b1, b2, eps, wd, 
     _check(lib().vd_adamw_ema_flagged(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(gnorm_sq), max_norm, lr, b1, b2, eps,
                                       wd, bc1, bc2, ema_decay, int(r_lo), int(r_hi), ptr(r_flag), ptr(r_steps), float(b1), float(b2),
                                       stream()), "vd_adamw_ema_flagged")
+
+
+def adamw_emas(p, g, m, v, ema, gnorm_sq, max_norm, lr, b1, b2, eps, wd, bc1, bc2, ema_decay, pema, pema_rate, r_lo=0, r_hi=0, r_mode=0,
+               r_bc1=1.0, r_bc2=1.0, r_flag=None, r_steps=None, n_pema=None):
+    """adamw_ema (r_flag None) or adamw_ema_flagged (r_flag, r_steps given) with the power-function EMA shadows ``pema`` (1..4 flat
+    tensors; an entry None is passed as NULL and refused) updated in the same pass at the rates ``pema_rate`` (the doubles 1 - beta_t of
+    phema.power_ema_rate): vd_adamw_emas.  ``n_pema`` defaults to len(pema)"""
+    if r_flag is not None:
+        assert r_flag.dtype == torch.float32 and r_steps is not None and r_steps.dtype == torch.int32
+    k = len(pema)
+    shadows = (_vp * max(k, 1))(*[ptr(e) for e in pema])
+    rates = (C.c_double * max(k, 1))(*[float(r) for r in pema_rate])
+    _check(lib().vd_adamw_emas(ptr(p), ptr(g), ptr(m), ptr(v), ptr(ema), p.numel(), ptr(gnorm_sq), max_norm, lr, b1, b2, eps, wd, bc1, bc2,
+                               ema_decay, int(r_lo), int(r_hi), int(r_mode), r_bc1, r_bc2, ptr(r_flag), ptr(r_steps), float(b1), float(b2),
+                               shadows, rates, k if n_pema is None else int(n_pema), stream()), "vd_adamw_emas")
+
+
+def ema_combine(out, acc, src, w):
+    """out (fp32, or None) = (float) s and acc (fp64, or None) = s with s = acc + sum_j w[j] src[j] in fp64, one fma per source in
+    order (vd_ema_combine).  ``src``: up to 32 flat fp32 tensors of one length (None allowed where w[j] == 0: such a source is not read)"""
+    k = len(src)
+    n = (out if out is not None else acc if acc is not None else src[0]).numel()
+    assert len(w) == k and all(s is None or (s.dtype == torch.float32 and s.numel() == n and s.is_contiguous()) for s in src)
+    assert out is None or (out.dtype == torch.float32 and out.is_contiguous() and out.numel() == n)
+    assert acc is None or (acc.dtype == torch.float64 and acc.is_contiguous() and acc.numel() == n)
+    srcs = (_vp * max(k, 1))(*[ptr(s) for s in src])
+    ws = (C.c_double * max(k, 1))(*[float(x) for x in w])
+    _check(lib().vd_ema_combine(ptr(out), ptr(acc), srcs, ws, k, n, stream()), "vd_ema_combine")
 
 
 # ----------------------------------------------------------------------------------------------- k-NN precision / recall (metrics.hip)

@@ -12,6 +12,7 @@ VIEWS of those slots (models/unet.py::_grad_targets), which ``AccumulateGrad`` k
 flat buffer when ``step()`` runs: one vd_adamw_ema launch updates parameters and moments (``EMA.update()`` then is one ``lerp_`` over it).  Same
 arithmetic as torch.optim.AdamW (decoupled weight decay, bias corrections, eps outside the square root's bias correction as torch does);
 parameters that received no gradient (a class-conditional network called with y = None) are skipped with their own step count, as torch does.
+``PowerEMA`` tracks the power-function profiles of post-hoc EMA (v_diffusion/phema.py) over the same flat store, with ``EMA``'s interface.
 There is no CPU path: CPU parameters raise."""
 import weakref
 
@@ -193,6 +194,133 @@ class EMA:
                     self.shadow[k].copy_(v)
         self.decay = state_dict.get("decay", self.decay)
         self.num_updates = state_dict.get("num_updates", self.num_updates)
+
+
+class PowerEMA:
+    """Power-function EMA profiles (post-hoc EMA, v_diffusion/phema.py) for the reference's own loop, with the interface of ``EMA``:
+    ``update / apply(sigma_rel) / restore``, context manager (the first profile), ``state_dict`` / ``load_state_dict``, and ``snapshot()``,
+    whose dicts ``phema.posthoc_ema`` rebuilds any profile from.  There is NO new kernel here: over a ``FusedAdamW`` store ``update()`` is
+    one ``lerp_`` launch per profile over its flat shadow, at the rate ``phema.power_ema_rate`` forms in double (as ``EMA.update`` is one
+    ``lerp_``); parameters that are not flat take one multi-tensor ``lerp_`` per profile.  The first update's rate is exactly 1: the
+    shadow becomes the parameters.  (The fused form, every profile in the optimizer's own pass, is ``HotPathTrainer(ema_sigma_rels=...)``.)"""
+
+    def __init__(self, model, sigma_rels=(0.05, 0.10)):
+        from . import phema
+        self.sigma_rels = tuple(float(s) for s in sigma_rels)
+        if not self.sigma_rels or len(set(self.sigma_rels)) != len(self.sigma_rels):
+            raise ValueError(f"PowerEMA: at least one width, all distinct, got {sigma_rels!r}")
+        self.gammas = tuple(phema.sigma_rel_to_gamma(s) for s in self.sigma_rels)
+        self._named = [(k, v) for k, v in model.named_parameters() if v.requires_grad]
+        self._refs = {k: weakref.ref(v) for k, v in self._named}
+        self.num_updates = 0
+        self.backup = None
+        self._store = None
+        self.shadows = None
+        self._build()
+
+    def _build(self):
+        """(re)build the shadows in the layout the parameters have NOW, as ``EMA._build`` does"""
+        ps = [v for _, v in self._named]
+        own = [owner(p) for p in ps]
+        st = own[0][0] if own and own[0] is not None else None
+        old = self.shadows
+        if st is not None and len(st.names) == len(ps) and all(o is not None and o[0] is st and o[1] == i for o, i in zip(own, st.names)):
+            self._store = weakref.ref(st)
+            self._flat = [st.p.clone() for _ in self.sigma_rels]
+            self.shadows = [{k: st.view(f, i) for i, (k, _) in zip(st.names, self._named)} for f in self._flat]
+        else:
+            self._store, self._flat = None, None
+            self.shadows = [{k: v.detach().clone() for k, v in self._named} for _ in self.sigma_rels]
+        if old is not None:
+            with torch.no_grad():
+                for new, was in zip(self.shadows, old):
+                    for k in new:
+                        new[k].copy_(was[k])
+
+    def _index(self, sigma_rel):
+        if sigma_rel is None:
+            return 0
+        if float(sigma_rel) not in self.sigma_rels:
+            raise KeyError(f"sigma_rel {sigma_rel!r} is not tracked (tracked: {self.sigma_rels})")
+        return self.sigma_rels.index(float(sigma_rel))
+
+    @torch.no_grad()
+    def update(self):
+        from . import phema
+        if self._store is None and all(owner(p) is not None for _, p in self._named):
+            self._build()
+        self.num_updates += 1
+        st = self._store() if self._store is not None else None
+        for j, g in enumerate(self.gammas):
+            rate = phema.power_ema_rate(self.num_updates, g)
+            if st is not None:
+                self._flat[j].lerp_(st.p, rate)
+            else:
+                torch._foreach_lerp_([self.shadows[j][k] for k, _ in self._named], [r().data for r in self._refs.values()], rate)
+
+    @torch.no_grad()
+    def apply(self, sigma_rel=None):
+        j = self._index(sigma_rel)
+        st = self._store() if self._store is not None else None
+        if st is not None:
+            self.backup = st.p.clone()
+            st.p.copy_(self._flat[j])
+        else:
+            self.backup = {k: r().detach().clone() for k, r in self._refs.items()}
+            for k, r in self._refs.items():
+                r().data.copy_(self.shadows[j][k])
+
+    @torch.no_grad()
+    def restore(self):
+        if self.backup is None:
+            raise RuntimeError("PowerEMA.restore() without a preceding apply()")
+        st = self._store() if self._store is not None else None
+        if st is not None and torch.is_tensor(self.backup):
+            st.p.copy_(self.backup)
+        else:
+            for k, r in self._refs.items():
+                r().data.copy_(self.backup[k])
+        self.backup = None
+
+    def __enter__(self):
+        self.apply()
+
+    def __exit__(self, *exc):
+        self.restore()
+
+    def snapshot(self):
+        """the profiles as a post-hoc EMA snapshot dict (phema.py): the flat shadows as they are over a flat store, else the shadows packed
+        in ``named_parameters()`` order at 4-float granules"""
+        from . import phema
+        st = self._store() if self._store is not None else None
+        if st is not None:
+            layout = [(k, st.offsets[i], tuple(p.shape)) for i, (k, p) in zip(st.names, self._named)]
+            return phema.make_snapshot(self.num_updates, self.sigma_rels, layout, st.numel, self._flat)
+        layout, n = [], 0
+        for k, p in self._named:
+            layout.append((k, n, tuple(p.shape)))
+            n += (p.numel() + 3) // 4 * 4
+        flats = []
+        for sh in self.shadows:
+            f = torch.zeros(n, dtype=torch.float32, device=self._named[0][1].device)
+            for k, o, shape in layout:
+                f[o:o + sh[k].numel()].copy_(sh[k].reshape(-1))
+            flats.append(f)
+        return phema.make_snapshot(self.num_updates, self.sigma_rels, layout, n, flats)
+
+    def state_dict(self):
+        return {"sigma_rels": list(self.sigma_rels), "shadows": self.shadows, "num_updates": self.num_updates}
+
+    def load_state_dict(self, state_dict):
+        if tuple(float(s) for s in state_dict["sigma_rels"]) != self.sigma_rels:
+            raise RuntimeError(f"PowerEMA: state tracks sigma_rels {tuple(state_dict['sigma_rels'])}, this object {self.sigma_rels}")
+        with torch.no_grad():
+            for mine, theirs in zip(self.shadows, state_dict["shadows"]):
+                if set(mine) != set(theirs):
+                    raise RuntimeError(f"PowerEMA: key mismatch: {sorted(set(mine) ^ set(theirs))[:4]} ...")
+                for k in mine:
+                    mine[k].copy_(theirs[k])
+        self.num_updates = int(state_dict["num_updates"])
 
 
 def use_fused_ema():

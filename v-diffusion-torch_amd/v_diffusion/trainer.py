@@ -22,11 +22,12 @@ MI355X-first choices
 import contextlib
 import math
 import os
+import warnings
 
 import torch
 import torch.distributed as dist
 
-from . import _hip
+from . import _hip, phema
 from .flat import FlatParams
 from .resample import LossSecondMomentResampler
 
@@ -45,9 +46,10 @@ def completion_order(model):
 
 class FlatState(FlatParams):
     """The trainer's flat buffers: parameters / gradients / Adam moments laid out in completion order, FLAG_SLOTS floats behind the
-    gradients, the class-embedding range with its device-side step count, and the EMA buffer."""
+    gradients, the class-embedding range with its device-side step count, the EMA buffer and, with ``ema_sigma_rels``, one more flat
+    buffer per power-function EMA profile (``pema``, v_diffusion/phema.py; ``pema_updates`` counts their updates)."""
 
-    def __init__(self, model, use_ema=True):
+    def __init__(self, model, use_ema=True, ema_sigma_rels=None):
         self.model = model
         params = dict(model.named_parameters())
         super().__init__([(k, params[k]) for k in completion_order(model)], extra_grad=FLAG_SLOTS, state_order=list(params))
@@ -59,6 +61,12 @@ class FlatState(FlatParams):
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=self.p.device)
         self.step_count = 0
         self.ema_updates = 0
+        self.pema_sigma_rels = tuple(float(s) for s in ema_sigma_rels) if ema_sigma_rels is not None else ()
+        if ema_sigma_rels is not None and not (1 <= len(self.pema_sigma_rels) <= 4 and len(set(self.pema_sigma_rels)) == len(self.pema_sigma_rels)):
+            raise ValueError(f"ema_sigma_rels: 1 to 4 distinct widths, got {ema_sigma_rels!r}")
+        self.pema_gammas = tuple(phema.sigma_rel_to_gamma(s) for s in self.pema_sigma_rels)
+        self.pema = [self.p.clone() for _ in self.pema_sigma_rels]      # (None: nothing allocated)
+        self.pema_updates = 0
         # the class-embedding tensors (unet.py:207-215) are the one parameter group that may see no gradient in a step (a class-
         # conditional network called with y = None: the reference leaves .grad None and torch.optim.AdamW skips those parameters,
         # so their per-parameter step count lags): a contiguous range at the end of the flat buffers with its own step count
@@ -79,6 +87,12 @@ class FlatState(FlatParams):
     def ema_state_dict(self):
         """EMA shadow as a reference-format state_dict (utils.py:168-175 keeps ``shadow`` per parameter name)."""
         return {k: self.view(self.ema, k) for k in self.names}
+
+    def pema_index(self, sigma_rel):
+        """position of the tracked profile of width ``sigma_rel``; KeyError when it is not tracked"""
+        if float(sigma_rel) not in self.pema_sigma_rels:
+            raise KeyError(f"sigma_rel {sigma_rel!r} is not tracked (tracked: {self.pema_sigma_rels})")
+        return self.pema_sigma_rels.index(float(sigma_rel))
 
 
 class GradReducer:
@@ -201,8 +215,10 @@ class HotPathTrainer:
 
     def __init__(self, model, diffusion, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, warmup=5000,
                  grad_norm=1.0, ema_decay=0.9999, use_ema=True, num_accum=1, timesteps=0, rank=0, world_size=1, group=None,
-                 schedule_sampler="uniform"):
-        """``schedule_sampler``: "uniform" (the reference's draw), "loss-second-moment" or a ``LossSecondMomentResampler`` -- timesteps
+                 schedule_sampler="uniform", ema_sigma_rels=None):
+        """``ema_sigma_rels``: None, or 1 to 4 distinct widths sigma_rel of power-function EMA profiles (v_diffusion/phema.py) tracked in the
+        update's own launch (vd_adamw_emas), with or without the classic shadow; None launches what a trainer without the argument launches.
+        ``schedule_sampler``: "uniform" (the reference's draw), "loss-second-moment" or a ``LossSecondMomentResampler`` -- timesteps
         drawn in proportion to the root mean square of their recent losses and the loss reweighted by 1/(T p_t) (v_diffusion/resample.py);
         needs a discrete grid (``timesteps`` > 0)"""
         if isinstance(schedule_sampler, str) and schedule_sampler not in ("uniform", "loss-second-moment"):
@@ -219,7 +235,7 @@ class HotPathTrainer:
         self.warmup, self.grad_norm, self.ema_decay, self.num_accum, self.timesteps = warmup, grad_norm, ema_decay, num_accum, timesteps
         self.rank, self.world = rank, world_size
         self.device = next(model.parameters()).device
-        self.flat = FlatState(model, use_ema=use_ema)
+        self.flat = FlatState(model, use_ema=use_ema, ema_sigma_rels=ema_sigma_rels)
         self.reducer = GradReducer(self.flat, world_size, group=group)
         model._grads_ready_hook = None
         self.generator = torch.Generator(self.device).manual_seed(8191 + rank)       # train_utils.py:124
@@ -239,6 +255,8 @@ class HotPathTrainer:
             dist.broadcast(self.flat.p, src=self.leader, group=group)
             if self.flat.ema is not None:
                 self.flat.ema.copy_(self.flat.p)
+            for e in self.flat.pema:
+                e.copy_(self.flat.p)
 
     def draw(self, x):
         B = x.shape[0]
@@ -304,7 +322,15 @@ class HotPathTrainer:
                 decay = min(self.ema_decay, (1 + flat.ema_updates) / (10 + flat.ema_updates))   # utils.py:145-146
             args = (flat.p, flat.g, flat.m, flat.v, flat.ema, flat.gnorm_sq, float(self.grad_norm), lr, self.betas[0], self.betas[1],
                     self.eps, self.wd, 1 - self.betas[0] ** k, 1 - self.betas[1] ** k, decay)
-            if flat.cls_range is not None:
+            if flat.pema:
+                # the power-function profiles ride in the same launch: their rates 1 - beta_t are doubles formed here (t counts their updates)
+                flat.pema_updates += 1
+                rates = [phema.power_ema_rate(flat.pema_updates, g) for g in flat.pema_gammas]
+                if flat.cls_range is not None:
+                    _hip.adamw_emas(*args, flat.pema, rates, flat.cls_range[0], flat.cls_range[1], r_flag=flat.flag, r_steps=flat.cls_steps_dev)
+                else:
+                    _hip.adamw_emas(*args, flat.pema, rates)
+            elif flat.cls_range is not None:
                 # reference semantics of parameters without a gradient (torch.optim.AdamW skips them: no moment decay, no weight
                 # decay, no update, their own step counter), decided and counted on the device: see vd_adamw_ema_flagged
                 _hip.adamw_ema_flagged(*args, flat.cls_range[0], flat.cls_range[1], flat.flag, flat.cls_steps_dev)
@@ -344,16 +370,34 @@ class HotPathTrainer:
 
     # ------------------------------------------------------------------ EMA weights for sampling (utils.py:151-166)
     @contextlib.contextmanager
-    def ema_weights(self):
+    def ema_weights(self, sigma_rel=None):
         """``with trainer.ema_weights(): ...`` runs the body on the EMA shadow.  The reference clones every parameter
         (``EMA.apply``) and copies back (``restore``); here the module's ``.data`` views are re-pointed from the flat
-        parameter buffer to the flat shadow buffer and back -- no device traffic at all."""
-        assert self.flat.ema is not None, "trainer was built with use_ema=False"
-        self.flat.point(self.flat.ema)
+        parameter buffer to the flat shadow buffer and back -- no device traffic at all.  ``sigma_rel``: the tracked power-function
+        profile of that width instead of the classic shadow (KeyError when it is not tracked)."""
+        if sigma_rel is None:
+            assert self.flat.ema is not None, "trainer was built with use_ema=False"
+            buf = self.flat.ema
+        else:
+            buf = self.flat.pema[self.flat.pema_index(sigma_rel)]
+        self.flat.point(buf)
         try:
             yield
         finally:
             self.flat.point(self.flat.p)
+
+    def ema_snapshot(self, path=None):
+        """the tracked power-function profiles as a post-hoc EMA snapshot (the dict of v_diffusion/phema.py: each flat buffer moved to the
+        CPU as it is); the leader also writes it to ``path`` when one is given.  ``phema.posthoc_ema`` rebuilds any profile from a list
+        of these."""
+        flat = self.flat
+        if not flat.pema:
+            raise RuntimeError("ema_snapshot: the trainer tracks no power-function profile (ema_sigma_rels=None)")
+        snap = phema.make_snapshot(flat.pema_updates, flat.pema_sigma_rels,
+                                   [(k, flat.offsets[k], tuple(flat.params[k].shape)) for k in flat.names], flat.numel, flat.pema)
+        if path is not None and self.is_leader:
+            torch.save(snap, path)
+        return snap
 
     # ------------------------------------------------------------------ checkpoints (train_utils.py:309-348)
     def _lr_now(self):
@@ -375,6 +419,9 @@ class HotPathTrainer:
         if flat.ema is not None:
             out["ema"] = {"decay": self.ema_decay, "shadow": {k: flat.view(flat.ema, k).clone() for k in names},
                           "num_updates": flat.ema_updates}
+        if flat.pema:                                              # (absent without the feature: reference-format checkpoints are unchanged)
+            out["ema_power"] = {"sigma_rels": list(flat.pema_sigma_rels), "num_updates": flat.pema_updates,
+                                "shadows": [{k: flat.view(e, k).clone() for k in names} for e in flat.pema]}
         out["scheduler"] = {"base_lrs": [self.lr], "last_epoch": flat.step_count, "_step_count": flat.step_count + 1,
                             "_get_lr_called_within_step": False, "_last_lr": [self._lr_now()], "lr_lambdas": [None]}
         if self.sampler is not None:                               # (absent for the uniform draw: reference-format checkpoints are unchanged)
@@ -431,6 +478,24 @@ class HotPathTrainer:
                     flat.view(flat.ema, k).copy_(shadow[k])
                 flat.ema_updates = int(ema["num_updates"])
                 self.ema_decay = float(ema.get("decay", self.ema_decay))
+            if flat.pema:
+                pw = ckpt.get("ema_power")
+                if pw is None:
+                    warnings.warn("checkpoint without 'ema_power': the power-function EMA profiles start at the loaded weights with t = 0")
+                    for e in flat.pema:
+                        e.copy_(flat.p)
+                    flat.pema_updates = 0
+                else:
+                    if tuple(float(s) for s in pw["sigma_rels"]) != flat.pema_sigma_rels:
+                        raise RuntimeError(f"checkpoint tracks sigma_rels {tuple(pw['sigma_rels'])}, the trainer {flat.pema_sigma_rels}")
+                    for e, shadow in zip(flat.pema, pw["shadows"]):
+                        shadow = strip(shadow)
+                        missing = set(names) ^ set(shadow)
+                        if missing:
+                            raise RuntimeError(f"power EMA key mismatch: {sorted(missing)[:4]} ...")
+                        for k in names:
+                            flat.view(e, k).copy_(shadow[k])
+                    flat.pema_updates = int(pw["num_updates"])
             sch = ckpt.get("scheduler")
             if sch is not None and opt is None:
                 flat.step_count = int(sch.get("last_epoch", flat.step_count))
@@ -441,7 +506,6 @@ class HotPathTrainer:
             if int(self.rank) in ckpt["rng"]:
                 self.generator.set_state(ckpt["rng"][int(self.rank)].cpu())
             else:
-                import warnings
                 warnings.warn(f"checkpoint holds no generator state for rank {self.rank} (has {sorted(ckpt['rng'])}): this rank "
                               f"continues from its fresh seed and will replay the t/noise stream it drew before the checkpoint")
         return ckpt.get("epoch", 0)
