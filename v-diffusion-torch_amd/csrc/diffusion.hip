@@ -7,10 +7,11 @@
 // Without a counterpart in the reference: progressive distillation; consistency distillation / training and the batched
 // target-network update; the DPM-Solver++(2M) reverse step, its dynamically thresholded form and the UniPC step; the RePaint
 // masked reverse step and the forward jump; the noise-map extraction of DDPM inversion; spherical interpolation; the residual and
-// the corrected reverse step of Diffusion Posterior Sampling; the null-space reverse step of DDNM.
+// the corrected reverse step of Diffusion Posterior Sampling, its residual under a blur operator; the null-space reverse step of DDNM.
 // All images here are NCHW, the layout of the reference call surface; the UNet converts at its own boundary.
 // Device side first, then the host helpers (launch, coefficient carrier, the refusals every entry shares), then the C entries.
 #include "common.h"
+#include "../../include/vdiff_blur.h"
 
 namespace {
 
@@ -1387,6 +1388,163 @@ __global__ __launch_bounds__(256) void dps_residual_kernel(const DpsResArgs p) {
     if (threadIdx.x == 0) p.sumsq[b] = (float)acc;
 }
 
+// ---- The blur operator of DPS (include/vdiff_blur.h): A g = the cross-correlation of every channel plane with ONE kh x kw kernel of
+// taps, reflect boundary without repeating the edge (F.pad(mode="reflect") + F.conv2d, depthwise).  Its preimages overlap, so the
+// "thread owns its preimage" split of dps_residual_kernel does not serve: a plane is staged in LDS and both A and A^T are stencils on it.
+//   blur_apply    (A g)[y, x]   = sum_i sum_j tap[i, j] * g[rho_H(y + i - Rh), rho_W(x + j - Rw)],  i, j ascending
+//   blur_adjoint  (A^T r)[y, x] = sum over p in pre_H(y), i, q in pre_W(x), j of tap[i, j] * r[p - i + Rh, q - j + Rw] where that lies in
+//                 the plane; pre_n(y) = y, then -y if 1 <= y <= R, then 2(n - 1) - y if n - 1 - R <= y <= n - 2 (the positions of the
+//                 padded axis that reflect onto y), in that order, i and j ascending inside -- the loops below ARE the order.
+// Both accumulate in fp64 (fma) and round once, dps_apply's rule; the taps stand in LDS as doubles (every lane reads one address: a
+// broadcast).  R <= n - 1 (the entries hold it) keeps rho inside the plane and the three preimages distinct.
+enum { BLUR_THREADS = 1024 };
+
+__device__ __forceinline__ int blur_reflect(int p, int n) {
+    p = p < 0 ? -p : p;
+    return min(p, 2 * (n - 1) - p);
+}
+
+struct BlurGeom { int kh, kw, H, W; };
+
+__device__ __forceinline__ float blur_apply(const float* pl, const double* taps, const BlurGeom& q, int y, int x) {
+    const int rh = q.kh >> 1, rw = q.kw >> 1;
+    double acc = 0.0;
+    for (int i = 0; i < q.kh; ++i) {
+        const float* row = pl + blur_reflect(y + i - rh, q.H) * q.W;
+        const double* tr = taps + i * q.kw;
+        for (int j = 0; j < q.kw; ++j) acc = __builtin_fma(tr[j], (double)row[blur_reflect(x + j - rw, q.W)], acc);
+    }
+    return (float)acc;
+}
+
+// position s = 0, 1, 2 of pre_n(y); false when the set has no such entry
+__device__ __forceinline__ bool blur_pre(int s, int y, int n, int r, int& p) {
+    p = s == 0 ? y : (s == 1 ? -y : 2 * (n - 1) - y);
+    return s == 0 || (s == 1 ? (y >= 1 && y <= r) : (y >= n - 1 - r && y <= n - 2));
+}
+
+__device__ __forceinline__ float blur_adjoint(const float* pl, const double* taps, const BlurGeom& q, int y, int x) {
+    const int rh = q.kh >> 1, rw = q.kw >> 1;
+    double acc = 0.0;
+    for (int s = 0; s < 3; ++s) {
+        int p;
+        if (!blur_pre(s, y, q.H, rh, p)) continue;
+        // the taps whose source row p - i + rh lies in the plane
+        const int i0 = max(0, p + rh - q.H + 1), i1 = min(q.kh - 1, p + rh);
+        for (int i = i0; i <= i1; ++i) {
+            const float* row = pl + (p - i + rh) * q.W;
+            const double* tr = taps + i * q.kw;
+            for (int t = 0; t < 3; ++t) {
+                int c;
+                if (!blur_pre(t, x, q.W, rw, c)) continue;
+                const int j0 = max(0, c + rw - q.W + 1), j1 = min(q.kw - 1, c + rw);
+                for (int j = j0; j <= j1; ++j) acc = __builtin_fma(tr[j], (double)row[c - j + rw], acc);
+            }
+        }
+    }
+    return (float)acc;
+}
+
+enum { BLUR_KMAX = VDX_BLUR_KMAX, BLUR_PLANE_MAX = VDX_BLUR_PLANE_MAX };
+
+__device__ __forceinline__ void blur_load_taps(const float* taps, double* sh, int count) {
+    for (int i = threadIdx.x; i < count; i += blockDim.x) sh[i] = (double)taps[i];
+}
+
+// dps_blur_kernel: dps_residual_kernel's outputs for the blur operator.  ONE WORKGROUP OWNS ONE SAMPLE and walks its C channels; per
+// channel three passes over the plane, element e = y W + x to thread e mod BLUR_THREADS in each:
+//   1. g = the guided clipped prediction (dps_residual_kernel's pred: PredX0, guide) -> the LDS plane gp (and x0hat);          barrier
+//   2. r = meas - blur_apply(gp); the thread's fp64 sum takes r^2; r -> the LDS plane rp;                                        barrier
+//   3. u = -blur_adjoint(rp); dout, dxt from u exactly as dps_residual_kernel forms them (dps_cot, dps_mul; the pass masks are
+//      recomputed from the inputs, as that kernel does for a preimage of more than one element);
+// and a barrier before the next channel reuses the two planes.
+// Every element of every output is written once, by one thread; sumsq is block_sum's fixed order: the same call gives the same bits.
+struct DpsBlurArgs {
+    const float* xt; const float* out; const float* meas; const float* taps; Coefs c; int type, cfg, clip;
+    float* dout; float* dxt; float* sumsq; float* x0hat; int C; BlurGeom q;
+};
+
+__global__ __launch_bounds__(BLUR_THREADS) void dps_blur_kernel(const DpsBlurArgs p) {
+    __shared__ double sh[BLUR_THREADS / 64];
+    __shared__ double taps[BLUR_KMAX * BLUR_KMAX];
+    __shared__ float gp[BLUR_PLANE_MAX], rp[BLUR_PLANE_MAX];
+    const BlurGeom q = p.q;
+    const int HW = q.H * q.W;
+    const long long b = blockIdx.x, N = (long long)p.C * HW;
+    const float* k = p.c.k;
+    const bool both = p.type == OUT_BOTH, cfg = p.cfg != 0;
+    const PredX0 x0 = {k[0], k[1], k[2], both, p.clip != 0};
+    const float a0 = k[0], b0x = k[1], b0e = k[2], w = k[6];
+    const long long row = (both ? 2 : 1) * N;
+    const float* zb = p.xt + b * N;
+    const float* oc = p.out + b * (1 + p.cfg) * row;
+    const float* ou = oc + row;
+    float* dc = p.dout + b * (1 + p.cfg) * row;
+    float* du = dc + row;
+    auto pred = [&](long long i, float& mc, float& mu) -> float {
+        const float z = zb[i];
+        const float pc = x0.raw(z, oc[i], both ? oc[N + i] : 0.f);
+        mc = x0.pass(pc); mu = 0.f;
+        float g = x0.clipped(pc);
+        if (cfg) {
+            const float pu = x0.raw(z, ou[i], both ? ou[N + i] : 0.f);
+            mu = x0.pass(pu);
+            g = guide(w, g, x0.clipped(pu));
+        }
+        return g;
+    };
+    blur_load_taps(p.taps, taps, q.kh * q.kw);
+    double acc = 0.0;
+    for (int c = 0; c < p.C; ++c) {
+        const long long base = (long long)c * HW;
+        for (int e = threadIdx.x; e < HW; e += BLUR_THREADS) {
+            float mc, mu;
+            const float g = pred(base + e, mc, mu);
+            gp[e] = g;
+            if (p.x0hat) p.x0hat[b * N + base + e] = g;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < HW; e += BLUR_THREADS) {
+            const float r = p.meas[b * N + base + e] - blur_apply(gp, taps, q, e / q.W, e % q.W);
+            acc += (double)r * (double)r;
+            rp[e] = r;
+        }
+        __syncthreads();
+        for (int e = threadIdx.x; e < HW; e += BLUR_THREADS) {
+            const long long i = base + e;
+            const float u = -blur_adjoint(rp, taps, q, e / q.W, e % q.W);
+            float mc, mu;
+            pred(i, mc, mu);
+            const DpsCot t = dps_cot(cfg, w, a0, mc, mu);
+            const float cc = dps_mul(t.c, u);
+            dc[i] = dps_mul(cc, b0x);
+            if (both) dc[N + i] = dps_mul(cc, b0e);
+            if (cfg) {
+                const float cu = dps_mul(t.u, u);
+                du[i] = dps_mul(cu, b0x);
+                if (both) du[N + i] = dps_mul(cu, b0e);
+            }
+            p.dxt[b * N + i] = dps_mul(t.z, u);
+        }
+        __syncthreads();
+    }
+    acc = block_sum(acc, sh);
+    if (threadIdx.x == 0) p.sumsq[b] = (float)acc;
+}
+
+// blur_planes_kernel: y = A x (adjoint = 0) or A^T x (1) of one plane per workgroup, by the two device functions above
+__global__ __launch_bounds__(BLUR_THREADS) void blur_planes_kernel(const float* x, const float* tp, int adjoint, float* y, BlurGeom q) {
+    __shared__ double taps[BLUR_KMAX * BLUR_KMAX];
+    __shared__ float pl[BLUR_PLANE_MAX];
+    const int HW = q.H * q.W;
+    const long long base = (long long)blockIdx.x * HW;
+    blur_load_taps(tp, taps, q.kh * q.kw);
+    for (int e = threadIdx.x; e < HW; e += BLUR_THREADS) pl[e] = x[base + e];
+    __syncthreads();
+    for (int e = threadIdx.x; e < HW; e += BLUR_THREADS)
+        y[base + e] = adjoint ? blur_adjoint(pl, taps, q, e / q.W, e % q.W) : blur_apply(pl, taps, q, e / q.W, e % q.W);
+}
+
 // dps_step_kernel: sample_step_kernel's row -- the same helpers: prediction, clip, guided mean_plain, last step, noise -- and then
 //   xn -= zeta / sqrt(sumsq[b]) * (dxt[b] + dxin[2b] + dxin[2b+1])      (dxt[b] + dxin[b] without guidance)
 // with dxin the network's input gradient of dps_residual_kernel's dout: the gradient of ||r|| itself, scaled by zeta.  The term is
@@ -2027,6 +2185,41 @@ extern "C" int vd_dps_step(const float* xt, const float* out, const float* noise
     launch_elems(dps_step_kernel<4>, dps_step_kernel<1>, p.s.N % 4 == 0 && all_aligned16(xt, out, noise, dxin, dxt, xn, xdup), n * p.s.N, stream,
                  p);
     VD_LAUNCH_CHECK("dps_step_kernel");
+    return 0;
+}
+
+// (the blur operator, include/vdiff_blur.h.)  What both entries refuse of the kernel and the plane, after their own pointers and counts
+static int blur_checks(const char* who, int kh, int kw, int H, int W) {
+    VD_REQUIRE(kh >= 1 && kh <= BLUR_KMAX && kw >= 1 && kw <= BLUR_KMAX && (kh & 1) && (kw & 1),
+               "%s: a kernel of %d x %d taps (both sides are odd and at most %d)", who, kh, kw, (int)BLUR_KMAX);
+    VD_REQUIRE(kh / 2 <= H - 1 && kw / 2 <= W - 1, "%s: the radii %d, %d of the kernel do not fit a %d x %d plane (at most H - 1, W - 1)", who,
+               kh / 2, kw / 2, H, W);
+    VD_REQUIRE((long long)H * W <= BLUR_PLANE_MAX, "%s: a plane of %d x %d is over the bound of %d elements", who, H, W, (int)BLUR_PLANE_MAX);
+    return 0;
+}
+
+extern "C" int vdx_dps_residual_blur(const float* xt, const float* out, const float* meas, const float* taps, const float* k, int32_t type,
+                                     int32_t cfg, int32_t clip, int32_t kh, int32_t kw, float* dout, float* dxt, float* sumsq, float* x0hat,
+                                     int32_t n, int32_t C, int32_t H, int32_t W, void* stream) {
+    DpsBlurArgs p = {xt, out, meas, taps, {}, type, cfg ? 1 : 0, clip ? 1 : 0, dout, dxt, sumsq, x0hat, C, {kh, kw, H, W}};
+    VD_REQUIRE(k != nullptr, "vdx_dps_residual_blur: null pointer");
+    VD_TRY(set_coefs("vdx_dps_residual_blur", p.c, k, nullptr, 8));
+    VD_TRY(args_given("vdx_dps_residual_blur", type, xt && out && meas && taps && dout && dxt && sumsq));
+    VD_REQUIRE(n > 0 && C > 0 && H > 0 && W > 0, "vdx_dps_residual_blur: empty batch or image (n=%d, C=%d, H=%d, W=%d)", n, C, H, W);
+    VD_TRY(blur_checks("vdx_dps_residual_blur", kh, kw, H, W));
+    hipLaunchKernelGGL(dps_blur_kernel, dim3(n), dim3(BLUR_THREADS), 0, (hipStream_t)stream, p);
+    VD_LAUNCH_CHECK("dps_blur_kernel");
+    return 0;
+}
+
+extern "C" int vdx_blur_planes(const float* x, const float* taps, int32_t kh, int32_t kw, int32_t adjoint, float* y, int32_t planes,
+                               int32_t H, int32_t W, void* stream) {
+    VD_REQUIRE(x && taps && y, "vdx_blur_planes: null pointer");
+    VD_REQUIRE(adjoint == 0 || adjoint == 1, "vdx_blur_planes: adjoint is 0 (A) or 1 (A^T), got %d", adjoint);
+    VD_REQUIRE(planes > 0 && H > 0 && W > 0, "vdx_blur_planes: empty batch or image (planes=%d, H=%d, W=%d)", planes, H, W);
+    VD_TRY(blur_checks("vdx_blur_planes", kh, kw, H, W));
+    hipLaunchKernelGGL(blur_planes_kernel, dim3(planes), dim3(BLUR_THREADS), 0, (hipStream_t)stream, x, taps, adjoint, y, BlurGeom{kh, kw, H, W});
+    VD_LAUNCH_CHECK("blur_planes_kernel");
     return 0;
 }
 

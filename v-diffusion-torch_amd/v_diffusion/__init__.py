@@ -10,7 +10,8 @@ timestep resampling (``LossSecondMomentResampler``: v_diffusion/resample.py, lik
 (``GaussianDiffusion.p_sample_unipc``, ``unipc_coefs``: v_diffusion/unipc.py, likewise) and consistency distillation / training with
 multistep consistency sampling (``ConsistencyDiffusion``, ``GaussianDiffusion.p_sample_consistency``, ``consistency_coefs``,
 ``consistency_sample_coefs``, ``consistency_schedule``: v_diffusion/consistency.py, likewise) and Diffusion Posterior Sampling
-(``GaussianDiffusion.p_sample_dps``, ``dps_measure``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input gradient) and
+(``GaussianDiffusion.p_sample_dps``, ``dps_measure``, ``blur``, ``gaussian_kernel``: v_diffusion/dps.py, likewise; ``UNet.forward_vjp`` is its input
+gradient) and
 DDNM null-space restoration (``GaussianDiffusion.p_sample_ddnm``, ``ddnm_rule``, ``ddnm_pinv``: v_diffusion/ddnm.py, likewise) and post-hoc EMA
 (``posthoc_ema``, ``solve_weights``, ``profile_dot``, ``power_ema_rate``, ``sigma_rel_to_gamma``, ``gamma_to_sigma_rel``: v_diffusion/phema.py, likewise;
 ``HotPathTrainer(ema_sigma_rels=...)`` and ``optim.PowerEMA`` track its profiles).  The other nine names the reference package re-exports (data loading,
@@ -27,7 +28,7 @@ from .consistency import ConsistencyDiffusion, consistency_coefs, consistency_sa
 from .ddnm import ddnm_pinv, ddnm_rule
 from .diffusion import GaussianDiffusion, get_logsnr_schedule
 from .distill import DistillationDiffusion, distill_coefs
-from .dps import dps_measure, p_sample_dps
+from .dps import blur, dps_measure, gaussian_kernel, p_sample_dps
 from .inpaint import jump_coefs, known_coefs, resampling_schedule
 from .invert import encode_coefs, slerp
 from .models.unet import UNet
@@ -40,7 +41,7 @@ _HOT = ["GaussianDiffusion", "get_logsnr_schedule", "UNet", "DistillationDiffusi
         "dynamic_threshold", "resampling_schedule", "known_coefs", "jump_coefs", "encode_coefs", "slerp", "LossSecondMomentResampler",
         "unipc_coefs", "p_sample_unipc", "ConsistencyDiffusion", "consistency_coefs", "consistency_sample_coefs", "consistency_schedule",
         "dps_measure", "p_sample_dps", "ddnm_rule", "ddnm_pinv", "sigma_rel_to_gamma", "gamma_to_sigma_rel", "power_ema_rate", "profile_dot",
-        "solve_weights", "posthoc_ema"]
+        "solve_weights", "posthoc_ema", "blur", "gaussian_kernel"]
 _DELEGATED = ["get_dataloader", "DATA_INFO", "dict2str", "seed_all", "update_config", "fill_with_defaults", "Trainer",
               "Evaluator", "DummyScheduler"]
 _ref_pkg = None

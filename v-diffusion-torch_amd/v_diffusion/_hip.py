@@ -1,4 +1,5 @@
-"""ctypes binding of libvdiff_hip.so (C ABI: include/vdiff_hip.h, and include/vdiff_phema.h for the post-hoc EMA entries).
+"""ctypes binding of libvdiff_hip.so (C ABI: include/vdiff_hip.h, include/vdiff_phema.h for the post-hoc EMA entries and
+include/vdiff_blur.h, prefix vdx_, for the blur operator of DPS).
 
 PyTorch is used only for device memory and streams: every function here takes torch CUDA(HIP) tensors,
 passes raw pointers + the current stream to the HIP library and returns nothing the library allocated.
@@ -14,6 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "vdiff_hip.h")
 PHEMA_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "vdiff_phema.h")      # the post-hoc EMA entries: a table of their own
+BLUR_HEADER_PATH = os.path.join(os.path.dirname(HEADER_PATH), "vdiff_blur.h")        # the blur operator of DPS: a table and a prefix of its own
 LIB_PATH = os.environ.get("VDIFF_HIP_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libvdiff_hip.so")   # (override: A/B builds)
 
 ROW, COL, IM2COL = 0, 1, 2
@@ -42,17 +44,20 @@ _BY_VALUE = {"int32_t": C.c_int32, "int64_t": C.c_int64, "uint32_t": C.c_uint32,
 _RETURNS = {**_BY_VALUE, "int": C.c_int, "const char*": C.c_char_p}
 _STRUCTS = {"vd_gemm_desc": GemmDesc}          # `const <struct>*` parameters bound to their ctypes mirror; every other pointer is c_void_p
 _DECL = re.compile(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(vd_\w+)\s*\(([^()]*)\)\s*;")
+BLUR_PREFIX = "vdx_"
 
 
-def _parse_header(text):
-    """The declarations of the C header: ({name: (return type, [parameter, ...])} of the product entries, the same of the entries inside
-    #ifdef VD_PROBES ... #endif), each in header order, types and parameters as whitespace-normalised C text ("const float* xt")."""
+def _parse_header(text, prefix="vd_"):
+    """The declarations of the C header whose names start with ``prefix``: ({name: (return type, [parameter, ...])} of the product entries,
+    the same of the entries inside #ifdef VD_PROBES ... #endif), each in header order, types and parameters as whitespace-normalised C text
+    ("const float* xt")."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    decl = _DECL if prefix == "vd_" else re.compile(_DECL.pattern.replace("vd_", re.escape(prefix)))
     tables = ({}, {})
     for i, part in enumerate(re.split(r"#ifdef\s+VD_PROBES\b(.*?)#endif", text, flags=re.S)):       # odd parts: inside the #ifdef
-        decls = _DECL.findall(part)
-        if len(decls) != len(re.findall(r"\bvd_\w+\s*\(", part)):
-            raise RuntimeError(f"{HEADER_PATH}: a vd_* declaration is not of the form `type vd_name(parameters);`")
+        decls = decl.findall(part)
+        if len(decls) != len(re.findall(r"\b" + re.escape(prefix) + r"\w+\s*\(", part)):
+            raise RuntimeError(f"{HEADER_PATH}: a {prefix}* declaration is not of the form `type {prefix}name(parameters);`")
         for ret, name, params in decls:
             if name in tables[0] or name in tables[1]:
                 raise RuntimeError(f"{HEADER_PATH}: {name} is declared twice")
@@ -76,12 +81,12 @@ def _ctypes_of(name, ret, params):
     return _RETURNS[ret], [arg(q) for q in params]
 
 
-def _header_signatures(path=None):
+def _header_signatures(path=None, prefix="vd_"):
     path = path or HEADER_PATH
     if not os.path.exists(path):
         raise RuntimeError(f"{path} not found: the ctypes binding is read from the C header of the source tree")
     with open(path) as f:
-        tables = _parse_header(f.read())
+        tables = _parse_header(f.read(), prefix)
     return [{name: _ctypes_of(name, *decl) for name, decl in t.items()} for t in tables]
 
 
@@ -103,6 +108,26 @@ def _phema_signatures(path=None):
 
 PHEMA_SIGNATURES = _phema_signatures()
 
+
+# the same for include/vdiff_blur.h (vdx_dps_residual_blur, vdx_blur_planes), under its own prefix
+def _blur_signatures(path=None):
+    """the product table of include/vdiff_blur.h: its vdx_* declarations.  It declares no vd_* name (those belong to the two recorded
+    tables above) and no probe entry, and those two headers declare no vdx_* name: no name stands in two headers"""
+    path = path or BLUR_HEADER_PATH
+    table, probe = _header_signatures(path, BLUR_PREFIX)
+    other = [n for t in _header_signatures(path) for n in t]
+    if other or probe:
+        raise RuntimeError(f"{path}: {other} belong in {HEADER_PATH} or {PHEMA_HEADER_PATH}: this header declares {BLUR_PREFIX}* names only"
+                           if other else f"{path}: probe entries belong in {HEADER_PATH}")
+    for elsewhere in (HEADER_PATH, PHEMA_HEADER_PATH):
+        stray = [n for t in _header_signatures(elsewhere, BLUR_PREFIX) for n in t]
+        if stray:
+            raise RuntimeError(f"{elsewhere}: {stray} belong in {BLUR_HEADER_PATH}")
+    return table
+
+
+BLUR_SIGNATURES = _blur_signatures()
+
 _lib = None
 
 
@@ -115,7 +140,7 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python __graft_entry__.py` (or make -C v-diffusion-torch_amd/csrc). "
                 "The v_diffusion hot path has no CPU/PyTorch fallback.")
         l = C.CDLL(LIB_PATH)
-        for name, (res, args) in (*_SIGNATURES.items(), *PHEMA_SIGNATURES.items()):
+        for name, (res, args) in (*_SIGNATURES.items(), *PHEMA_SIGNATURES.items(), *BLUR_SIGNATURES.items()):
             fn = getattr(l, name)           # AttributeError if the symbol is missing
             fn.restype, fn.argtypes = res, args
         for name, (res, args) in PROBE_EXPORTS.items():
@@ -1028,6 +1053,24 @@ def dps_residual(xt, out, meas, mask, k8, mot, cfg, clip, op, par, dout, dxt, su
     arr = _host_floats(k8, 8)
     _check(lib().vd_dps_residual(ptr(xt), ptr(out), ptr(meas), ptr(mask), arr, mot, int(cfg), int(clip), int(op), int(par), ptr(dout),
                                  ptr(dxt), ptr(sumsq), ptr(x0hat), n, Cc, H, W, stream()), "vd_dps_residual")
+
+
+BLUR_KMAX, BLUR_PLANE_MAX = 33, 4096         # VDX_BLUR_KMAX, VDX_BLUR_PLANE_MAX of include/vdiff_blur.h (tests/test_blur_cpu.py holds them together)
+
+
+def dps_residual_blur(xt, out, meas, taps, k8, mot, cfg, clip, dout, dxt, sumsq, x0hat, n, Cc, H, W):
+    """dps_residual for the blur operator (vdx_dps_residual_blur): taps = the (kh, kw) kernel on the device, fp32 contiguous, one for every
+    sample and channel; cross-correlation, reflect boundary; meas of the image's shape.  The outputs are dps_residual's"""
+    arr = _host_floats(k8, 8)
+    _check(lib().vdx_dps_residual_blur(ptr(xt), ptr(out), ptr(meas), ptr(taps), arr, mot, int(cfg), int(clip), int(taps.shape[0]),
+                                       int(taps.shape[1]), ptr(dout), ptr(dxt), ptr(sumsq), ptr(x0hat), n, Cc, H, W, stream()),
+           "vdx_dps_residual_blur")
+
+
+def blur_planes(x, taps, adjoint, y, planes, H, W):
+    """y = A x, or A^T x with ``adjoint``, of ``planes`` planes of H x W floats under the blur operator of ``taps`` (vdx_blur_planes)"""
+    _check(lib().vdx_blur_planes(ptr(x), ptr(taps), int(taps.shape[0]), int(taps.shape[1]), int(bool(adjoint)), ptr(y), planes, H, W, stream()),
+           "vdx_blur_planes")
 
 
 def dps_step(xt, out, noise, dxin, dxt, sumsq, k8, zeta, mot, cfg, last, clip, xn, xdup, n, Cc, HW):

@@ -30,7 +30,7 @@ from . import _hip
 from .chain import refuse_variants
 from .diffusion import _need_cuda
 from .inpaint import jump_coefs, resampling_schedule
-from .restore import ddnm_pinv, open_chain, parse_operator, per_index      # noqa: F401  (ddnm_pinv: v_diffusion.ddnm.ddnm_pinv)
+from .restore import NO_PINV, ddnm_pinv, open_chain, parse_operator, per_index      # noqa: F401  (ddnm_pinv: v_diffusion.ddnm.ddnm_pinv)
 
 
 def ddnm_rule(c2, noise_scale, sigma_y, last, lam=None):
@@ -57,6 +57,8 @@ def _check_inputs(gd, measurement, operator, shape, sigma_y, lam, use_ddim, jump
     """everything that can be refused before a launch; returns (kind, par, mask, sigma_y, the lams or None, the schedule)"""
     refuse_variants(gd, "p_sample_ddnm")
     kind, par, mask, _ = parse_operator(operator, tuple(shape), measurement, "measurement")
+    if kind == "blur":
+        raise NotImplementedError(f"p_sample_ddnm: {NO_PINV}")
     if isinstance(sigma_y, bool) or not isinstance(sigma_y, numbers.Real) or not (math.isfinite(sigma_y) and sigma_y >= 0.0):
         raise ValueError(f"sigma_y must be finite and >= 0, got {sigma_y!r}")
     if sigma_y > 0.0 and use_ddim:

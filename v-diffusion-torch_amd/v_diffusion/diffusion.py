@@ -908,7 +908,9 @@ class GaussianDiffusion:
         """Reverse chain conditioned on a measurement y = A x (+ noise) by Diffusion Posterior Sampling (extension, v_diffusion/dps.py;
         Chung et al. 2023, Algorithm 1): training-free restoration with an existing checkpoint.  ``operator`` names A: ``("mask", mask)``
         -- soft or noisy inpainting, ``mask`` as in ``p_sample_inpaint`` (1 = measured) -- ``("down", f)`` -- box down-sampling by f in
-        {2, 4, 8}, super-resolution -- or ``("gray",)`` -- the channel mean, colourisation.  ``measurement`` is A's image of ``shape`` =
+        {2, 4, 8}, super-resolution -- ``("gray",)`` -- the channel mean, colourisation -- or ``("blur", kernel)`` -- the cross-correlation
+        of every channel with one 2-D float ``kernel`` of odd sides up to 33 taps, reflect boundary, on planes of at most 4096 pixels
+        (``v_diffusion.gaussian_kernel``; its residual launch is vdx_dps_residual_blur).  ``measurement`` is A's image of ``shape`` =
         (B, C, H, W) on the GPU (``v_diffusion.dps_measure(x, operator)`` makes one).  Every step is the ordinary posterior step (DDPM, or
         DDIM with ``use_ddim``) followed by x <- x - zeta * grad_{x_t} ||y - A x0_hat(x_t)||, x0_hat the step's guided, clipped
         prediction: one network call with tape, one launch for the residual and its cotangents (vd_dps_residual), the network's input
@@ -929,7 +931,8 @@ class GaussianDiffusion:
         """Reverse chain conditioned on a measurement y = A x (+ noise) by the Denoising Diffusion Null-space Model (extension,
         v_diffusion/ddnm.py; Wang, Yu, Zhang 2023): training-free restoration with an existing checkpoint and WITHOUT a gradient.
         ``operator``, ``measurement`` and ``shape`` are ``p_sample_dps``'s: ``("mask", mask)``, ``("down", f)`` or ``("gray",)``, each
-        with a closed-form pseudo-inverse A^+ (``v_diffusion.ddnm_pinv``).  Every step is the ordinary posterior step (DDPM, or DDIM with
+        with a closed-form pseudo-inverse A^+ (``v_diffusion.ddnm_pinv``); ``("blur", kernel)`` is refused (NotImplementedError: its A^+ is
+        an FFT or an SVD, not a per-thread preimage).  Every step is the ordinary posterior step (DDPM, or DDIM with
         ``use_ddim``) on the corrected prediction g + lam * A^+(y - A g), g the step's guided, clipped x0 prediction: one ordinary
         network call and ONE launch (vd_ddnm_step); the last step returns the corrected prediction, so with ``sigma_y=0`` the result
         satisfies A x = y to rounding, and exactly where a mask is 1.  ``sigma_y`` > 0 (the measurement's noise, DDNM+): lam and the

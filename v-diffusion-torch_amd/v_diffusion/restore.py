@@ -9,8 +9,10 @@ import torch.nn.functional as F
 from .chain import Chain
 from .diffusion import _device_ctx
 
-OPERATORS = ("mask", "down", "gray")
+OPERATORS = ("mask", "down", "gray", "blur")
 DOWN_FACTORS = (2, 4, 8)
+BLUR_KMAX = 33                 # the most taps per side of a blur kernel (VDX_BLUR_KMAX of include/vdiff_blur.h)
+NO_PINV = "the pseudo-inverse A^+ of a blur is not a per-thread preimage (it is an FFT or an SVD): DDNM does not take ('blur', kernel)"
 
 
 def mask_channels(mask, shape, what="images"):
@@ -32,10 +34,10 @@ def mask_channels(mask, shape, what="images"):
 
 def parse_operator(operator, shape, y=None, name=None):
     """``(kind, par, mask or None, the shape of A's image)`` of an operator on images of ``shape`` = (B, C, H, W); everything about it
-    that can be refused without a device.  par: the mask's channel count / the down-sampling factor / 0.  With ``name``, ``y`` is
-    held to the shape of A's image under that name."""
+    that can be refused without a device.  par: the mask's channel count / the down-sampling factor / 0 / 0 (the kernel of a blur is
+    ``operator[1]``, held to ``blur_kernel``'s rule here).  With ``name``, ``y`` is held to the shape of A's image under that name."""
     if not isinstance(operator, (tuple, list)) or not operator or operator[0] not in OPERATORS:
-        raise ValueError(f"operator must be ('mask', mask), ('down', f) or ('gray',), got {operator!r}")
+        raise ValueError(f"operator must be ('mask', mask), ('down', f), ('gray',) or ('blur', kernel), got {operator!r}")
     if len(shape) != 4 or any(isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < 1 for v in shape):
         raise ValueError(f"shape must be (B, C, H, W) of positive integers, got {tuple(shape)!r}")
     B, C, H, W = (int(v) for v in shape)
@@ -51,6 +53,9 @@ def parse_operator(operator, shape, y=None, name=None):
         if H % f or W % f:
             raise ValueError(f"the down-sampling factor {f} must divide H = {H} and W = {W}")
         par, mask, mshape = int(f), None, (B, C, H // f, W // f)
+    elif kind == "blur":
+        blur_kernel(operator[1], H, W)
+        par, mask, mshape = 0, None, (B, C, H, W)
     else:
         par, mask, mshape = mask_channels(operator[1], (B, C, H, W)), operator[1], (B, C, H, W)
     if name is not None and (not torch.is_tensor(y) or tuple(y.shape) != mshape):
@@ -59,10 +64,42 @@ def parse_operator(operator, shape, y=None, name=None):
     return kind, par, mask, mshape
 
 
+def blur_kernel(kernel, H, W):
+    """the rule of the kernel of ``("blur", kernel)`` on H x W images: a 2-D floating tensor (Kh, Kw), both sides odd and at most
+    ``BLUR_KMAX``, every tap finite, the radii (Kh-1)/2 <= H-1 and (Kw-1)/2 <= W-1 (the reflect boundary needs them inside the image).
+    Returns (Kh, Kw)."""
+    if not torch.is_tensor(kernel) or kernel.dim() != 2 or not kernel.dtype.is_floating_point:
+        raise ValueError(f"the kernel of the 'blur' operator must be a 2-D floating tensor (Kh, Kw), got "
+                         f"{tuple(kernel.shape) if torch.is_tensor(kernel) else kernel!r}"
+                         f"{' of ' + str(kernel.dtype) if torch.is_tensor(kernel) else ''}")
+    kh, kw = (int(v) for v in kernel.shape)
+    if kh % 2 != 1 or kw % 2 != 1 or kh > BLUR_KMAX or kw > BLUR_KMAX:
+        raise ValueError(f"the kernel of the 'blur' operator has odd sides of at most {BLUR_KMAX} taps, got {kh} x {kw}")
+    if not bool(torch.isfinite(kernel).all()):
+        raise ValueError("the kernel of the 'blur' operator has a tap that is not finite")
+    if kh // 2 > H - 1 or kw // 2 > W - 1:
+        raise ValueError(f"the radii {kh // 2}, {kw // 2} of the 'blur' operator's kernel do not fit a {H} x {W} image (at most H - 1, W - 1)")
+    return kh, kw
+
+
+def gaussian_kernel(size, std):
+    """the (size, size) fp32 Gaussian blur kernel of the DPS experiments: taps exp(-d^2 / (2 std^2)) at the distances d from the centre in
+    fp64, their outer product, divided by its fp64 sum, rounded to fp32 once.  ``size`` odd, 1 ... ``BLUR_KMAX``; ``std`` finite, > 0."""
+    if isinstance(size, bool) or not isinstance(size, numbers.Integral) or size < 1 or size > BLUR_KMAX or size % 2 != 1:
+        raise ValueError(f"size must be an odd integer in 1 ... {BLUR_KMAX}, got {size!r}")
+    if isinstance(std, bool) or not isinstance(std, numbers.Real) or not (std > 0.0 and std < float("inf")):
+        raise ValueError(f"std must be finite and > 0, got {std!r}")
+    d = torch.arange(int(size), dtype=torch.float64) - (int(size) - 1) / 2
+    g = torch.exp(-(d * d) / (2.0 * float(std) ** 2))
+    k = torch.outer(g, g)
+    return (k / k.sum()).to(torch.float32)
+
+
 def dps_measure(x, operator):
     """A x of an image batch ``x`` (B, C, H, W) with plain torch operations on ``x``'s device: M (.) x for ``("mask", mask)``, the mean
-    over f x f blocks for ``("down", f)``, the channel mean (B, 1, H, W) for ``("gray",)``.  Not hot path: it makes the measurement a
-    caller hands to ``p_sample_dps`` (adding the measurement noise is the caller's)."""
+    over f x f blocks for ``("down", f)``, the channel mean (B, 1, H, W) for ``("gray",)``, the depthwise cross-correlation with the
+    kernel after reflect padding for ``("blur", kernel)``.  Not hot path: it makes the measurement a caller hands to ``p_sample_dps``
+    (adding the measurement noise is the caller's)."""
     if not torch.is_tensor(x) or x.dim() != 4:
         raise ValueError(f"x must be a (B, C, H, W) tensor, got shape {tuple(getattr(x, 'shape', ()))}")
     kind, par, mask, _ = parse_operator(operator, tuple(x.shape))
@@ -70,6 +107,10 @@ def dps_measure(x, operator):
         return mask.to(device=x.device, dtype=x.dtype) * x
     if kind == "down":
         return F.avg_pool2d(x, par)
+    if kind == "blur":
+        k = operator[1].to(device=x.device, dtype=x.dtype)
+        C, (kh, kw) = x.shape[1], k.shape
+        return F.conv2d(F.pad(x, (kw // 2, kw // 2, kh // 2, kh // 2), mode="reflect"), k.expand(C, 1, kh, kw), groups=C)
     return x.mean(dim=1, keepdim=True)
 
 
@@ -79,6 +120,8 @@ def ddnm_pinv(y, operator, shape):
     over the C channels for ``("gray",)`` (both means: A^+ copies).  The companion of ``dps_measure``: A A^+ y = y on the range of A.
     Not hot path."""
     kind, par, mask, mshape = parse_operator(operator, tuple(shape), y, "y")
+    if kind == "blur":
+        raise NotImplementedError(f"ddnm_pinv: {NO_PINV}")
     if kind == "mask":
         m = mask.to(device=y.device, dtype=y.dtype).expand(mshape)
         return torch.where(m > 0, y / torch.where(m > 0, m, torch.ones_like(m)), torch.zeros_like(y))
